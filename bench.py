@@ -16,6 +16,12 @@ Other BASELINE.json configs (--config c1|c3|c4|c5; c2 is the default): c1 Cornel
 spatial passes + temporal reuse threading each frame's grid into the next (1 GPU), c4 4K / 1024 lights and
 c5 8K / 4096 lights / M=64 / unbiased + visibility reuse (strong scaling: the image is fixed and split).
 
+A plain run (--gpus, --steps, --warmup, --config) sets up, warms up, times the steps and prints the line: value,
+ms_per_step and the spatial pass's roofline, whose launch times are read inside the timed region.  --full adds what
+takes runs of its own: the streaming-read ceiling, the per-kernel run (kernels, roofline_ris, roofline_rays, balance),
+the CPU baseline and, at N > 1, the halo self-check.  --dump-outputs DIR writes what the last timed step computed as
+.npy files (the inputs are fixed by the config and the keyed RNG seed, so two builds compare output for output).
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -56,7 +62,8 @@ def parse():
     ap.add_argument("--passes", type=int, default=None, help="override the config's spatial passes")
     ap.add_argument("--tile-width", type=int, default=None)
     ap.add_argument("--tile-height", type=int, default=None)
-    ap.add_argument("--cpu-baseline", dest="cpu_baseline", action="store_true", default=True)
+    ap.add_argument("--cpu-baseline", dest="cpu_baseline", action="store_true", default=True,
+                    help="with --full: the oracle's rate on the same workload (cpu_baseline)")
     ap.add_argument("--no-cpu-baseline", dest="cpu_baseline", action="store_false")
     ap.add_argument("--no-cpu-stages", dest="cpu_stages", action="store_false", default=True,
                     help="skip cpu_baseline.stages (per-stage oracle rates for C1 and C2)")
@@ -70,7 +77,8 @@ def parse():
     ap.add_argument("--halo-check", default="auto", choices=["auto", "on", "off"],
                     help="N > 1: before timing, render one frame of this rank's tile through the RCCL reservoir halo "
                          "(HaloFrames) and through the ghost zone, require them bit-identical (exit 3 otherwise) and "
-                         "time the halo-mode frame and its exchange (auto = on when the frame has spatial passes)")
+                         "time the halo-mode frame and its exchange with --full (auto = on under --full when the frame has "
+                         "spatial passes)")
     ap.add_argument("--halo-transport", default="auto", choices=["auto", "native", "torch"],
                     help="halo transport: the library's own RCCL communicator (native), torch.distributed p2p (torch); "
                          "auto = native under nccl, torch under gloo")
@@ -93,7 +101,37 @@ def parse():
                     help="restir_set_tuning knobs for A/B runs (launch shapes and timing only; results are identical)")
     ap.add_argument("--traffic-csv", default=None,
                     help="rocprofv3 --pmc CSV (FETCH_SIZE / WRITE_SIZE) of this command for roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything that takes runs of its own beside the headline: the streaming-read ceiling "
+                         "(roofline.measured_read_peak), the per-kernel run (kernels, roofline_ris, roofline_rays, balance), "
+                         "the CPU baseline and its stages (cpu_baseline) and, at N > 1, the halo self-check and its timings "
+                         "(halo).  Without it a run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: this rank's RGB "
+                         "tile (rgb; rgb.rank<i> at N > 1) and, with temporal reuse, the reservoir grid it hands to the next "
+                         "frame (grid_pos, grid_color, grid_W, grid_M); at most 64 MB in all (see dump_outputs)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 60 << 20   # array bytes: under 64 MB (10^6 bytes) with the .npy headers
+DUMP_SEED = 0x5EED0001
+
+
+def dump_outputs(path, arrays, ranks=1):
+    """--dump-outputs: each array as path/<name>.npy, float32 as it is and integers as float64 (exact).  When the arrays
+    of all ranks would pass DUMP_BUDGET_BYTES, an array larger than its equal share of that is cut to the share: a
+    fixed, seeded sample of its flattened elements in index order, so two runs with the same arguments store the same
+    elements."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    share = DUMP_BUDGET_BYTES // max(1, ranks * len(arrays))
+    over = ranks * sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, size=share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def dist_setup(n_gpus, backend="nccl"):
@@ -450,7 +488,7 @@ def select_halo(torch, world, local, backend, transport, make, check):
 
 
 def halo_frames(torch, r, rank, world, local, f, cam, GW, GH, tx, ty, passes, args, transport, check_on, fatal=True,
-                layout=None):
+                layout=None, timed=True):
     """N > 1 with spatial passes: this rank's tile rendered through the reservoir halo exchange (HaloFrames: interior
     launched while the border reservoirs move, border strips after) must equal, bit for bit, the same tile rendered
     with a ghost zone (restir_render on tile + passes * r) -- exits 3 on any mismatch (check_on).  Then the halo-mode
@@ -458,7 +496,8 @@ def halo_frames(torch, r, rank, world, local, f, cam, GW, GH, tx, ty, passes, ar
     Returns (hf, rec): the verified HaloFrames -- the halo-mode main loop (c4 / c5, --mode halo) times this instance,
     so the run never times a transport other than the one it checked -- and the JSON record.  fatal = False (the halo
     is only checked, as with c2's ghost-zone frames at N > 1): a mismatch, or a render error that every rank sees as one,
-    is recorded and the run goes on (returns hf None) -- the timed frames do not use the halo."""
+    is recorded and the run goes on (returns hf None) -- the timed frames do not use the halo.  timed = False (a run
+    without --full): the halo-mode frames and the exchange are not timed here."""
     from romis_amd import _abi, distributed, restir
     fc = _abi.Features.from_buffer_copy(f)
     fc.temporal_reuse = 0
@@ -501,6 +540,8 @@ def halo_frames(torch, r, rank, world, local, f, cam, GW, GH, tx, ty, passes, ar
             print(json.dumps({"error": "halo tile differs from the ghost-zone tile", "halo": rec}), flush=True)
         torch.distributed.barrier()
         sys.exit(3)
+    if not timed:
+        return hf, rec
     # halo-mode frames, timed like the main loop (max over ranks)
     k = max(5, min(args.steps, 20))
     for _ in range(2):
@@ -586,11 +627,12 @@ def main():
         transport = "native" if args.dist_backend == "nccl" else "torch"
     hf = None
     halo_rec = None
-    check_on = world > 1 and passes > 0 and args.halo_check != "off"
+    # the self-check renders frames of its own: --halo-check auto runs it with --full only
+    check_on = world > 1 and passes > 0 and (args.halo_check == "on" or (args.halo_check == "auto" and args.full))
     if halo or check_on:
         # one HaloFrames per run, chosen and verified by halo_frames (select_halo); the halo-mode loop times it
         hf_checked, halo_rec = halo_frames(torch, r, rank, world, local, f, cam, GW, GH, tx, ty, passes, args, transport,
-                                           check_on, fatal=halo, layout=layout)
+                                           check_on, fatal=halo, layout=layout, timed=args.full)
         r.set_seed(_abi.RESTIR_DEFAULT_SEED, 0)
         if halo:
             hf = hf_checked
@@ -607,9 +649,9 @@ def main():
         else:
             r.render_restir(None, cam, GW, GH, f, tile=tile, want_rgb=False, want_grid=False)
 
-    # the practical HBM-read ceiling reported beside the roofline, then the GPU clock pre-warm (not a frame, not timed)
-    # right before the warm-up frames
-    measured = r.measure_read_bandwidth(4 << 30, 10)
+    # the practical HBM-read ceiling reported beside the roofline (--full), then the GPU clock pre-warm (not a frame, not
+    # timed) right before the warm-up frames
+    measured = r.measure_read_bandwidth(4 << 30, 10) if args.full else None
     if args.prewarm_gemm_ms > 0:
         gemm_prewarm(torch, local, args.prewarm_gemm_ms)
     for _ in range(args.warmup):
@@ -631,22 +673,33 @@ def main():
     r.enable_timing(False)
     elapsed = max_over_ranks(torch, world, t1 - t0, local)
     kt = r.timings()
-    # per-kernel breakdown: serial frames (no overlap), every launch timed
-    r.reset_timings()
-    r.set_tuning("timing.mask", -1)
-    r.set_tuning("timing.every", 1)
-    r.enable_timing(True)
-    for _ in range(min(args.steps, 20)):
-        step()
-    r.synchronize()
-    r.enable_timing(False)
-    kt_all = r.timings()
+    if args.dump_outputs:
+        # what the last timed step left: the frame's RGB stays on the device (want_rgb = False), the temporal configs'
+        # grid is the handle the step returned
+        sfx = f".rank{rank}" if world > 1 else ""
+        arrays = {"rgb" + sfx: r.download_rgb(tile.width, tile.height)}
+        if state["grid"] is not None:
+            arrays.update(zip([n + sfx for n in ("grid_pos", "grid_color", "grid_W", "grid_M")], state["grid"].download()))
+        dump_outputs(args.dump_outputs, arrays, world)
+        del arrays
+    kt_all = {}
+    if args.full:
+        # per-kernel breakdown: serial frames (no overlap), every launch timed
+        r.reset_timings()
+        r.set_tuning("timing.mask", -1)
+        r.set_tuning("timing.every", 1)
+        r.enable_timing(True)
+        for _ in range(min(args.steps, 20)):
+            step()
+        r.synchronize()
+        r.enable_timing(False)
+        kt_all = r.timings()
     bg_info = r.background_pixels()
     # per-rank GPU kernel time per frame of that run (the balance of the tile layout, measured): gathered to rank 0
     n_kf = max(1, min(args.steps, 20))
     busy_ms = sum(v[0] for v in kt_all.values()) / n_kf
     rank_busy = [busy_ms]
-    if world > 1:
+    if world > 1 and args.full:
         on_gpu = torch.distributed.get_backend() == "nccl"
         bt = torch.tensor([busy_ms], dtype=torch.float64, device=torch.device("cuda", local) if on_gpu else "cpu")
         outs = [torch.zeros_like(bt) for _ in range(world)]
@@ -701,9 +754,10 @@ def main():
             # the survey's read-only bar (§8d: 64 B/px, <= 41.5 us at 1080p for 0.40)
             roofline["read_only_bar_us"] = round(sp_px * (32 + 32 * args.N) / (0.40 * HBM_PEAK_GBS * 1e9) * 1e6, 2)
         # the practical ceiling next to the spec: a streaming-read kernel over 4 GiB (past the Infinity Cache), run
-        # before the warm-up frames
-        roofline["measured_read_peak"] = round(measured, 1)
-        roofline["frac_of_measured_peak"] = round(achieved / measured, 4)
+        # before the warm-up frames (--full)
+        if measured is not None:
+            roofline["measured_read_peak"] = round(measured, 1)
+            roofline["frac_of_measured_peak"] = round(achieved / measured, 4)
         if cf.get("geometry") is not None:
             # the TOML camera's C4 / C5 frame (profiles/r5/balance.json: 13.2 % of the pixels hit the box): background
             # tiles are written from the RIS flags without reads, so frac is an algorithmic rate, not bytes moved and
@@ -712,7 +766,7 @@ def main():
             roofline["frac_kind"] = "algorithmic rate over a background-dominated frame (not a roofline; see c4f / c5f)"
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline:
         rows = args.cpu_rows or min(GH, max(8, 1036800 // GW))   # ~1 Mpx of the workload, ~0.3 s on 16 cores
         cpu = cpu_baseline(sc, lambda w, h: scene.camera_for(cf["scene"], w, h, cf.get("camera")), f, rows, GW, GH)
         if args.cpu_stages:
@@ -763,7 +817,10 @@ def main():
                          "final_grays_per_s": round(px * args.N / (fms / fn * 1e-3) / 1e9, 2),
                          "note": "ray slots = (k+1) N per pixel, an upper bound on the shadow rays cast; final = 1 per "
                                  "pixel and sub-reservoir (also an upper bound: no ray where the shaded value is 0)"}
-    kernels["note"] = "separate run after the timed region, every kernel's dispatch recording HIP events"
+    if args.full:
+        kernels["note"] = "separate run after the timed region, every kernel's dispatch recording HIP events"
+    else:   # no per-kernel run: roofline_ris / roofline_rays, computed from it, are None too
+        kernels = None
     # every rank computed the same mismatch count (select_halo sums it over ranks): all exit alike
     halo_failed = halo_rec is not None and halo_rec.get("check") not in ("bit-exact", "off")
     if rank == 0:
@@ -774,6 +831,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": scaling,
@@ -787,7 +845,7 @@ def main():
             "cpu_baseline": cpu,
             "kernels": kernels,
         }
-        if world > 1:
+        if world > 1 and args.full:
             out["balance"] = {"kernel_ms_per_frame_per_rank": [round(v, 4) for v in rank_busy],
                               "efficiency": round(float(np.mean(rank_busy) / max(rank_busy)), 4) if max(rank_busy) > 0 else None,
                               "note": "GPU kernel time per frame on each rank (HIP events, the per-kernel run): mean / max "

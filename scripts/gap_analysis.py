@@ -5,7 +5,7 @@ consecutive kernels of a frame and between frames, for every frame in dispatch o
     python scripts/gap_analysis.py <run_kernel_trace.csv> [--warmup W --steps K]
 
 A frame = the kernels from one k_primary_ris* dispatch up to the next.  With --warmup / --steps the frames are
-labelled (bench.py renders W warm-up frames, K timed ones, then min(K, 20) all-kernel-timed ones).  Prints one
+labelled (bench.py renders W warm-up frames, K timed ones, then with --full min(K, 20) all-kernel-timed ones).  Prints one
 JSON object: per-frame spans, and averages over the timed frames (kernel sum, in-frame gaps, frame-to-frame gap).
 """
 import argparse

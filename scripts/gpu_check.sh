@@ -18,5 +18,5 @@ fi
 tail -3 "$OUT/tests.log"
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { cat "$OUT/smoke.log"; exit 22; }
 cat "$OUT/smoke.log"
-timeout -k 10 300 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 23; }
+timeout -k 10 300 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 23; }
 cat "$OUT/bench.json"

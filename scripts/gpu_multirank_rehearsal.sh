@@ -17,7 +17,7 @@ RUNS+=("c5:2")
 for R in "${RUNS[@]}"; do
     CFG=${R%%:*}; N=${R#*:}
     timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 \
-        --master-port $PORT bench.py --config $CFG --gpus "$N" --dist-backend gloo --steps 10 --warmup 2 --no-cpu-baseline \
+        --master-port $PORT bench.py --config $CFG --gpus "$N" --dist-backend gloo --steps 10 --warmup 2 --full --no-cpu-baseline \
         > "$OUT/${CFG}_n$N.json" 2> "$OUT/${CFG}_n$N.err" || { tail -20 "$OUT/${CFG}_n$N.err"; exit 31; }
     cat "$OUT/${CFG}_n$N.json"
     PORT=$((PORT + 1))

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Profile the headline bench on the GPU box (run through gpurun from the repo root).
 #   scripts/gpu_profile.sh <tag>
-# Writes under gpurun_out/<tag>/: bench.json (plain run), the rocprofv3 kernel-trace + stats of the same
-# command, and two separate --pmc passes (FETCH_SIZE, WRITE_SIZE: they do not fit one pass on gfx950).
+# Writes under $OUT (one directory per <tag>): bench.json (the --full run, no profiler), the rocprofv3 kernel-trace +
+# stats of the same frames without --full, and two separate --pmc passes (FETCH_SIZE, WRITE_SIZE: they do not fit one pass on gfx950).
 set -o pipefail
 TAG=${1:-prof}
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -13,8 +13,8 @@ cd "$REPO" || exit 1
 BENCH_ARGS=${BENCH_ARGS:-"--steps 50 --warmup 5"}
 
 python3 -c "from romis_amd import build; print(build.source_hash())" > "$OUT/source_hash.txt" || exit 10
-echo "[profile] plain bench" >&2
-timeout -k 10 300 python3 bench.py $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 11
+echo "[profile] full bench" >&2
+timeout -k 10 300 python3 bench.py $BENCH_ARGS --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 11
 cat "$OUT/bench.json"
 
 echo "[profile] kernel trace + stats" >&2
