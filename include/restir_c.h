@@ -550,7 +550,10 @@ restir_status restir_enable_timing(restir_ctx* ctx, int enable);
  * shadow rays walk 16-byte quantized BVH nodes: 0 never, 1 always, 2 = at N = 2, the default), "primary.tl" (the fused
  * primary + RIS kernel's primary rays test their 32x8 tile's candidate triangles -- those not wholly outside the tile's
  * ray pyramid -- instead of walking the BVH; default 1), "ris.late" (stage the light table after the primary rays, only
- * for tiles that need it), "final.sort" (bin each tile's shadow rays by target), "final.miss" (final shading reads only p_mat and
+ * for tiles that need it), "final.sort" (bin each tile's shadow rays by target), "final.fuse" (restir_render shades
+ * inside the last N = 1 point-light handle pass, k_spatial1hg_t2_final, where that pass and the binned final kernel would
+ * both run -- timed as RESTIR_K_SPATIAL, RESTIR_K_FINAL then has no launches; 0: always two kernels; default 1),
+ * "final.miss" (final shading reads only p_mat and
  * (pos, W) for a primary-ray miss), "miss.tiles" (background-tile flags from RIS to the spatial passes and final
  * shading, N <= 2 without temporal reuse), "miss.gbuf" (0 / 1 / 2 = auto: RIS also skips background tiles' G-buffer
  * stores), "timing.every" / "timing.fence" (event sampling), "mis.chunk" (R-OMIS samples per launch pair).  All default

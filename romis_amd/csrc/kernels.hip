@@ -1388,16 +1388,37 @@ __device__ __forceinline__ void h_stage(const SceneDev& s, const Region& rg, con
     if (threadIdx.x < 2u) l_lt[threadIdx.x ? 2u * L + 1u : L] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
-// HG (round 6 probe): the handles are gathered from global memory (the own pixel's coalesced, an accepted
-// neighbour's one 4 + 4 B gather) instead of staged in LDS: the block's LDS is the n_t window and the light table only
-// (34 KB at 32 x 16: four blocks of 8 waves per CU instead of three)
-template <bool DBG, uint32_t TH = 1, bool HG = false>
+// The final-shading output of a fused last pass (k_spatial1hg_t2_final): the RGB rows of the pass's rect (row 0 = its
+// top, k_final's layout) and final.miss (launch_final's sf.miss_shade_zero)
+struct FinalOut { float* rgb; uint32_t miss; };
+// LDS of the fused kernel's ray phase, in float4 behind the staged BVH: s_from and s_to (512 rays), s_vis (512 words),
+// the 256 bin counts, the four wave totals of their scan
+constexpr uint32_t kFinRays = 512u;
+constexpr uint32_t kFinLdsF4 = 2u * kFinRays + kFinRays / 4u + 256u / 4u + 1u;
+// (defined with final shading below)
+__device__ __forceinline__ void fin_store_background(const Region& rg, const FeaturesDev& f, const FinalOut& fin, int x, int y);
+__device__ __forceinline__ void fin_shade_block(const SceneDev& s, const Region& rg, const FeaturesDev& f, const FinalOut& fin,
+                                                const GlTabs& tb, bool live, bool own_bg, int tx0, int ty0, uint32_t wave, const Px& px,
+                                                bool pm_miss, v3 pos, v3 col, float W);
+
+// HG (the default 32 x 16 form since round 6): the handles are gathered from global memory (the own pixel's coalesced,
+// an accepted neighbour's one 4 + 4 B gather) instead of staged in LDS: the block's LDS is the n_t window and the light
+// table only (34 KB at 32 x 16: four blocks of 8 waves per CU instead of three)
+// FIN (k_spatial1hg_t2_final, the last pass at N = 1): the block goes on to shade its own 32 x 16 pixels as
+// final_sorted_body<true, 1> does, from the reservoir it just combined (still in registers) and the G-buffer records it
+// already holds -- no reservoir round trip, no G-buffer re-read, no second launch.  Every lane of a non-background
+// block reaches the ray phase's barriers: a lane that would have left early (outside the rect, the miss material)
+// carries the reservoir it would have written instead.  After the combine the window and the light table are dead;
+// their bytes hold the BVH, the binned rays and the histogram (one barrier between the two uses).
+template <bool DBG, uint32_t TH = 1, bool HG = false, bool FIN = false>
 __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key,
                                                v3 origin, const float4* __restrict__ n_t, const float4* __restrict__ p_mat,
                                                HandlesIn hi, float4* __restrict__ oa, float4* __restrict__ ob,
                                                float2* __restrict__ odbg, const float* __restrict__ rp_in,
                                                float* __restrict__ rp_out, float* __restrict__ how,
-                                               uint32_t* __restrict__ hom, MissTiles mt, uint32_t odead) {
+                                               uint32_t* __restrict__ hom, MissTiles mt, uint32_t odead,
+                                               FinalOut fin = FinalOut{nullptr, 0u}) {
+    static_assert(!FIN || (!DBG && TH == 2u && HG), "the fused form is the 32 x 16 gather pass without a debug plane");
     constexpr uint32_t kTH = kTileH * TH;
     float4* const l_nt = g_lds;
     float* const l_w = reinterpret_cast<float*>(g_lds + apron_max(TH));
@@ -1423,6 +1444,7 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
                 if (DBG) st_at(odbg, mp << 3, make_float2(ROMIS_FLT_MIN, 0.0f));
                 if (rp_out) rp_out[mp] = 0.0f;
                 if (how) { how[mp] = 0.0f; hom[mp] = mt.m | (L << 24); }
+                if (FIN) fin_store_background(rg, f, fin, mx, my);   // final_sorted_body's miss-tile branch
             }
             return;
         }
@@ -1483,73 +1505,95 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
         }
     }
     __syncthreads();
-    if (!live) return;   // no barrier follows
-    const uint32_t own = (uint32_t)(y - ay0) * AW + (uint32_t)(x - ax0);
-    const float4 cn = l_nt[own];
-    const float cw = own_bg ? 0.0f : (HG ? gw : l_w[own]);
-    const uint32_t cm = own_bg ? (mt.m | (L << 24)) : (HG ? gm : l_m[own]);
-    const uint32_t cli = cm >> 24;
-    const v3 cpos = xyz(l_lt[cli]), ccol = xyz(l_lt[L + 1u + cli]);
-    const Px cur = make_px(s, cn, cpm, origin, pix);
-    if (cur.mat == s.num_materials - 1u && s.normals_bounded && !__builtin_isnan(cur.P.x + cur.P.y + cur.P.z) &&
-        __builtin_isfinite(cw) && __builtin_isfinite(ccol.x + ccol.y + ccol.z)) {
-        if (!odead) {
-            st_at(oa, pix << 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-            st_at(ob, pix << 4, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(cm & kHandleM)));
+    // FIN: the reservoir a live lane's combine leaves -- what the planes receive -- and its shading context, for the
+    // block's final shading below
+    Px rpx;
+    v3 rpos = mk(0.0f, 0.0f, 0.0f), rcol = mk(0.0f, 0.0f, 0.0f);
+    float rW = 0.0f;
+    uint32_t wave = 0u;
+    if constexpr (FIN) wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    bool pm_miss = false;   // final_sorted_body's miss test, the part on p_mat (decided here: a flag, not pm.w, stays live)
+    if constexpr (FIN) {
+        if (fin.miss && s.miss_shade_zero) {
+            const uint32_t m = min(__float_as_uint(cpm.w), s.num_materials - 1u);
+            pm_miss = m == s.num_materials - 1u && !__builtin_isnan(cpm.x + cpm.y + cpm.z);
         }
-        if (DBG) st_at(odbg, pix << 3, make_float2(ROMIS_FLT_MIN, 0.0f));
-        if (rp_out) rp_out[pix] = 0.0f;
-        if (how) { how[pix] = 0.0f; hom[pix] = (cm & kHandleM) | (L << 24); }
-        return;
     }
-    const double rt = rcp_d(cur.t);
-    const bool rt_all = __all(div_fast_ok(cur.t));
-    bool ok[kLeanK];
-    uint32_t qm[kLeanK];
-    float qw[kLeanK];
-#pragma unroll
-    for (uint32_t n = 0; n < kLeanK; n++) {
-        ok[n] = false;
-        qm[n] = 0u;
-        qw[n] = 0.0f;
-        if (n < K) {
-            const float4 g = l_nt[qi[n]];
-            if (!HG) {
-                qm[n] = l_m[qi[n]];
-                qw[n] = l_w[qi[n]];
+    if (!live) {   // no barrier follows (FIN: the ray phase's do)
+        if constexpr (FIN) goto shade; else return;
+    }
+    {
+        const uint32_t own = (uint32_t)(y - ay0) * AW + (uint32_t)(x - ax0);
+        const float4 cn = l_nt[own];
+        const float cw = own_bg ? 0.0f : (HG ? gw : l_w[own]);
+        const uint32_t cm = own_bg ? (mt.m | (L << 24)) : (HG ? gm : l_m[own]);
+        const uint32_t cli = cm >> 24;
+        const v3 cpos = xyz(l_lt[cli]), ccol = xyz(l_lt[L + 1u + cli]);
+        const Px cur = make_px(s, cn, cpm, origin, pix);
+        if constexpr (FIN) rpx = cur;
+        if (cur.mat == s.num_materials - 1u && s.normals_bounded && !__builtin_isnan(cur.P.x + cur.P.y + cur.P.z) &&
+            __builtin_isfinite(cw) && __builtin_isfinite(ccol.x + ccol.y + ccol.z)) {
+            if (!odead) {
+                st_at(oa, pix << 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+                st_at(ob, pix << 4, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(cm & kHandleM)));
             }
-            const float nd = vdot(xyz(g), cur.N);
-            float q = div_by_rcp_d(g.w, rt);
-            if (__builtin_expect(!rt_all, 0)) {
-                if (!div_fast_ok(cur.t)) q = g.w / cur.t;
-            }
-            ok[n] = !(nd < 0.90630778703f) && !(fabsf(1.0f - q) > 0.1f);
-            if (HG && ok[n]) { qm[n] = hi.m[qp[n]]; qw[n] = hi.w[qp[n]]; }
+            if (DBG) st_at(odbg, pix << 3, make_float2(ROMIS_FLT_MIN, 0.0f));
+            if (rp_out) rp_out[pix] = 0.0f;
+            if (how) { how[pix] = 0.0f; hom[pix] = (cm & kHandleM) | (L << 24); }
+            if constexpr (FIN) goto shade; else return;   // FIN: with the (0, 0), W = 0 reservoir just written
         }
-    }
-    const float pd_cur = rp_in ? pd_cached : target_pdf(s, f, cur, cpos, ccol, tb);
-    Comb1h cmb;
-    cmb.wsum = ROMIS_FLT_MIN; cmb.chosen = 0.0f; cmb.pd = 0.0f; cmb.macc = 0u; cmb.li = L; cmb.has_pd = false;
-    cmb.h = ps + 2u * K * 0x9E3779B9u;
+        const double rt = rcp_d(cur.t);
+        const bool rt_all = __all(div_fast_ok(cur.t));
+        bool ok[kLeanK];
+        uint32_t qm[kLeanK];
+        float qw[kLeanK];
 #pragma unroll
-    for (uint32_t n = 0; n < kLeanK; n++) {
-        if (ok[n]) {
-            const uint32_t li = qm[n] >> 24;
-            cmb.take(target_pdf(s, f, cur, xyz(l_lt[li]), xyz(l_lt[L + 1u + li]), tb), qw[n], qm[n] & kHandleM, li);
+        for (uint32_t n = 0; n < kLeanK; n++) {
+            ok[n] = false;
+            qm[n] = 0u;
+            qw[n] = 0.0f;
+            if (n < K) {
+                const float4 g = l_nt[qi[n]];
+                if (!HG) {
+                    qm[n] = l_m[qi[n]];
+                    qw[n] = l_w[qi[n]];
+                }
+                const float nd = vdot(xyz(g), cur.N);
+                float q = div_by_rcp_d(g.w, rt);
+                if (__builtin_expect(!rt_all, 0)) {
+                    if (!div_fast_ok(cur.t)) q = g.w / cur.t;
+                }
+                ok[n] = !(nd < 0.90630778703f) && !(fabsf(1.0f - q) > 0.1f);
+                if (HG && ok[n]) { qm[n] = hi.m[qp[n]]; qw[n] = hi.w[qp[n]]; }
+            }
         }
+        const float pd_cur = rp_in ? pd_cached : target_pdf(s, f, cur, cpos, ccol, tb);
+        Comb1h cmb;
+        cmb.wsum = ROMIS_FLT_MIN; cmb.chosen = 0.0f; cmb.pd = 0.0f; cmb.macc = 0u; cmb.li = L; cmb.has_pd = false;
+        cmb.h = ps + 2u * K * 0x9E3779B9u;
+#pragma unroll
+        for (uint32_t n = 0; n < kLeanK; n++) {
+            if (ok[n]) {
+                const uint32_t li = qm[n] >> 24;
+                cmb.take(target_pdf(s, f, cur, xyz(l_lt[li]), xyz(l_lt[L + 1u + li]), tb), qw[n], qm[n] & kHandleM, li);
+            }
+        }
+        cmb.take(pd_cur, cw, cm & kHandleM, cli);
+        const v3 pos = xyz(l_lt[cmb.li]), col = xyz(l_lt[L + 1u + cmb.li]);
+        float p = cmb.pd;
+        if (!cmb.has_pd) p = (f.shading && !__builtin_isnan(cur.P.x + cur.P.y + cur.P.z)) ? 0.0f : target_pdf(s, f, cur, pos, col, tb);
+        const float W = contribution_weight(p, cmb.macc, cmb.wsum);
+        if (!odead) {   // odead: a later handle pass is the output's only reader
+            st_at(oa, pix << 4, make_float4(pos.x, pos.y, pos.z, W));
+            st_at(ob, pix << 4, make_float4(col.x, col.y, col.z, __uint_as_float(cmb.macc)));
+        }
+        if (DBG) st_at(odbg, pix << 3, make_float2(cmb.wsum, cmb.chosen));
+        if (rp_out) rp_out[pix] = p;
+        if (how) { how[pix] = W; hom[pix] = cmb.macc | (cmb.li << 24); }
+        if constexpr (FIN) { rpos = pos; rcol = col; rW = W; }
     }
-    cmb.take(pd_cur, cw, cm & kHandleM, cli);
-    const v3 pos = xyz(l_lt[cmb.li]), col = xyz(l_lt[L + 1u + cmb.li]);
-    float p = cmb.pd;
-    if (!cmb.has_pd) p = (f.shading && !__builtin_isnan(cur.P.x + cur.P.y + cur.P.z)) ? 0.0f : target_pdf(s, f, cur, pos, col, tb);
-    const float W = contribution_weight(p, cmb.macc, cmb.wsum);
-    if (!odead) {   // odead: a later handle pass is the output's only reader
-        st_at(oa, pix << 4, make_float4(pos.x, pos.y, pos.z, W));
-        st_at(ob, pix << 4, make_float4(col.x, col.y, col.z, __uint_as_float(cmb.macc)));
-    }
-    if (DBG) st_at(odbg, pix << 3, make_float2(cmb.wsum, cmb.chosen));
-    if (rp_out) rp_out[pix] = p;
-    if (how) { how[pix] = W; hom[pix] = cmb.macc | (cmb.li << 24); }
+shade:
+    if constexpr (FIN) fin_shade_block(s, rg, f, fin, tb, live, own_bg, tx0, ty0, wave, rpx, pm_miss, rpos, rcol, rW);
 }
 
 #ifndef ROMIS_SPATIAL1H_WPE
@@ -2455,7 +2499,115 @@ extern "C" __global__ __launch_bounds__(256) void k_final_n2_sorted_q(SceneDev s
     final_sorted_body<true, 2, true>(s, rg, f, mk(ox, oy, oz), n_t, p_mat, ra, rb, rgb, nullptr, mt);
 }
 
-#define ROMIS_FINAL_KERNEL(NT, LDS, NAME)                                                                              \
+// ---------------------------------------------------------------------------------------------------------
+// k_spatial1hg_t2_final: the last N = 1 biased pass (spatial1h_body<false, 2, true>) with final shading of the block's
+// 32 x 16 pixels in the same block (spatial1h_body FIN).  A pixel's RGB comes out of final_sorted_body<true, 1>'s
+// operations on the reservoir the pass produced, in its order: shade, the need test, the miss path with its finiteness
+// checks, visible, x W, / 1, the tone map, the y-flipped store.
+
+// a background tile's pixel (global x, y): final_sorted_body's miss-tile branch, the tone-mapped +0
+__device__ __forceinline__ void fin_store_background(const Region& rg, const FeaturesDev& f, const FinalOut& fin, int x, int y) {
+    const v3 color = tone_map_rgb(f, vdivs(mk(0.0f, 0.0f, 0.0f), 1.0f), gl_global_tabs());
+    const uint32_t row = rg.rh - 1u - ((uint32_t)y - rg.ry0);
+    float* o = fin.rgb + 3 * ((size_t)row * rg.rw + ((uint32_t)x - rg.rx0));
+    o[0] = color.x; o[1] = color.y; o[2] = color.z;
+}
+
+// Every thread of the 512-thread block calls this after the combine (live: the lane has a pixel of the rect; px, pm and
+// the reservoir (pos, col, W) are a live lane's).  own_bg: the pixel lies in a background RIS tile (MissTiles), whose
+// G-buffer records may be unstored -- it holds W = 0 and the initial (0, 0) sample, which final shading colours +0
+// (its miss-tile branch where the pixel's whole 32 x 8 tile is background, else its miss path: 0 + sc x 0).
+// The rays: 256 bins as final_sorted_body, up to 512 rays, ray i traced on thread i over the float BVH staged in the
+// bytes the window and the light table held.
+__device__ __forceinline__ void fin_shade_block(const SceneDev& s, const Region& rg, const FeaturesDev& f, const FinalOut& fin,
+                                                const GlTabs& tb, bool live, bool own_bg, int tx0, int ty0, uint32_t wave, const Px& px,
+                                                bool pm_miss, v3 pos, v3 col, float W) {
+    // the thread index from the wave's (scalar) index and the lane: neither it nor the pixel's coordinates (recomputed
+    // for the store below) occupy a vector register across the combine, which runs at the kernel's register limit
+    const uint32_t t = (wave << 6) | __lane_id();
+    v3 sc = mk(0.0f, 0.0f, 0.0f);
+    bool need = false;
+    if (live && !own_bg) {
+        // final_sorted_body's per-pixel part on a = (pos, W), b = (col, M): the miss shortcut (pm_miss: its p_mat part;
+        // px.P is p_mat's xyz), else shade + need
+        const bool miss = pm_miss && __builtin_isfinite(W) &&
+                          !__builtin_isnan((pos.x - px.P.x) + (pos.y - px.P.y) + (pos.z - px.P.z));
+        if (!miss) {
+            sc = shade(s, f, px, pos, col, tb);
+            need = sc.x != 0.0f || sc.y != 0.0f || sc.z != 0.0f;   // see final_body: no ray when sc == 0
+        } else {
+            W = 0.0f;
+        }
+    } else {
+        W = 0.0f;
+    }
+    __syncthreads();   // every lane is done with the window and the light table
+    const uint32_t nb = 2u * s.num_nodes + 3u * s.num_tris;
+    float4* const s_from = g_lds + nb;
+    float4* const s_to = s_from + kFinRays;
+    uint32_t* const s_vis = reinterpret_cast<uint32_t*>(s_to + kFinRays);
+    uint32_t* const s_hist = s_vis + kFinRays;
+    uint32_t* const s_wsum = s_hist + 256u;
+    if (t < 256u) s_hist[t] = 0u;
+    const Bvh bvh = stage_bvh(s, g_lds);   // ends with a barrier
+    const uint32_t bin = need ? target_bin(bvh, pos) : 0u;
+    const uint32_t rank = need ? atomicAdd(&s_hist[bin], 1u) : 0u;
+    __syncthreads();
+    // exclusive scan of the 256 bin counts by waves 0-3 (final_sorted_body's)
+    uint32_t cnt = 0u, inc = 0u;
+    if (t < 256u) {   // wave-uniform
+        cnt = s_hist[t];
+        inc = cnt;
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t v = __shfl_up(inc, d, 64);
+            if ((t & 63u) >= d) inc += v;
+        }
+        if ((t & 63u) == 63u) s_wsum[t >> 6] = inc;
+    }
+    __syncthreads();
+    const uint32_t total = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
+    if (t < 256u) {
+        uint32_t base = 0;
+        for (uint32_t w = 0; w < (t >> 6); w++) base += s_wsum[w];
+        s_hist[t] = base + inc - cnt;   // every count was read before the barrier above
+    }
+    __syncthreads();
+    if (need) {
+        const uint32_t slot = s_hist[bin] + rank;
+        s_from[slot] = make_float4(px.P.x, px.P.y, px.P.z, __uint_as_float(t));
+        s_to[slot] = make_float4(pos.x, pos.y, pos.z, 0.0f);
+    }
+    __syncthreads();
+    if (t < total) {
+        const float4 a = s_from[t], b = s_to[t];
+        s_vis[__float_as_uint(a.w)] = visible(bvh, xyz(a), xyz(b)) ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!live) return;
+    // finalShading's sum from 0 (final_body: -0 -> +0), then / N
+    v3 c = sc;
+    if (need && !s_vis[t]) c = mk(0.0f, 0.0f, 0.0f);
+    v3 color = vadd(mk(0.0f, 0.0f, 0.0f), vscale(c, W));
+    color = tone_map_rgb(f, vdivs(color, 1.0f), tb);
+    const uint32_t w = t >> 6, l = t & 63u;   // spatial1h_body's pixel of the 32 x 16 tile
+    const uint32_t x = (uint32_t)tx0 + (w & 3u) * 8u + (l & 7u), y = (uint32_t)ty0 + (w >> 2) * 8u + (l >> 3);
+    const uint32_t row = rg.rh - 1u - (y - rg.ry0);
+    float* o = fin.rgb + 3 * ((size_t)row * rg.rw + (x - rg.rx0));
+    o[0] = color.x; o[1] = color.y; o[2] = color.z;
+}
+
+#ifndef ROMIS_SPATIAL1HG_FINAL_WPE
+#define ROMIS_SPATIAL1HG_FINAL_WPE ROMIS_SPATIAL1HG_WPE
+#endif
+extern "C" __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(ROMIS_SPATIAL1HG_FINAL_WPE))) void
+k_spatial1hg_t2_final(SceneDev s, Region rg, FeaturesDev f, uint32_t key, float ox, float oy, float oz, const float4* n_t,
+                      const float4* p_mat, HandlesIn hi, float4* oa, float4* ob, const float* rp_in, float* how,
+                      uint32_t* hom, MissTiles mt, uint32_t odead, FinalOut fin) {
+    spatial1h_body<false, 2, true, true>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, hi, oa, ob, nullptr, rp_in, nullptr, how,
+                                         hom, mt, odead, fin);
+}
+
+#define ROMIS_FINAL_KERNEL(NT, LDS, NAME)                                                                            \
     extern "C" __global__ __launch_bounds__(256) void NAME(SceneDev s, Region rg, FeaturesDev f, float ox, float oy,     \
                                                           float oz, const float4* n_t, const float4* p_mat,             \
                                                           const float4* ra, const float4* rb, float* rgb) {             \
@@ -2729,8 +2881,9 @@ hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDe
                           const float4* n_t, const float4* p_mat, const float4* ia, const float4* ib, float4* oa,
                           float4* ob, float2* odbg, const float* rp_in, const float* rp_nb, float* rp_out,
                           bool* rp_written, const Tuning& tu, hipStream_t stream, uint8_t* vis_out, bool* vis_written,
-                          MissTiles mt, Handles hin, Handles hout) {
+                          MissTiles mt, Handles hin, Handles hout, FusedFinal fin) {
     if (rp_written) *rp_written = false;
+    if (fin.done) *fin.done = false;
     if (!mt.flags) mt.m = mt.gbuf = 0u;
     if (vis_written) *vis_written = false;
     if (rg0.rw == 0 || rg0.rh == 0) return hipSuccess;
@@ -2830,6 +2983,17 @@ hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDe
             }
             const size_t lds = (size_t)apron_max(2) * 16u + (size_t)(2u * s.num_lights + 2u) * 16u;
             const HandlesIn hi{hin.w, hin.m};
+            // final shading in the same kernel (FusedFinal, launch.h): launch_final's conditions for k_final_n1_sorted,
+            // and the ray phase's LDS -- the BVH, the rays, the histogram, in the bytes of the window and the light table
+            const size_t lds_fin = bvh_bytes + (size_t)kFinLdsF4 * 16u;
+            if (fin.rgb && fin.done && tu.final_fuse && !odbg && !rp_out && tu.final_sort && tu.final_lds &&
+                bvh_bytes <= kLdsBudget && !(tu.final_qbvh == 1u && s.nodes_q_ok) && std::max(lds, lds_fin) <= kLdsBudget) {
+                ROMIS_LAUNCH(k_spatial1hg_t2_final, dim3(grid), dim3(2u * kBlock), std::max(lds, lds_fin), stream, s, rg, f,
+                             key, o[0], o[1], o[2], n_t, p_mat, hi, oa, ob, rp_in, hout.w, hout.m, mt,
+                             (fin.res_dead || hout.res_dead) ? 1u : 0u, FinalOut{fin.rgb, tu.final_miss ? 1u : 0u});
+                *fin.done = true;
+                return hipGetLastError();   // (*rp_written stays false: the last pass writes no pdf cache)
+            }
             ROMIS_LAUNCH(odbg ? k_spatial1hg_t2_dbg : k_spatial1hg_t2, dim3(grid), dim3(2u * kBlock), lds, stream, s, rg, f,
                          key, o[0], o[1], o[2], n_t, p_mat, hi, oa, ob, odbg, rp_in, rp_out, hout.w, hout.m, mt,
                          hout.res_dead);

@@ -42,13 +42,25 @@ hipError_t launch_temporal(const SceneDev& s, const Region& rg, const FeaturesDe
                            const float4* n_t, const float4* p_mat, const float4* ca, const float4* cb,
                            const float4* pa, const float4* pb, float4* oa, float4* ob, float2* odbg,
                            const float* rp_in, float* rp_out, const Tuning& tu, hipStream_t stream);
+// Final shading fused into the last pass (tuning "final.fuse"): when the pass would run k_spatial1hg_t2 and launch_final
+// k_final_n1_sorted over the same rect -- N = 1 biased, point-light handles gathered on 32 x 16 tiles, no debug plane;
+// final.sort and final.lds on, the float nodes, the BVH and the rays within the LDS budget -- one kernel
+// (k_spatial1hg_t2_final) does both and *done = true: the caller then skips launch_final.  rgb: launch_final's (the
+// pass's rect is the owned rect).  res_dead: nothing else reads the pass's reservoir planes (no returned grid): the
+// fused kernel does not store them.  The caller offers it only when launch_final would get no vis_in.
+struct FusedFinal {
+    float* rgb;
+    bool res_dead;
+    bool* done;
+};
 hipError_t launch_spatial(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key, const float* origin,
                           const float4* n_t, const float4* p_mat, const float4* ia, const float4* ib, float4* oa,
                           float4* ob, float2* odbg, const float* rp_in, const float* rp_nb, float* rp_out,
                           bool* rp_written, const Tuning& tu, hipStream_t stream, uint8_t* vis_out = nullptr,
                           bool* vis_written = nullptr, MissTiles mt = MissTiles{nullptr, 0u, 0u},
                           Handles hin = Handles{nullptr, nullptr, 0u},    // the input's sample handles (k_spatial1h)
-                          Handles hout = Handles{nullptr, nullptr, 0u});  // the output's, for a later pass
+                          Handles hout = Handles{nullptr, nullptr, 0u},   // the output's, for a later pass
+                          FusedFinal fin = FusedFinal{nullptr, false, nullptr});
 hipError_t launch_final(const SceneDev& s, const Region& rg, const FeaturesDev& f, const float* origin,
                         const float4* n_t, const float4* p_mat, const float4* ra, const float4* rb, float* rgb,
                         const Tuning& tu, hipStream_t stream, const uint8_t* vis_in = nullptr,

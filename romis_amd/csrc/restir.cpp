@@ -1634,9 +1634,15 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
         ST_TRY(fb.vis().ensure((size_t)t.gwidth * t.gheight));
         vis = fb.vis().as<uint8_t>();
     }
+    // final shading inside the last pass (final.fuse; launch.h FusedFinal), offered where launch_final would read the
+    // pass's grid without an own-pixel ray plane; the last pass's rect is the owned rect (grow_rect(owned, 0)), also on
+    // ghost-zoned tiles.  Without a returned grid nothing else reads that pass's reservoir planes (the stage and halo
+    // paths keep their own buffers and the separate kernels): they are not stored
+    bool final_done = false;
     for (uint32_t pass = 0; pass < passes; pass++) {
         const Region pr = grow_rect(owned, (passes - 1u - pass) * f.R);
         const int nxt = cur ^ 1;
+        const bool offer = pass + 1 == passes && c->tuning.final_fuse && N == 1 && !vis;
         TIMED(c, RESTIR_K_SPATIAL,
               launch_spatial(s, pr, f, restir_rng_key(c->seed, frame, RESTIR_STAGE_SPATIAL, pass), camd.origin, fb.nt(cur), pm,
                              fb.ra(cur), fb.rb(cur), fb.ra(nxt), fb.rb(nxt), nullptr, rp_ok ? fb.rp(cur) : nullptr,
@@ -1654,11 +1660,15 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
                              // a pass before the last is read by the next one's handles alone: no reservoir planes
                              handles && pass + 1 < passes ? Handles{fb.h(nxt).w, fb.h(nxt).m, 1u}
                              : frame_handles              ? fb.fh(nxt)
-                                                          : Handles{nullptr, nullptr, 0u}));
+                                                          : Handles{nullptr, nullptr, 0u},
+                             offer ? FusedFinal{fb.rgb().as<float>(), out_next == nullptr, &final_done}
+                                   : FusedFinal{nullptr, false, nullptr}));
         cur = nxt;
     }
-    TIMED(c, RESTIR_K_FINAL, launch_final(s, owned, f, camd.origin, fb.nt(cur), pm, fb.ra(cur), fb.rb(cur), fb.rgb().as<float>(),
-                                          c->tuning, st, vis_ok ? vis : nullptr, MissTiles{tmiss, 0u, 0u}));
+    if (!final_done)
+        TIMED(c, RESTIR_K_FINAL, launch_final(s, owned, f, camd.origin, fb.nt(cur), pm, fb.ra(cur), fb.rb(cur),
+                                              fb.rgb().as<float>(), c->tuning, st, vis_ok ? vis : nullptr,
+                                              MissTiles{tmiss, 0u, 0u}));
     c->cur = cur;
 
     if (out_next) {
@@ -2670,6 +2680,7 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     else if (!std::strcmp(key, "bvh.max_leaf")) t.bvh_max_leaf = v;
     else if (!std::strcmp(key, "final.sort")) t.final_sort = v;
     else if (!std::strcmp(key, "final.qbvh")) t.final_qbvh = v;
+    else if (!std::strcmp(key, "final.fuse")) t.final_fuse = v;
     else if (!std::strcmp(key, "primary.tl")) t.primary_tl = v;
     else if (!std::strcmp(key, "mis.chunk")) t.mis_chunk = v;   // applies from the next ensure_mis
     else if (!std::strcmp(key, "layout.records")) t.records = v;   // frame-path buffer layout
