@@ -1028,36 +1028,188 @@ __device__ __forceinline__ uint32_t tile_flag_at(const MissTiles& mt, const Regi
 constexpr uint32_t kLdsSpatialR = 10;
 constexpr uint32_t kApronMax = (kTileW + 2u * kLdsSpatialR) * (kTileH + 2u * kLdsSpatialR);   // 1456 px
 
-// k_spatial1_ntl: the N = 1 biased pass with the tile's n_t neighbourhood staged in LDS: the block copies the
-// (32 + 2R) x (8 + 2R) n_t window (23 KB at R = 10) with row-coalesced LDS-DMA loads issued with the pixel's own
-// records, so the heuristic's five neighbour records are ds_reads, not 16-byte gathers (each touching ~50 distinct
-// 128-byte lines, DESIGN.md §6).  The accepted neighbours' reservoirs stay global gathers, one neighbour ahead of
-// the consume sequence (k_spatial1h reads sample handles from LDS instead, point-light scenes).  R <= kLdsSpatialR.
-// The n_t window of an ntl spatial block: the tile grown by R, clipped, AW entries per row, copied to LDS by
-// LDS-DMA.  Each wave's 64 consecutive window entries l_nt[256k + 64w + lane] are written straight from global
-// memory (global_load_lds_dwordx4, lane l at the wave-uniform base + 16 l), no VGPR round trip; the caller waits
-// for them (explicit s_waitcnt vmcnt(0)) before its barrier, so after it every wave may read every entry.
+// ---------------------------------------------------------------------------------------------------------
+// The prologue the lean spatial kernels share.  The four windowed bodies (spatial1_ntl_body, spatial1h_body,
+// spatialn_ntl_body, spatial2hg_body) run it in this order: lean_tile, lean_background_exit, lean_window, their own
+// loads and the window's staging, lean_draws, lean_window_ready; then lean_primary_miss and LeanSimilar decide what
+// the combine reads.  spatial1u_body, which stages no window, takes lean_tile, lean_background_exit and lean_draw.
 // TH: tile height in 8-row units (blocks of 256 TH threads, a (32 + 2R) x (8 TH + 2R) window).
 constexpr uint32_t apron_max(uint32_t TH) { return (kTileW + 2u * kLdsSpatialR) * (kTileH * TH + 2u * kLdsSpatialR); }
+
+// A block's 32 x 8 TH tile (xcd_tile's order over the pass's rect) and the lane's pixel in it: wave w is the 8 x 8
+// pixels (w % 4, w / 4) of the tile.  Global coordinates.
+struct LeanTile {
+    int tx0, ty0;   // the tile's first pixel
+    int x1, y1;     // its last pixel inside the rect
+    int x, y;       // the lane's pixel
+    bool live;      // ... inside the rect
+    uint32_t pix;   // ... as an index into the stored view's planes
+};
+// false: the block has no tile (block-uniform)
+template <uint32_t TH>
+__device__ __forceinline__ bool lean_tile(const Region& rg, LeanTile& t) {
+    constexpr uint32_t kTH = kTileH * TH;   // tile rows
+    const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW;
+    uint32_t tile;
+    if (!xcd_tile(rg, ntx * ((rg.rh + kTH - 1) / kTH), blockIdx.x, tile)) return false;
+    t.tx0 = (int)(rg.rx0 + (tile % ntx) * kTileW);
+    t.ty0 = (int)(rg.ry0 + (tile / ntx) * kTH);
+    t.x1 = min(t.tx0 + (int)kTileW, (int)(rg.rx0 + rg.rw)) - 1;
+    t.y1 = min(t.ty0 + (int)kTH, (int)(rg.ry0 + rg.rh)) - 1;
+    const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63u;
+    t.x = t.tx0 + (int)((w & 3u) * 8u + (l & 7u));
+    t.y = t.ty0 + (int)((w >> 2) * 8u + (l >> 3));
+    t.live = t.x < (int)(rg.rx0 + rg.rw) && t.y < (int)(rg.ry0 + rg.rh);
+    t.pix = (uint32_t)(t.y - (int)rg.vy0) * rg.vw + (uint32_t)(t.x - (int)rg.vx0);
+    return true;
+}
+
+// Background tiles (mt.m != 0): when every RIS tile meeting [x0, x1] x [y0, y1] is one, the block's pixels hold the
+// known result of the miss shortcut, which store(pixel index) writes for the lane's pixel without reading the tile, its
+// window or its neighbours; true then (block-uniform, before any barrier): the caller returns.  *mixed: some tile of
+// the rect is a background tile (whose RIS records may be unwritten: the caller substitutes them).
+template <class Store>
+__device__ __forceinline__ bool lean_background_exit(const MissTiles& mt, const Region& rg, const LeanTile& t, int x0, int x1,
+                                                     int y0, int y1, bool* mixed, Store&& store) {
+    if (!mt.m || !tiles_known_miss(mt, rg, x0, x1, y0, y1, mixed)) return false;
+    if (t.x <= t.x1 && t.y <= t.y1) store(t.pix);
+    return true;
+}
+
+// The tile's neighbourhood window: the tile grown by R and clipped to where neighbours may lie.
+struct LeanWindow {
+    int xlo, xhi, ylo, yhi;   // neighbour clamp bounds (render_utils.cpp:109-110: the image; here also the stored view)
+    int ax0, ay0;             // the window's first pixel
+    uint32_t AW, n_apron;     // entries per row, entries
+    uint32_t magic;           // 0xFFFFFFFF / AW + 1
+    __device__ __forceinline__ uint32_t at(int x, int y) const { return (uint32_t)(y - ay0) * AW + (uint32_t)(x - ax0); }
+    // the row i / AW of entry i < 2^16, by the reciprocal instead of a division
+    __device__ __forceinline__ uint32_t row(uint32_t i) const {
+        uint32_t r = __umulhi(i, magic);
+        if (r * AW > i) r--;
+        return r;
+    }
+};
+template <uint32_t TH>
+__device__ __forceinline__ LeanWindow lean_window(const Region& rg, const FeaturesDev& f, const LeanTile& t) {
+    LeanWindow wn;
+    wn.xlo = max(0, (int)rg.vx0); wn.xhi = min((int)rg.W, (int)(rg.vx0 + rg.vw)) - 1;
+    wn.ylo = max(0, (int)rg.vy0); wn.yhi = min((int)rg.H, (int)(rg.vy0 + rg.vh)) - 1;
+    const int R = (int)f.R;
+    wn.ax0 = max(t.tx0 - R, wn.xlo);
+    wn.ay0 = max(t.ty0 - R, wn.ylo);
+    const int ax1 = min(t.tx0 + (int)kTileW - 1 + R, wn.xhi), ay1 = min(t.ty0 + (int)(kTileH * TH) - 1 + R, wn.yhi);
+    wn.AW = (uint32_t)(ax1 - wn.ax0 + 1);
+    wn.n_apron = wn.AW * (uint32_t)(ay1 - wn.ay0 + 1);
+    wn.magic = 0xFFFFFFFFu / wn.AW + 1u;
+    return wn;
+}
+
+// The window's n_t records, AW entries per row, copied to LDS by LDS-DMA.  Each wave's 64 consecutive window entries
+// l_nt[256 TH k + 64w + lane] are written straight from global memory (global_load_lds_dwordx4, lane l at the
+// wave-uniform base + 16 l), no VGPR round trip; lean_window_ready makes them readable by every wave.
 template <uint32_t TH = 1>
-__device__ __forceinline__ void ntl_stage_window(const Region& rg, const float4* __restrict__ n_t, float4* l_nt, int ax0,
-                                                 int ay0, uint32_t AW, uint32_t n_apron) {
+__device__ __forceinline__ void ntl_stage_window(const Region& rg, const float4* __restrict__ n_t, float4* l_nt,
+                                                 const LeanWindow& wn) {
     constexpr uint32_t kThreads = 256u * TH, kPer = (apron_max(TH) + kThreads - 1u) / kThreads;
-    const uint32_t magic = 0xFFFFFFFFu / AW + 1u;
     const uint32_t w64 = (threadIdx.x >> 6) << 6;
 #pragma unroll
     for (uint32_t k = 0; k < kPer; k++) {
         const uint32_t i = threadIdx.x + kThreads * k;
-        if (i < n_apron) {
-            uint32_t r = __umulhi(i, magic);   // i / AW for i < 2^16
-            if (r * AW > i) r--;
-            const uint32_t c = i - r * AW;
-            const float4* src = n_t + (((uint32_t)(ay0 - (int)rg.vy0) + r) * rg.vw + (uint32_t)(ax0 - (int)rg.vx0) + c);
+        if (i < wn.n_apron) {
+            const uint32_t r = wn.row(i);
+            const uint32_t c = i - r * wn.AW;
+            const float4* src = n_t + (((uint32_t)(wn.ay0 - (int)rg.vy0) + r) * rg.vw + (uint32_t)(wn.ax0 - (int)rg.vx0) + c);
             __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(l_nt + kThreads * k + w64), 16, 0, 0);
         }
     }
 }
+
+// Neighbour n of the pixel whose +-R square starts at (bx, by): two draws of its RNG state ps (render_utils.cpp:108-111),
+// clamped to [xlo, xhi] x [ylo, yhi] -- the same coordinate frame throughout, global or view-relative
+__device__ __forceinline__ void lean_draw(uint32_t ps, uint32_t n, uint32_t span, int bx, int by, int xlo, int xhi, int ylo,
+                                          int yhi, int& nx, int& ny) {
+    nx = min(max(bx + (int)__umulhi(draw(ps, 2u * n), span), xlo), xhi);
+    ny = min(max(by + (int)__umulhi(draw(ps, 2u * n + 1u), span), ylo), yhi);
+}
+// The K <= kLeanK (host check) neighbours of the lane's pixel: qi[n] their window entries, qp[n] their view pixel
+// indices << shift (0: elements, 4: bytes of a float4 plane); entries n >= K get 0 and fill
+__device__ __forceinline__ void lean_draws(const Region& rg, const FeaturesDev& f, const LeanTile& t, const LeanWindow& wn,
+                                           uint32_t ps, uint32_t (&qi)[kLeanK], uint32_t (&qp)[kLeanK], uint32_t fill,
+                                           uint32_t shift) {
+    const uint32_t span = 2u * f.R + 1u;
+#pragma unroll
+    for (uint32_t n = 0; n < kLeanK; n++) {
+        qi[n] = 0u;
+        qp[n] = fill;
+        if (n < f.K) {
+            int nx, ny;
+            lean_draw(ps, n, span, t.x - (int)f.R, t.y - (int)f.R, wn.xlo, wn.xhi, wn.ylo, wn.yhi, nx, ny);
+            qi[n] = wn.at(nx, ny);
+            qp[n] = ((uint32_t)(ny - (int)rg.vy0) * rg.vw + (uint32_t)(nx - (int)rg.vx0)) << shift;
+        }
+    }
+}
+
+// The window is complete and visible to every wave after this.  Other waves read this wave's LDS-DMA entries after the
+// barrier; the compiler only waits for a wave's own DMA before that wave's ds_reads, and a workgroup-scope fence need
+// not drain vmcnt on gfx950, so the wait is explicit (scripts/kernel_isa.sh k_spatial1_ntl: s_waitcnt vmcnt(0) directly
+// before s_barrier).  With mt.gbuf RIS stored no G-buffer for background tiles: a thread's window entries there (its own
+// LDS-DMA copies, landed after the wait) become a miss's record, normal 0 and t = FLT_MAX -- what RIS would have stored.
+template <uint32_t TH>
+__device__ __forceinline__ void lean_window_ready(const MissTiles& mt, const Region& rg, const LeanWindow& wn, float4* l_nt) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (mt.m && mt.gbuf) {
+        constexpr uint32_t kThreads = 256u * TH, kPer = (apron_max(TH) + kThreads - 1u) / kThreads;
+#pragma unroll
+        for (uint32_t k = 0; k < kPer; k++) {
+            const uint32_t i = threadIdx.x + kThreads * k;
+            if (i < wn.n_apron) {
+                const uint32_t r = wn.row(i);
+                const uint32_t c = i - r * wn.AW;
+                if (tile_flag_at(mt, rg, wn.ax0 + (int)c, wn.ay0 + (int)r) == 0u)
+                    l_nt[i] = make_float4(0.0f, 0.0f, 0.0f, ROMIS_FLT_MAX);
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// A primary-ray miss (value-initialised HitInfo: the miss material kd = ks = 0, normal 0, P not NaN): its zero normal
+// rejects every neighbour (finite neighbour normals, s.normals_bounded: dot = +-0 < 0.906), and the target pdf of any
+// finite-colour sample there is exactly 0.
+__device__ __forceinline__ bool lean_primary_miss(const SceneDev& s, const Px& cur) {
+    return cur.mat == s.num_materials - 1u && s.normals_bounded && !__builtin_isnan(cur.P.x + cur.P.y + cur.P.z);
+}
+
+// The depth / normal heuristic (render_utils.cpp:114-118) of the pixel cur against neighbour records g = (normal, t)
+// read from the window: one shared reciprocal of the pixel's depth, both tests for every lane from one ds_read_b128 (a
+// branch around the depth test only saved work on rejected lanes).  The correctly rounded division for depths outside
+// the reciprocal's range is a wave-uniform branch: left to the compiler it is if-converted and evaluated for every
+// neighbour of every lane.
+struct LeanSimilar {
+    v3 N;
+    float t;
+    double rt;
+    bool rt_all;
+    __device__ __forceinline__ explicit LeanSimilar(const Px& cur)
+        : N(cur.N), t(cur.t), rt(rcp_d(cur.t)), rt_all(__all(div_fast_ok(cur.t))) {}
+    __device__ __forceinline__ bool operator()(float4 g) const {
+        const float nd = vdot(xyz(g), N);
+        float q = div_by_rcp_d(g.w, rt);
+        if (__builtin_expect(!rt_all, 0)) {
+            if (!div_fast_ok(t)) q = g.w / t;
+        }
+        return !(nd < 0.90630778703f) && !(fabsf(1.0f - q) > 0.1f);
+    }
+};
+
+// k_spatial1_ntl: the N = 1 biased pass with the tile's n_t neighbourhood staged in LDS: the block copies the
+// (32 + 2R) x (8 + 2R) n_t window (23 KB at R = 10) with row-coalesced LDS-DMA loads issued with the pixel's own
+// records, so the heuristic's five neighbour records are ds_reads, not 16-byte gathers (each touching ~50 distinct
+// 128-byte lines, DESIGN.md §6).  The accepted neighbours' reservoirs stay global gathers, one neighbour ahead of
+// the consume sequence (k_spatial1h reads sample handles from LDS instead, point-light scenes).  R <= kLdsSpatialR.
 
 // GH (k_spatial1g_t2, a regular light grid): the input reservoirs arrive as grid handles (hg_in; ia / ib unused), one
 // 16-byte gather per accepted neighbour instead of two, the sample rebuilt by grid_sample from the light colours the
@@ -1081,43 +1233,26 @@ __device__ __forceinline__ void spatial1_ntl_body(const SceneDev& s, const Regio
     auto put_handle = [&](uint32_t ofs, float W, uint32_t M, uint32_t li, float a, float b) {
         if (GH && hg_out) st_at(hg_out, ofs, make_float4(W, __uint_as_float(M | (li << 19)), a, b));
     };
-    uint32_t tile;
-    constexpr uint32_t kTH = kTileH * TH;   // tile rows
-    const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW;
-    if (!xcd_tile(rg, ntx * ((rg.rh + kTH - 1) / kTH), blockIdx.x, tile)) return;   // block-uniform
-    const int tx0 = (int)(rg.rx0 + (tile % ntx) * kTileW), ty0 = (int)(rg.ry0 + (tile / ntx) * kTH);
+    LeanTile t;
+    if (!lean_tile<TH>(rg, t)) return;   // block-uniform
     bool mixed = false;   // some of the tile's pixels lie in background tiles (whose RIS reservoirs may be unwritten)
-    if (mt.m) {
-        // a tile of background pixels holding (0, W = 0), (0, M = mt.m): the miss shortcut's result below (W = 0, M the
-        // pixel's own, wSum FLT_MIN), written without reading the tile, its window or its neighbours
-        const int x1 = min(tx0 + (int)kTileW, (int)(rg.rx0 + rg.rw)) - 1, y1 = min(ty0 + (int)kTH, (int)(rg.ry0 + rg.rh)) - 1;
-        if (tiles_known_miss(mt, rg, tx0, x1, ty0, y1, &mixed)) {
-            const uint32_t mw = threadIdx.x >> 6, ml = threadIdx.x & 63u;
-            const int mx = tx0 + (int)((mw & 3u) * 8u + (ml & 7u)), my = ty0 + (int)((mw >> 2) * 8u + (ml >> 3));
-            if (mx <= x1 && my <= y1) {
-                const uint32_t mo = ((uint32_t)(my - (int)rg.vy0) * rg.vw + (uint32_t)(mx - (int)rg.vx0)) << 4;
-                if (!odead) {
-                    st_at(oa, mo, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                    st_at(ob, mo, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(mt.m)));
-                }
-                if (DBG) st_at(odbg, mo >> 1, make_float2(ROMIS_FLT_MIN, 0.0f));
-                if (rp_out) st_at(rp_out, mo >> 2, 0.0f);
-                put_handle(mo, 0.0f, mt.m, L, 0.0f, 0.0f);
+    // a tile of background pixels holding (0, W = 0), (0, M = mt.m): the miss shortcut's result below (W = 0, M the
+    // pixel's own, wSum FLT_MIN)
+    if (lean_background_exit(mt, rg, t, t.tx0, t.x1, t.ty0, t.y1, &mixed, [&](uint32_t mp) {
+            const uint32_t mo = mp << 4;
+            if (!odead) {
+                st_at(oa, mo, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+                st_at(ob, mo, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(mt.m)));
             }
-            return;   // block-uniform, before the window's barrier
-        }
-    }
-    // neighbour clamp bounds (render_utils.cpp:109-110: the image; here also the stored view), global coords
-    const int xlo = max(0, (int)rg.vx0), xhi = min((int)rg.W, (int)(rg.vx0 + rg.vw)) - 1;
-    const int ylo = max(0, (int)rg.vy0), yhi = min((int)rg.H, (int)(rg.vy0 + rg.vh)) - 1;
-    const int R = (int)f.R;
-    const int ax0 = max(tx0 - R, xlo), ax1 = min(tx0 + (int)kTileW - 1 + R, xhi);
-    const int ay0 = max(ty0 - R, ylo), ay1 = min(ty0 + (int)kTH - 1 + R, yhi);
-    const uint32_t AW = (uint32_t)(ax1 - ax0 + 1), n_apron = AW * (uint32_t)(ay1 - ay0 + 1);
-    const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63u;   // wave w: the 8x8 block (w % 4, w / 4)
-    const int x = tx0 + (int)((w & 3u) * 8u + (l & 7u)), y = ty0 + (int)((w >> 2) * 8u + (l >> 3));
-    const bool live = x < (int)(rg.rx0 + rg.rw) && y < (int)(rg.ry0 + rg.rh);
-    const uint32_t pofs = ((uint32_t)(y - (int)rg.vy0) * rg.vw + (uint32_t)(x - (int)rg.vx0)) << 4;
+            if (DBG) st_at(odbg, mo >> 1, make_float2(ROMIS_FLT_MIN, 0.0f));
+            if (rp_out) st_at(rp_out, mo >> 2, 0.0f);
+            put_handle(mo, 0.0f, mt.m, L, 0.0f, 0.0f);
+        }))
+        return;
+    const LeanWindow wn = lean_window<TH>(rg, f, t);
+    const int x = t.x, y = t.y;
+    const bool live = t.live;
+    const uint32_t pofs = t.pix << 4;
     // the pixel's own records (coalesced), issued first
     float4 cpm = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ca = cpm, cb = cpm;
     float4 ch = make_float4(0.0f, __uint_as_float(L << 19), 0.0f, 0.0f);   // GH: the own handle
@@ -1141,7 +1276,7 @@ __device__ __forceinline__ void spatial1_ntl_body(const SceneDev& s, const Regio
             if (rp_in) pd_cached = ld_at(rp_in, pofs >> 2);
         }
     }
-    ntl_stage_window<TH>(rg, n_t, l_nt, ax0, ay0, AW, n_apron);
+    ntl_stage_window<TH>(rg, n_t, l_nt, wn);
     if (GH) {   // the light colours behind the window (LDS-DMA, the same wait and barrier)
         const uint32_t w64 = (threadIdx.x >> 6) << 6;
         for (uint32_t d0 = 0; d0 < L; d0 += 256u * TH)
@@ -1155,42 +1290,11 @@ __device__ __forceinline__ void spatial1_ntl_body(const SceneDev& s, const Regio
     // neighbour draws while the loads are in flight
     const uint32_t K = f.K;   // <= kLeanK (host check)
     const uint32_t ps = pix_state(key, (uint32_t)y * rg.W + (uint32_t)x);
-    const uint32_t span = 2u * f.R + 1u;
-    uint32_t qi[kLeanK], qo[kLeanK];
-#pragma unroll
-    for (uint32_t n = 0; n < kLeanK; n++) {
-        qi[n] = 0u;
-        qo[n] = pofs;
-        if (n < K) {
-            const int nx = min(max(x - R + (int)__umulhi(draw(ps, 2u * n), span), xlo), xhi);
-            const int ny = min(max(y - R + (int)__umulhi(draw(ps, 2u * n + 1u), span), ylo), yhi);
-            qi[n] = (uint32_t)(ny - ay0) * AW + (uint32_t)(nx - ax0);
-            qo[n] = ((uint32_t)(ny - (int)rg.vy0) * rg.vw + (uint32_t)(nx - (int)rg.vx0)) << 4;
-        }
-    }
-    // Other waves read this wave's LDS-DMA entries after the barrier.  The compiler only waits for a wave's own
-    // DMA before that wave's ds_reads, and a workgroup-scope fence need not drain vmcnt on gfx950, so the wait
-    // is explicit (scripts/kernel_isa.sh k_spatial1_ntl: s_waitcnt vmcnt(0) directly before s_barrier).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (mt.m && mt.gbuf) {
-        // RIS stored no G-buffer for background tiles: this thread's window entries there (its own LDS-DMA copies,
-        // landed after the wait above) become a miss's record, normal 0 and t = FLT_MAX -- what RIS would have stored
-        constexpr uint32_t kThreads = 256u * TH, kPer = (apron_max(TH) + kThreads - 1u) / kThreads;
-#pragma unroll
-        for (uint32_t k = 0; k < kPer; k++) {
-            const uint32_t i = threadIdx.x + kThreads * k;
-            if (i < n_apron) {
-                uint32_t r = __umulhi(i, 0xFFFFFFFFu / AW + 1u);   // i / AW for i < 2^16 (ntl_stage_window)
-                if (r * AW > i) r--;
-                const uint32_t c = i - r * AW;
-                if (tile_flag_at(mt, rg, ax0 + (int)c, ay0 + (int)r) == 0u)
-                    l_nt[i] = make_float4(0.0f, 0.0f, 0.0f, ROMIS_FLT_MAX);
-            }
-        }
-    }
-    __syncthreads();
+    uint32_t qi[kLeanK], qo[kLeanK];   // qo: byte offsets into the float4 planes
+    lean_draws(rg, f, t, wn, ps, qi, qo, pofs, 4u);
+    lean_window_ready<TH>(mt, rg, wn, l_nt);
     if (!live) return;   // no barrier follows
-    const float4 cn = l_nt[(uint32_t)(y - ay0) * AW + (uint32_t)(x - ax0)];
+    const float4 cn = l_nt[wn.at(x, y)];
     const uint32_t cli = __float_as_uint(ch.y) >> 19;
     if (GH) {   // the own reservoir from its handle
         v3 p, c;
@@ -1199,12 +1303,9 @@ __device__ __forceinline__ void spatial1_ntl_body(const SceneDev& s, const Regio
         cb = make_float4(c.x, c.y, c.z, __uint_as_float(__float_as_uint(ch.y) & kHandleMG));
     }
     const Px cur = make_px(s, cn, cpm, origin, pofs >> 4);
-    // A primary-ray miss (value-initialised HitInfo: material kd = ks = 0, normal 0, P not NaN): its zero normal
-    // rejects every neighbour (finite neighbour normals, s.normals_bounded: dot = +-0 < 0.906), and the target pdf of
-    // any finite-colour sample there is exactly 0, so the combine takes only the pixel's own reservoir
-    // with w = (0 * W) * M = +-0 (W finite): nothing is accepted, wSum stays FLT_MIN, M = M_own, W = 0.
-    if (cur.mat == s.num_materials - 1u && s.normals_bounded && !__builtin_isnan(cur.P.x + cur.P.y + cur.P.z) &&
-        __builtin_isfinite(ca.w) && __builtin_isfinite(cb.x + cb.y + cb.z)) {
+    // A primary-ray miss: the combine takes only the pixel's own reservoir with w = (0 * W) * M = +-0 (W finite): nothing
+    // is accepted, wSum stays FLT_MIN, M = M_own, W = 0.
+    if (lean_primary_miss(s, cur) && __builtin_isfinite(ca.w) && __builtin_isfinite(cb.x + cb.y + cb.z)) {
         if (!odead) {
             st_at(oa, pofs, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
             st_at(ob, pofs, make_float4(0.0f, 0.0f, 0.0f, cb.w));
@@ -1214,26 +1315,10 @@ __device__ __forceinline__ void spatial1_ntl_body(const SceneDev& s, const Regio
         put_handle(pofs, 0.0f, __float_as_uint(cb.w), L, 0.0f, 0.0f);
         return;
     }
-    // depth / normal heuristic (render_utils.cpp:114-118), one shared reciprocal of the pixel's depth; both tests
-    // for every lane from one ds_read_b128 (a branch around the depth test only saved work on rejected lanes).  The
-    // correctly rounded division for depths outside the reciprocal's range is a wave-uniform branch: left to the
-    // compiler it is if-converted and evaluated for every neighbour of every lane.
-    const double rt = rcp_d(cur.t);
-    const bool rt_all = __all(div_fast_ok(cur.t));
+    const LeanSimilar similar(cur);
     bool ok[kLeanK];
 #pragma unroll
-    for (uint32_t n = 0; n < kLeanK; n++) {
-        ok[n] = false;
-        if (n < K) {
-            const float4 g = l_nt[qi[n]];
-            const float nd = vdot(xyz(g), cur.N);
-            float q = div_by_rcp_d(g.w, rt);
-            if (__builtin_expect(!rt_all, 0)) {
-                if (!div_fast_ok(cur.t)) q = g.w / cur.t;
-            }
-            ok[n] = !(nd < 0.90630778703f) && !(fabsf(1.0f - q) > 0.1f);
-        }
-    }
+    for (uint32_t n = 0; n < kLeanK; n++) ok[n] = n < K && similar(l_nt[qi[n]]);
     float4 na[kLeanK], nb[kLeanK];   // GH: na = the neighbour's handle
     auto gather = [&](uint32_t n) {
         if (GH) { na[n] = ld_at(hg_in, qo[n]); }
@@ -1349,21 +1434,36 @@ struct Comb1h {
 // LDS of a handle block: the n_t window, the two handle windows, then the light table (2 (L + 1) float4)
 __host__ __device__ constexpr uint32_t h_lds_f4(uint32_t TH) { return apron_max(TH) + apron_max(TH) / 2u; }
 
+// The point-light table of a handle block by LDS-DMA (kThreads threads): entries d = 0 .. L positions, L + 1 .. 2L + 1
+// colours (the light_c2 planes); d = L and 2L + 1 are the zero sample's, stored by two threads
+template <uint32_t kThreads>
+__device__ __forceinline__ void stage_light_table(const SceneDev& s, float4* l_lt) {
+    const uint32_t L = s.num_lights, nd = 2u * L + 2u, w64 = (threadIdx.x >> 6) << 6;
+    for (uint32_t d0 = 0; d0 < nd; d0 += kThreads) {
+        const uint32_t d = d0 + threadIdx.x;
+        if (d < nd && d != L && d != 2u * L + 1u) {
+            const float4* src = d < L ? s.light_c2 + d : s.light_c2 + (d - 1u);
+            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)src,
+                                             (__attribute__((address_space(3))) void*)(l_lt + d0 + w64), 16, 0, 0);
+        }
+    }
+    if (threadIdx.x < 2u) l_lt[threadIdx.x ? 2u * L + 1u : L] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// The window's n_t records (ntl_stage_window's copy) with, unless HG, the two handle planes beside them, then the
+// light table
 template <uint32_t TH, bool HG = false>
 __device__ __forceinline__ void h_stage(const SceneDev& s, const Region& rg, const float4* __restrict__ n_t, HandlesIn hi,
-                                        float4* l_nt, float* l_w, uint32_t* l_m, float4* l_lt, int ax0, int ay0, uint32_t AW,
-                                        uint32_t n_apron) {
+                                        float4* l_nt, float* l_w, uint32_t* l_m, float4* l_lt, const LeanWindow& wn) {
     constexpr uint32_t kThreads = 256u * TH, kPer = (apron_max(TH) + kThreads - 1u) / kThreads;
-    const uint32_t magic = 0xFFFFFFFFu / AW + 1u;
     const uint32_t w64 = (threadIdx.x >> 6) << 6;
-    const uint32_t base = (uint32_t)(ay0 - (int)rg.vy0) * rg.vw + (uint32_t)(ax0 - (int)rg.vx0);
+    const uint32_t base = (uint32_t)(wn.ay0 - (int)rg.vy0) * rg.vw + (uint32_t)(wn.ax0 - (int)rg.vx0);
 #pragma unroll
     for (uint32_t k = 0; k < kPer; k++) {
         const uint32_t i = threadIdx.x + kThreads * k;
-        if (i < n_apron) {
-            uint32_t r = __umulhi(i, magic);   // i / AW for i < 2^16
-            if (r * AW > i) r--;
-            const uint32_t o = base + r * rg.vw + (i - r * AW);
+        if (i < wn.n_apron) {
+            const uint32_t r = wn.row(i);
+            const uint32_t o = base + r * rg.vw + (i - r * wn.AW);
             __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(n_t + o),
                                              (__attribute__((address_space(3))) void*)(l_nt + kThreads * k + w64), 16, 0, 0);
             if (!HG) {
@@ -1374,18 +1474,7 @@ __device__ __forceinline__ void h_stage(const SceneDev& s, const Region& rg, con
             }
         }
     }
-    // light table: entries d = 0 .. L positions, L + 1 .. 2L + 1 colours (the light_c2 planes); d = L and 2L + 1 are
-    // the zero sample's, stored by two threads
-    const uint32_t L = s.num_lights, nd = 2u * L + 2u;
-    for (uint32_t d0 = 0; d0 < nd; d0 += kThreads) {
-        const uint32_t d = d0 + threadIdx.x;
-        if (d < nd && d != L && d != 2u * L + 1u) {
-            const float4* src = d < L ? s.light_c2 + d : s.light_c2 + (d - 1u);
-            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(l_lt + d0 + w64), 16, 0, 0);
-        }
-    }
-    if (threadIdx.x < 2u) l_lt[threadIdx.x ? 2u * L + 1u : L] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    stage_light_table<kThreads>(s, l_lt);
 }
 
 // The final-shading output of a fused last pass (k_spatial1hg_t2_final): the RGB rows of the pass's rect (row 0 = its
@@ -1419,46 +1508,29 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
                                                uint32_t* __restrict__ hom, MissTiles mt, uint32_t odead,
                                                FinalOut fin = FinalOut{nullptr, 0u}) {
     static_assert(!FIN || (!DBG && TH == 2u && HG), "the fused form is the 32 x 16 gather pass without a debug plane");
-    constexpr uint32_t kTH = kTileH * TH;
     float4* const l_nt = g_lds;
     float* const l_w = reinterpret_cast<float*>(g_lds + apron_max(TH));
     uint32_t* const l_m = reinterpret_cast<uint32_t*>(l_w + apron_max(TH));
     float4* const l_lt = g_lds + (HG ? apron_max(TH) : h_lds_f4(TH));
     const uint32_t L = s.num_lights;
-    uint32_t tile;
-    const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW;
-    if (!xcd_tile(rg, ntx * ((rg.rh + kTH - 1) / kTH), blockIdx.x, tile)) return;   // block-uniform
-    const int tx0 = (int)(rg.rx0 + (tile % ntx) * kTileW), ty0 = (int)(rg.ry0 + (tile / ntx) * kTH);
+    LeanTile t;
+    if (!lean_tile<TH>(rg, t)) return;   // block-uniform
     bool mixed = false;
-    if (mt.m) {   // background tiles: spatial1_ntl_body
-        const int x1 = min(tx0 + (int)kTileW, (int)(rg.rx0 + rg.rw)) - 1, y1 = min(ty0 + (int)kTH, (int)(rg.ry0 + rg.rh)) - 1;
-        if (tiles_known_miss(mt, rg, tx0, x1, ty0, y1, &mixed)) {
-            const uint32_t mw = threadIdx.x >> 6, ml = threadIdx.x & 63u;
-            const int mx = tx0 + (int)((mw & 3u) * 8u + (ml & 7u)), my = ty0 + (int)((mw >> 2) * 8u + (ml >> 3));
-            if (mx <= x1 && my <= y1) {
-                const uint32_t mp = (uint32_t)(my - (int)rg.vy0) * rg.vw + (uint32_t)(mx - (int)rg.vx0);
-                if (!odead) {
-                    st_at(oa, mp << 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                    st_at(ob, mp << 4, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(mt.m)));
-                }
-                if (DBG) st_at(odbg, mp << 3, make_float2(ROMIS_FLT_MIN, 0.0f));
-                if (rp_out) rp_out[mp] = 0.0f;
-                if (how) { how[mp] = 0.0f; hom[mp] = mt.m | (L << 24); }
-                if (FIN) fin_store_background(rg, f, fin, mx, my);   // final_sorted_body's miss-tile branch
+    if (lean_background_exit(mt, rg, t, t.tx0, t.x1, t.ty0, t.y1, &mixed, [&](uint32_t mp) {
+            if (!odead) {
+                st_at(oa, mp << 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+                st_at(ob, mp << 4, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(mt.m)));
             }
-            return;
-        }
-    }
-    const int xlo = max(0, (int)rg.vx0), xhi = min((int)rg.W, (int)(rg.vx0 + rg.vw)) - 1;
-    const int ylo = max(0, (int)rg.vy0), yhi = min((int)rg.H, (int)(rg.vy0 + rg.vh)) - 1;
-    const int R = (int)f.R;
-    const int ax0 = max(tx0 - R, xlo), ax1 = min(tx0 + (int)kTileW - 1 + R, xhi);
-    const int ay0 = max(ty0 - R, ylo), ay1 = min(ty0 + (int)kTH - 1 + R, yhi);
-    const uint32_t AW = (uint32_t)(ax1 - ax0 + 1), n_apron = AW * (uint32_t)(ay1 - ay0 + 1);
-    const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63u;
-    const int x = tx0 + (int)((w & 3u) * 8u + (l & 7u)), y = ty0 + (int)((w >> 2) * 8u + (l >> 3));
-    const bool live = x < (int)(rg.rx0 + rg.rw) && y < (int)(rg.ry0 + rg.rh);
-    const uint32_t pix = (uint32_t)(y - (int)rg.vy0) * rg.vw + (uint32_t)(x - (int)rg.vx0);
+            if (DBG) st_at(odbg, mp << 3, make_float2(ROMIS_FLT_MIN, 0.0f));
+            if (rp_out) rp_out[mp] = 0.0f;
+            if (how) { how[mp] = 0.0f; hom[mp] = mt.m | (L << 24); }
+            if (FIN) fin_store_background(rg, f, fin, t.x, t.y);   // final_sorted_body's miss-tile branch
+        }))
+        return;
+    const LeanWindow wn = lean_window<TH>(rg, f, t);
+    const int x = t.x, y = t.y, tx0 = t.tx0, ty0 = t.ty0;
+    const bool live = t.live;
+    const uint32_t pix = t.pix;
     float4 cpm = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float pd_cached = 0.0f;
     float gw = 0.0f;
@@ -1473,38 +1545,13 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
             if (HG) { gw = hi.w[pix]; gm = hi.m[pix]; }
         }
     }
-    h_stage<TH, HG>(s, rg, n_t, hi, l_nt, l_w, l_m, l_lt, ax0, ay0, AW, n_apron);
+    h_stage<TH, HG>(s, rg, n_t, hi, l_nt, l_w, l_m, l_lt, wn);
     const GlTabs tb = gl_stage_tables_dma();
     const uint32_t K = f.K;   // <= kLeanK (host check)
     const uint32_t ps = pix_state(key, (uint32_t)y * rg.W + (uint32_t)x);
-    const uint32_t span = 2u * f.R + 1u;
-    uint32_t qi[kLeanK], qp[kLeanK];
-#pragma unroll
-    for (uint32_t n = 0; n < kLeanK; n++) {
-        qi[n] = 0u;
-        qp[n] = 0u;
-        if (n < K) {
-            const int nx = min(max(x - R + (int)__umulhi(draw(ps, 2u * n), span), xlo), xhi);
-            const int ny = min(max(y - R + (int)__umulhi(draw(ps, 2u * n + 1u), span), ylo), yhi);
-            qi[n] = (uint32_t)(ny - ay0) * AW + (uint32_t)(nx - ax0);
-            if (HG) qp[n] = (uint32_t)(ny - (int)rg.vy0) * rg.vw + (uint32_t)(nx - (int)rg.vx0);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave's DMA before the barrier (spatial1_ntl_body)
-    if (mt.m && mt.gbuf) {   // background G-buffer records: spatial1_ntl_body's window fix-up
-        constexpr uint32_t kThreads = 256u * TH, kPer = (apron_max(TH) + kThreads - 1u) / kThreads;
-#pragma unroll
-        for (uint32_t k = 0; k < kPer; k++) {
-            const uint32_t i = threadIdx.x + kThreads * k;
-            if (i < n_apron) {
-                uint32_t r = __umulhi(i, 0xFFFFFFFFu / AW + 1u);
-                if (r * AW > i) r--;
-                const uint32_t c = i - r * AW;
-                if (tile_flag_at(mt, rg, ax0 + (int)c, ay0 + (int)r) == 0u) l_nt[i] = make_float4(0.0f, 0.0f, 0.0f, ROMIS_FLT_MAX);
-            }
-        }
-    }
-    __syncthreads();
+    uint32_t qi[kLeanK], qp[kLeanK];   // qp: pixel indices (HG: the handle gathers)
+    lean_draws(rg, f, t, wn, ps, qi, qp, 0u, 0u);
+    lean_window_ready<TH>(mt, rg, wn, l_nt);
     // FIN: the reservoir a live lane's combine leaves -- what the planes receive -- and its shading context, for the
     // block's final shading below
     Px rpx;
@@ -1523,7 +1570,7 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
         if constexpr (FIN) goto shade; else return;
     }
     {
-        const uint32_t own = (uint32_t)(y - ay0) * AW + (uint32_t)(x - ax0);
+        const uint32_t own = wn.at(x, y);
         const float4 cn = l_nt[own];
         const float cw = own_bg ? 0.0f : (HG ? gw : l_w[own]);
         const uint32_t cm = own_bg ? (mt.m | (L << 24)) : (HG ? gm : l_m[own]);
@@ -1531,6 +1578,8 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
         const v3 cpos = xyz(l_lt[cli]), ccol = xyz(l_lt[L + 1u + cli]);
         const Px cur = make_px(s, cn, cpm, origin, pix);
         if constexpr (FIN) rpx = cur;
+        // lean_primary_miss's test, written out: through the helper k_spatial1hg_t2_dbg, at the 64-VGPR cap of 8 waves per
+        // SIMD, spills 5 VGPRs (20 B of scratch) that it does not spill this way
         if (cur.mat == s.num_materials - 1u && s.normals_bounded && !__builtin_isnan(cur.P.x + cur.P.y + cur.P.z) &&
             __builtin_isfinite(cw) && __builtin_isfinite(ccol.x + ccol.y + ccol.z)) {
             if (!odead) {
@@ -1542,8 +1591,7 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
             if (how) { how[pix] = 0.0f; hom[pix] = (cm & kHandleM) | (L << 24); }
             if constexpr (FIN) goto shade; else return;   // FIN: with the (0, 0), W = 0 reservoir just written
         }
-        const double rt = rcp_d(cur.t);
-        const bool rt_all = __all(div_fast_ok(cur.t));
+        const LeanSimilar similar(cur);
         bool ok[kLeanK];
         uint32_t qm[kLeanK];
         float qw[kLeanK];
@@ -1558,12 +1606,7 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
                     qm[n] = l_m[qi[n]];
                     qw[n] = l_w[qi[n]];
                 }
-                const float nd = vdot(xyz(g), cur.N);
-                float q = div_by_rcp_d(g.w, rt);
-                if (__builtin_expect(!rt_all, 0)) {
-                    if (!div_fast_ok(cur.t)) q = g.w / cur.t;
-                }
-                ok[n] = !(nd < 0.90630778703f) && !(fabsf(1.0f - q) > 0.1f);
+                ok[n] = similar(g);
                 if (HG && ok[n]) { qm[n] = hi.m[qp[n]]; qw[n] = hi.w[qp[n]]; }
             }
         }
@@ -1676,42 +1719,26 @@ __device__ __forceinline__ void spatialn_ntl_body(const SceneDev& s, const Regio
                                                   float4* __restrict__ ob, float2* __restrict__ odbg, MissTiles mt) {
     const GlTabs tb = gl_stage_tables<false>();   // made visible by the window's barrier below
     float4* const l_nt = g_lds;
-    uint32_t tile;
-    if (!xcd_tile(rg, num_tiles(rg), blockIdx.x, tile)) return;   // block-uniform
-    const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW;
-    const int tx0 = (int)(rg.rx0 + (tile % ntx) * kTileW), ty0 = (int)(rg.ry0 + (tile / ntx) * kTileH);
-    if (mt.m) {
-        // a tile of background pixels: after RIS and after every biased pass each holds sub-reservoir 0 = (0, W = 0),
-        // (0, M = mt.m) and the others (0, W = 0), (0, M = 0) -- the miss shortcut's result below (M_0 = the sum of
-        // the own Ms), written without reading the tile or its window
-        const int x1 = min(tx0 + (int)kTileW, (int)(rg.rx0 + rg.rw)) - 1, y1 = min(ty0 + (int)kTileH, (int)(rg.ry0 + rg.rh)) - 1;
-        if (tiles_known_miss(mt, rg, tx0, x1, ty0, y1)) {
-            const uint32_t mw = threadIdx.x >> 6, ml = threadIdx.x & 63u;
-            const int mx = tx0 + (int)(mw * 8u + (ml & 7u)), my = ty0 + (int)(ml >> 3);
-            if (mx <= x1 && my <= y1) {
-                const uint32_t mo = ((uint32_t)(my - (int)rg.vy0) * rg.vw + (uint32_t)(mx - (int)rg.vx0)) << 4;
-                const uint32_t jo = rg.js << 4;
-#pragma unroll
-                for (int j = 0; j < NT; j++) {
-                    st_at(oa, mo + (uint32_t)j * jo, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                    st_at(ob, mo + (uint32_t)j * jo, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(j == 0 ? mt.m : 0u)));
-                    if (DBG) st_at(odbg, (mo + (uint32_t)j * jo) >> 1, make_float2(ROMIS_FLT_MIN, 0.0f));
-                }
-            }
-            return;   // block-uniform, before the window's barrier
-        }
-    }
-    const int xlo = max(0, (int)rg.vx0), xhi = min((int)rg.W, (int)(rg.vx0 + rg.vw)) - 1;
-    const int ylo = max(0, (int)rg.vy0), yhi = min((int)rg.H, (int)(rg.vy0 + rg.vh)) - 1;
-    const int R = (int)f.R;
-    const int ax0 = max(tx0 - R, xlo), ax1 = min(tx0 + (int)kTileW - 1 + R, xhi);
-    const int ay0 = max(ty0 - R, ylo), ay1 = min(ty0 + (int)kTileH - 1 + R, yhi);
-    const uint32_t AW = (uint32_t)(ax1 - ax0 + 1), n_apron = AW * (uint32_t)(ay1 - ay0 + 1);
-    const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63u;
-    const int x = tx0 + (int)(w * 8u + (l & 7u)), y = ty0 + (int)(l >> 3);
-    const bool live = x < (int)(rg.rx0 + rg.rw) && y < (int)(rg.ry0 + rg.rh);
-    const uint32_t pofs = ((uint32_t)(y - (int)rg.vy0) * rg.vw + (uint32_t)(x - (int)rg.vx0)) << 4;
     const uint32_t jofs = rg.js << 4;   // bytes between sub-reservoir planes (host check: fits 32 bits)
+    LeanTile t;
+    if (!lean_tile<1>(rg, t)) return;   // block-uniform
+    // a tile of background pixels: after RIS and after every biased pass each holds sub-reservoir 0 = (0, W = 0),
+    // (0, M = mt.m) and the others (0, W = 0), (0, M = 0) -- the miss shortcut's result below (M_0 = the sum of the own
+    // Ms).  (Tiles that only partly lie in background tiles are read whole: the host keeps RIS's records at N = 2.)
+    if (lean_background_exit(mt, rg, t, t.tx0, t.x1, t.ty0, t.y1, nullptr, [&](uint32_t mp) {
+#pragma unroll
+            for (int j = 0; j < NT; j++) {
+                const uint32_t mo = (mp << 4) + (uint32_t)j * jofs;
+                st_at(oa, mo, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+                st_at(ob, mo, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(j == 0 ? mt.m : 0u)));
+                if (DBG) st_at(odbg, mo >> 1, make_float2(ROMIS_FLT_MIN, 0.0f));
+            }
+        }))
+        return;
+    const LeanWindow wn = lean_window<1>(rg, f, t);
+    const int x = t.x, y = t.y;
+    const bool live = t.live;
+    const uint32_t pofs = t.pix << 4;
     float4 cpm = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ca[NT], cb[NT];
 #pragma unroll
     for (int j = 0; j < NT; j++) { ca[j] = cpm; cb[j] = cpm; }
@@ -1720,30 +1747,18 @@ __device__ __forceinline__ void spatialn_ntl_body(const SceneDev& s, const Regio
 #pragma unroll
         for (int j = 0; j < NT; j++) { ca[j] = ld_at(ia, pofs + (uint32_t)j * jofs); cb[j] = ld_at(ib, pofs + (uint32_t)j * jofs); }
     }
-    ntl_stage_window(rg, n_t, l_nt, ax0, ay0, AW, n_apron);
+    ntl_stage_window(rg, n_t, l_nt, wn);
     const uint32_t K = f.K;   // <= kLeanK (host check)
     const uint32_t ps = pix_state(key, (uint32_t)y * rg.W + (uint32_t)x);
-    const uint32_t span = 2u * f.R + 1u;
-    uint32_t qi[kLeanK], qo[kLeanK];
-#pragma unroll
-    for (uint32_t n = 0; n < kLeanK; n++) {
-        qi[n] = 0u;
-        qo[n] = pofs;
-        if (n < K) {
-            const int nx = min(max(x - R + (int)__umulhi(draw(ps, 2u * n), span), xlo), xhi);
-            const int ny = min(max(y - R + (int)__umulhi(draw(ps, 2u * n + 1u), span), ylo), yhi);
-            qi[n] = (uint32_t)(ny - ay0) * AW + (uint32_t)(nx - ax0);
-            qo[n] = ((uint32_t)(ny - (int)rg.vy0) * rg.vw + (uint32_t)(nx - (int)rg.vx0)) << 4;
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's window copies, before the barrier
-    __syncthreads();
+    uint32_t qi[kLeanK], qo[kLeanK];   // qo: byte offsets into the float4 planes
+    lean_draws(rg, f, t, wn, ps, qi, qo, pofs, 4u);
+    lean_window_ready<1>(mt, rg, wn, l_nt);
     if (!live) return;   // no barrier follows
-    const float4 cn = l_nt[(uint32_t)(y - ay0) * AW + (uint32_t)(x - ax0)];
+    const float4 cn = l_nt[wn.at(x, y)];
     const Px cur = make_px(s, cn, cpm, origin, pofs >> 4);
-    // primary-ray miss (see spatial1_ntl_body): every neighbour is rejected and every own input weighs (0 W) M = +-0,
-    // so both go to sub-reservoir 0 (equal wSums FLT_MIN), nothing is accepted: M_0 = sum of the own Ms, W = 0
-    bool miss = cur.mat == s.num_materials - 1u && s.normals_bounded && !__builtin_isnan(cur.P.x + cur.P.y + cur.P.z);
+    // primary-ray miss: every neighbour is rejected and every own input weighs (0 W) M = +-0, so both go to
+    // sub-reservoir 0 (equal wSums FLT_MIN), nothing is accepted: M_0 = sum of the own Ms, W = 0
+    bool miss = lean_primary_miss(s, cur);
 #pragma unroll
     for (int j = 0; j < NT; j++) miss = miss && __builtin_isfinite(ca[j].w) && __builtin_isfinite(cb[j].x + cb[j].y + cb[j].z);
     if (miss) {
@@ -1758,23 +1773,10 @@ __device__ __forceinline__ void spatialn_ntl_body(const SceneDev& s, const Regio
         }
         return;
     }
-    // depth / normal heuristic (render_utils.cpp:114-118), as in spatial1_ntl_body
-    const double rt = rcp_d(cur.t);
-    const bool rt_all = __all(div_fast_ok(cur.t));
+    const LeanSimilar similar(cur);
     bool ok[kLeanK];
 #pragma unroll
-    for (uint32_t n = 0; n < kLeanK; n++) {
-        ok[n] = false;
-        if (n < K) {
-            const float4 g = l_nt[qi[n]];
-            const float nd = vdot(xyz(g), cur.N);
-            float q = div_by_rcp_d(g.w, rt);
-            if (__builtin_expect(!rt_all, 0)) {
-                if (!div_fast_ok(cur.t)) q = g.w / cur.t;
-            }
-            ok[n] = !(nd < 0.90630778703f) && !(fabsf(1.0f - q) > 0.1f);
-        }
-    }
+    for (uint32_t n = 0; n < kLeanK; n++) ok[n] = n < K && similar(l_nt[qi[n]]);
     CombN<NT> cmb;
     cmb.init(ps + 2u * K * 0x9E3779B9u);
     float4 na[NT], nb[NT];
@@ -1852,16 +1854,12 @@ __device__ __forceinline__ void spatial2hg_body(const SceneDev& s, const Region&
                                                 const float4* __restrict__ hin, float4* __restrict__ oa,
                                                 float4* __restrict__ ob, float2* __restrict__ odbg, float4* __restrict__ hout,
                                                 MissTiles mt, uint32_t odead) {
-    constexpr uint32_t kTH = kTileH * TH;
     float4* const l_nt = g_lds;
     float4* const l_lt = g_lds + apron_max(TH);
     const uint32_t L = s.num_lights;
     const uint32_t jofs = rg.js << 4;   // bytes between the sub-reservoir planes
-    uint32_t tile;
-    const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW;
-    if (!xcd_tile(rg, ntx * ((rg.rh + kTH - 1) / kTH), blockIdx.x, tile)) return;   // block-uniform
-    const int tx0 = (int)(rg.rx0 + (tile % ntx) * kTileW), ty0 = (int)(rg.ry0 + (tile / ntx) * kTH);
-    const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63u;   // wave w: the 8x8 block (w % 4, w / 4)
+    LeanTile t;
+    if (!lean_tile<TH>(rg, t)) return;   // block-uniform
     auto put = [&](uint32_t pix, const float* W, const uint32_t* M, const uint32_t* li, const float* ws, const float* ch) {
 #pragma unroll
         for (int j = 0; j < 2; j++) {
@@ -1875,37 +1873,25 @@ __device__ __forceinline__ void spatial2hg_body(const SceneDev& s, const Region&
         if (hout) hout[pix] = make_float4(W[0], __uint_as_float(M[0] | (li[0] << 24)), W[1], __uint_as_float(M[1] | (li[1] << 24)));
     };
     bool mixed = false;
-    if (mt.m) {
-        // a tile of background pixels: sub-reservoir 0 = (0, W = 0), (0, M = mt.m), sub-reservoir 1 = (0, W = 0), (0, M = 0)
-        // -- the miss shortcut's result below, written without reading the tile, its window or its neighbours.  The
-        // light table is not staged: the zero sample's (position, colour) are written as zeros
-        const int x1 = min(tx0 + (int)kTileW, (int)(rg.rx0 + rg.rw)) - 1, y1 = min(ty0 + (int)kTH, (int)(rg.ry0 + rg.rh)) - 1;
-        if (tiles_known_miss(mt, rg, tx0, x1, ty0, y1, &mixed)) {
-            const int mx = tx0 + (int)((w & 3u) * 8u + (l & 7u)), my = ty0 + (int)((w >> 2) * 8u + (l >> 3));
-            if (mx <= x1 && my <= y1) {
-                const uint32_t mp = (uint32_t)(my - (int)rg.vy0) * rg.vw + (uint32_t)(mx - (int)rg.vx0);
+    // a tile of background pixels: sub-reservoir 0 = (0, W = 0), (0, M = mt.m), sub-reservoir 1 = (0, W = 0), (0, M = 0)
+    // -- the miss shortcut's result below.  The light table is not staged: the zero sample's (position, colour) are
+    // written as zeros
+    if (lean_background_exit(mt, rg, t, t.tx0, t.x1, t.ty0, t.y1, &mixed, [&](uint32_t mp) {
 #pragma unroll
-                for (int j = 0; j < 2; j++) {
-                    if (!odead) {
-                        st_at(oa, (mp << 4) + (uint32_t)j * jofs, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                        st_at(ob, (mp << 4) + (uint32_t)j * jofs, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(j == 0 ? mt.m : 0u)));
-                    }
-                    if (DBG) st_at(odbg, ((mp << 4) + (uint32_t)j * jofs) >> 1, make_float2(ROMIS_FLT_MIN, 0.0f));
+            for (int j = 0; j < 2; j++) {
+                if (!odead) {
+                    st_at(oa, (mp << 4) + (uint32_t)j * jofs, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+                    st_at(ob, (mp << 4) + (uint32_t)j * jofs, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(j == 0 ? mt.m : 0u)));
                 }
-                if (hout) hout[mp] = make_float4(0.0f, __uint_as_float(mt.m | (L << 24)), 0.0f, __uint_as_float(L << 24));
+                if (DBG) st_at(odbg, ((mp << 4) + (uint32_t)j * jofs) >> 1, make_float2(ROMIS_FLT_MIN, 0.0f));
             }
-            return;   // block-uniform, before the window's barrier
-        }
-    }
-    const int xlo = max(0, (int)rg.vx0), xhi = min((int)rg.W, (int)(rg.vx0 + rg.vw)) - 1;
-    const int ylo = max(0, (int)rg.vy0), yhi = min((int)rg.H, (int)(rg.vy0 + rg.vh)) - 1;
-    const int R = (int)f.R;
-    const int ax0 = max(tx0 - R, xlo), ax1 = min(tx0 + (int)kTileW - 1 + R, xhi);
-    const int ay0 = max(ty0 - R, ylo), ay1 = min(ty0 + (int)kTH - 1 + R, yhi);
-    const uint32_t AW = (uint32_t)(ax1 - ax0 + 1), n_apron = AW * (uint32_t)(ay1 - ay0 + 1);
-    const int x = tx0 + (int)((w & 3u) * 8u + (l & 7u)), y = ty0 + (int)((w >> 2) * 8u + (l >> 3));
-    const bool live = x < (int)(rg.rx0 + rg.rw) && y < (int)(rg.ry0 + rg.rh);
-    const uint32_t pix = (uint32_t)(y - (int)rg.vy0) * rg.vw + (uint32_t)(x - (int)rg.vx0);
+            if (hout) hout[mp] = make_float4(0.0f, __uint_as_float(mt.m | (L << 24)), 0.0f, __uint_as_float(L << 24));
+        }))
+        return;
+    const LeanWindow wn = lean_window<TH>(rg, f, t);
+    const int x = t.x, y = t.y;
+    const bool live = t.live;
+    const uint32_t pix = t.pix;
     float4 cpm = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 ch = make_float4(0.0f, __uint_as_float(L << 24), 0.0f, __uint_as_float(L << 24));   // the own handle record
     const bool own_bg = live && mixed && tile_flag_at(mt, rg, x, y) == 0u;   // a background RIS tile: known, unread
@@ -1918,56 +1904,21 @@ __device__ __forceinline__ void spatial2hg_body(const SceneDev& s, const Region&
             ch = hin[pix];
         }
     }
-    ntl_stage_window<TH>(rg, n_t, l_nt, ax0, ay0, AW, n_apron);
-    {   // the light table behind the window: positions, zero, colours, zero (h_stage)
-        constexpr uint32_t kThreads = 256u * TH;
-        const uint32_t nd = 2u * L + 2u, w64 = (threadIdx.x >> 6) << 6;
-        for (uint32_t d0 = 0; d0 < nd; d0 += kThreads) {
-            const uint32_t d = d0 + threadIdx.x;
-            if (d < nd && d != L && d != 2u * L + 1u)
-                __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(d < L ? s.light_c2 + d : s.light_c2 + (d - 1u)),
-                                                 (__attribute__((address_space(3))) void*)(l_lt + d0 + w64), 16, 0, 0);
-        }
-        if (threadIdx.x < 2u) l_lt[threadIdx.x ? 2u * L + 1u : L] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
+    ntl_stage_window<TH>(rg, n_t, l_nt, wn);
+    stage_light_table<256u * TH>(s, l_lt);   // behind the window
     const GlTabs tb = gl_stage_tables_dma();
     const uint32_t K = f.K;   // <= kLeanK (host check)
     const uint32_t ps = pix_state(key, (uint32_t)y * rg.W + (uint32_t)x);
-    const uint32_t span = 2u * f.R + 1u;
-    uint32_t qi[kLeanK], qp[kLeanK];
-#pragma unroll
-    for (uint32_t n = 0; n < kLeanK; n++) {
-        qi[n] = 0u;
-        qp[n] = pix;
-        if (n < K) {
-            const int nx = min(max(x - R + (int)__umulhi(draw(ps, 2u * n), span), xlo), xhi);
-            const int ny = min(max(y - R + (int)__umulhi(draw(ps, 2u * n + 1u), span), ylo), yhi);
-            qi[n] = (uint32_t)(ny - ay0) * AW + (uint32_t)(nx - ax0);
-            qp[n] = (uint32_t)(ny - (int)rg.vy0) * rg.vw + (uint32_t)(nx - (int)rg.vx0);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave's DMA before the barrier (spatial1_ntl_body)
-    if (mt.m && mt.gbuf) {   // background G-buffer records: spatial1_ntl_body's window fix-up
-        constexpr uint32_t kThreads = 256u * TH, kPer = (apron_max(TH) + kThreads - 1u) / kThreads;
-#pragma unroll
-        for (uint32_t k = 0; k < kPer; k++) {
-            const uint32_t i = threadIdx.x + kThreads * k;
-            if (i < n_apron) {
-                uint32_t r = __umulhi(i, 0xFFFFFFFFu / AW + 1u);
-                if (r * AW > i) r--;
-                const uint32_t c = i - r * AW;
-                if (tile_flag_at(mt, rg, ax0 + (int)c, ay0 + (int)r) == 0u) l_nt[i] = make_float4(0.0f, 0.0f, 0.0f, ROMIS_FLT_MAX);
-            }
-        }
-    }
-    __syncthreads();
+    uint32_t qi[kLeanK], qp[kLeanK];   // qp: pixel indices (the handle gathers)
+    lean_draws(rg, f, t, wn, ps, qi, qp, pix, 0u);
+    lean_window_ready<TH>(mt, rg, wn, l_nt);
     if (!live) return;   // no barrier follows
-    const float4 cn = l_nt[(uint32_t)(y - ay0) * AW + (uint32_t)(x - ax0)];
+    const float4 cn = l_nt[wn.at(x, y)];
     const float cw[2] = {ch.x, ch.z};
     const uint32_t cm[2] = {__float_as_uint(ch.y), __float_as_uint(ch.w)};
     const Px cur = make_px(s, cn, cpm, origin, pix);
-    // primary-ray miss (spatialn_ntl_body): both own inputs go to sub-reservoir 0, nothing is accepted
-    bool miss = cur.mat == s.num_materials - 1u && s.normals_bounded && !__builtin_isnan(cur.P.x + cur.P.y + cur.P.z);
+    // primary-ray miss: both own inputs go to sub-reservoir 0 (equal wSums FLT_MIN), nothing is accepted
+    bool miss = lean_primary_miss(s, cur);
 #pragma unroll
     for (int j = 0; j < 2; j++) {
         const v3 cc = xyz(l_lt[L + 1u + (cm[j] >> 24)]);
@@ -1979,24 +1930,14 @@ __device__ __forceinline__ void spatial2hg_body(const SceneDev& s, const Region&
         put(pix, W0, M, li, ws, c0);
         return;
     }
-    const double rt = rcp_d(cur.t);
-    const bool rt_all = __all(div_fast_ok(cur.t));
+    const LeanSimilar similar(cur);
     bool ok[kLeanK];
     float4 qh[kLeanK];
 #pragma unroll
     for (uint32_t n = 0; n < kLeanK; n++) {
-        ok[n] = false;
+        ok[n] = n < K && similar(l_nt[qi[n]]);
         qh[n] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (n < K) {
-            const float4 g = l_nt[qi[n]];
-            const float nd = vdot(xyz(g), cur.N);
-            float q = div_by_rcp_d(g.w, rt);
-            if (__builtin_expect(!rt_all, 0)) {
-                if (!div_fast_ok(cur.t)) q = g.w / cur.t;
-            }
-            ok[n] = !(nd < 0.90630778703f) && !(fabsf(1.0f - q) > 0.1f);
-            if (ok[n]) qh[n] = hin[qp[n]];
-        }
+        if (ok[n]) qh[n] = hin[qp[n]];
     }
     Comb2h cmb;
     cmb.init(ps + 2u * K * 0x9E3779B9u, L);
@@ -2076,38 +2017,30 @@ __device__ __forceinline__ void spatial1u_body(const SceneDev& s, const Region& 
                                                float4* __restrict__ oa, float4* __restrict__ ob, float2* __restrict__ odbg,
                                                const float* __restrict__ rp_in, const float* __restrict__ rp_nb,
                                                float* __restrict__ rp_out, uint8_t* __restrict__ vis_out, MissTiles mt) {
-    uint32_t tile;
-    if (!xcd_tile(rg, num_tiles(rg), blockIdx.x, tile)) return;   // block-uniform, before any barrier
-    const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW;
-    const int tx0 = (int)(rg.rx0 + (tile % ntx) * kTileW), ty0 = (int)(rg.ry0 + (tile / ntx) * kTileH);
-    const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63u;
-    const int x = tx0 + (int)(w * 8u + (l & 7u)), y = ty0 + (int)(l >> 3);
+    LeanTile t;
+    if (!lean_tile<1>(rg, t)) return;   // block-uniform, before any barrier
+    const int x = t.x, y = t.y;
     const uint32_t K = f.K;   // <= kLeanK (host check)
     bool mixed = false;   // some input lies in a background tile (whose RIS reservoir may be unwritten: substituted)
-    if (mt.m) {
-        // the tile and every pixel its neighbour draws can reach (grown by R, clamped to the image and the view) are
-        // background pixels holding (0, W = 0), (0, M = mt.m): the miss shortcut's result below with M = (K + 1) mt.m
-        const int x1 = min(tx0 + (int)kTileW, (int)(rg.rx0 + rg.rw)) - 1, y1 = min(ty0 + (int)kTileH, (int)(rg.ry0 + rg.rh)) - 1;
-        const int gx0 = max(max(tx0 - (int)f.R, 0), (int)rg.vx0), gy0 = max(max(ty0 - (int)f.R, 0), (int)rg.vy0);
-        const int gx1 = min(min(x1 + (int)f.R, (int)rg.W - 1), (int)(rg.vx0 + rg.vw) - 1);
-        const int gy1 = min(min(y1 + (int)f.R, (int)rg.H - 1), (int)(rg.vy0 + rg.vh) - 1);
-        if (tiles_known_miss(mt, rg, gx0, gx1, gy0, gy1, &mixed)) {
-            if (x <= x1 && y <= y1) {
-                const uint32_t mo = ((uint32_t)(y - (int)rg.vy0) * rg.vw + (uint32_t)(x - (int)rg.vx0)) << 4;
-                st_at(oa, mo, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                st_at(ob, mo, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((K + 1u) * mt.m)));
-                if (DBG) st_at(odbg, mo >> 1, make_float2(ROMIS_FLT_MIN, 0.0f));
-                if (rp_out) st_at(rp_out, mo >> 2, 0.0f);
-                if (vis_out) vis_out[mo >> 4] = 0u;
-            }
-            return;   // block-uniform, before the BVH's barrier
-        }
-    }
+    // the tile and every pixel its neighbour draws can reach (grown by R, clamped to the image and the view) are
+    // background pixels holding (0, W = 0), (0, M = mt.m): the miss shortcut's result below with M = (K + 1) mt.m
+    const int gx0 = max(max(t.tx0 - (int)f.R, 0), (int)rg.vx0), gy0 = max(max(t.ty0 - (int)f.R, 0), (int)rg.vy0);
+    const int gx1 = min(min(t.x1 + (int)f.R, (int)rg.W - 1), (int)(rg.vx0 + rg.vw) - 1);
+    const int gy1 = min(min(t.y1 + (int)f.R, (int)rg.H - 1), (int)(rg.vy0 + rg.vh) - 1);
+    if (lean_background_exit(mt, rg, t, gx0, gx1, gy0, gy1, &mixed, [&](uint32_t mp) {
+            const uint32_t mo = mp << 4;
+            st_at(oa, mo, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+            st_at(ob, mo, make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((K + 1u) * mt.m)));
+            if (DBG) st_at(odbg, mo >> 1, make_float2(ROMIS_FLT_MIN, 0.0f));
+            if (rp_out) st_at(rp_out, mo >> 2, 0.0f);
+            if (vis_out) vis_out[mp] = 0u;
+        }))
+        return;   // before the BVH's barrier
     const Bvh bvh = VIS ? stage_bvh(s, g_lds) : global_bvh(s);   // ends with a barrier (every thread gets here)
     const GlTabs tb = gl_stage_tables();
-    if (x >= (int)(rg.rx0 + rg.rw) || y >= (int)(rg.ry0 + rg.rh)) return;
+    if (!t.live) return;
     const int rx = x - (int)rg.vx0, ry = y - (int)rg.vy0;
-    const uint32_t pofs = ((uint32_t)ry * rg.vw + (uint32_t)rx) << 4;
+    const uint32_t pofs = t.pix << 4;
     // an input pixel of a background tile holds the known (0, W = 0), (0, M = mt.m), pdf 0 (RIS may not have stored
     // them, its skip_res): in blocks whose neighbourhood meets such a tile (block-uniform) they are not read
     const uint32_t ntxv = (rg.vw + kTileW - 1u) / kTileW;
@@ -2150,8 +2083,8 @@ __device__ __forceinline__ void spatial1u_body(const SceneDev& s, const Region& 
         qo[n] = pofs;
         qk[n] = own_known;
         if (n < K) {
-            const int nx = min(max(bx + (int)__umulhi(draw(ps, 2u * n), span), xlo), xhi);
-            const int ny = min(max(by + (int)__umulhi(draw(ps, 2u * n + 1u), span), ylo), yhi);
+            int nx, ny;
+            lean_draw(ps, n, span, bx, by, xlo, xhi, ylo, yhi, nx, ny);
             qo[n] = ((uint32_t)ny * rg.vw + (uint32_t)nx) << 4;
             qk[n] = known(nx, ny);
         }
@@ -2164,8 +2097,7 @@ __device__ __forceinline__ void spatial1u_body(const SceneDev& s, const Region& 
     // stays FLT_MIN, the held sample is the initial (0, 0) one and W = 0 (p-hat 0, reservoir.cpp:99).  Unlike the biased
     // pass nothing is rejected (combineUnbiased takes every neighbour), so M sums all K + 1 inputs: their reservoirs are
     // still read, their K target pdfs and the Z loop are not.  (C5: 87 % of the 8K frame's pixels miss the box.)
-    if (cur.mat == s.num_materials - 1u && s.normals_bounded && !__builtin_isnan(cur.P.x + cur.P.y + cur.P.z) &&
-        (!rp_in || pd_cached == 0.0f)) {
+    if (lean_primary_miss(s, cur) && (!rp_in || pd_cached == 0.0f)) {
         bool fin = __builtin_isfinite(ca.w) && __builtin_isfinite(na[0].w);
         uint32_t m = __float_as_uint(cb.w) + __float_as_uint(nb[0].w);
 #pragma unroll
@@ -2877,6 +2809,47 @@ hipError_t launch_temporal(const SceneDev& s, const Region& rg0, const FeaturesD
     return hipGetLastError();
 }
 
+// The automatic XCD chunks (spatial.xcd_rows / spatial.xcd_cols left at auto) of a lean spatial kernel
+enum class XcdChunks {
+    kL2Rows,    // whole tile rows, as many as one XCD's L2 holds
+    kOneRow,    // one tile row (the staged and gathered sample-handle kernels on 32 x 16 tiles)
+    kThirds,    // 32 x 8 tiles: from 24 tiles a row 2-D chunks of 8 rows x a third of the row, else kL2Rows
+    kGrid4x8,   // light-grid handles, 32 x 16 tiles: from 64 tiles a row 2-D chunks of 4 x 8 tiles, else kL2Rows
+};
+// The grid of a lean spatial kernel: one block per 32 x 8 th tile of the rect in xcd_tile's order, rounded to the XCD
+// that owns the most tiles.  Sets rg.xcd_rows / rg.xcd_cols: the knobs where they are explicit (an explicit
+// spatial.xcd_rows counts rows of the kernel's own tiles), else the kernel's rule.
+static uint32_t lean_grid(Region& rg, const Tuning& tu, uint32_t th, XcdChunks rule) {
+    const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW, nty = (rg.rh + th * kTileH - 1) / (th * kTileH);
+    const bool auto_rows = tu.spatial_xcd_rows == kXcdRowsAuto, auto_cols = tu.spatial_xcd_cols == kXcdColsAuto;
+    rg.xcd_rows = tu.spatial_xcd_rows;
+    rg.xcd_cols = auto_cols ? 0u : tu.spatial_xcd_cols;
+    if (auto_rows) {
+        // a chunk's records (n_t, p_mat, res_a, res_b: 64 B/px over 8-px tile rows) within one XCD's 4 MB L2:
+        // 4 tile rows at 1920 px, 2 at 3840 (kbench: 4K 239 -> 225 us with 2, 1080p best with 4; r2bb); half as many
+        // of the twice as tall 32 x 16 tile rows
+        rg.xcd_rows = std::max(1u, std::min(8u, 8192u / std::max(rg.rw, 1u)) / th);
+        // the handle kernels: one 32 x 16 row (k_spatial1h_t2 at C2: 66.1 / 65.7 us against 66.7 / 66.3 with two,
+        // 72.9 / 72.5 with four; profiles/r5/probes/r5p23)
+        if (rule == XcdChunks::kOneRow) rg.xcd_rows = 1u;
+    }
+    if (rule == XcdChunks::kThirds && auto_cols && rg.xcd_rows && ntx >= 24u) {
+        // 2-D chunks: 8 tile rows x a third of the tile row (an odd number of chunks per chunk row, so the
+        // round-robin XCDs cover every column).  C2: fetch 83 -> 66 B/px at the same time (profiles/r4/r4g,
+        // r4h): the window rows a chunk's consecutive tile rows share stay in the XCD's L2.
+        if (auto_rows) rg.xcd_rows = 8u;
+        rg.xcd_cols = (ntx + 2u) / 3u;
+    }
+    if (rule == XcdChunks::kGrid4x8 && auto_rows && auto_cols && ntx >= 64u) {
+        // wide frames: 2-D chunks of 4 x 8 tiles (128 x 64 px), so the +-R window rows of vertically adjacent tiles
+        // are re-read from one XCD's L2: C4f HBM traffic 1.30 -> 1.01x algorithmic (FETCH 770 -> 541 MB a launch),
+        // spatial 404.5 -> 398.2 us (round 6, profiles/r6/probes/s4)
+        rg.xcd_rows = 4u;
+        rg.xcd_cols = 8u;
+    }
+    return rg.xcd_rows ? xcd_grid(rg, ntx, nty) : ntx * nty;
+}
+
 hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDev& f, uint32_t key, const float* o,
                           const float4* n_t, const float4* p_mat, const float4* ia, const float4* ib, float4* oa,
                           float4* ob, float2* odbg, const float* rp_in, const float* rp_nb, float* rp_out,
@@ -2888,7 +2861,6 @@ hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDe
     if (vis_written) *vis_written = false;
     if (rg0.rw == 0 || rg0.rh == 0) return hipSuccess;
     Region rg = with_map(rg0, 2u);   // 32 x 8 tiles of 8 x 8 waves (the lean kernels' XCD tile order, xcd_tile)
-    uint32_t grid = items_of(rg);
     const size_t bvh_bytes = bvh_lds_bytes(s);
     const bool lean = tu.spatial_lean && f.N == 1 && f.K <= kLeanK && rg.ps == 1u && rg.map2d == 2u &&
                       (size_t)rg.vw * rg.vh * 16u <= 0xFFFFFFFFull;
@@ -2897,11 +2869,7 @@ hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDe
                        (size_t)rg.js * 16u + (size_t)rg.vw * rg.vh * 16u <= 0xFFFFFFFFull;
     if (lean && f.unbiased && (!f.spatial_vis || bvh_bytes <= kLdsBudget)) {
         // combineUnbiased, N = 1: one block per tile in the XCD order of the biased pass (xcd_tile)
-        const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW, nty = (rg.rh + kTileH - 1) / kTileH;
-        rg.xcd_rows = tu.spatial_xcd_rows == kXcdRowsAuto ? std::max(1u, std::min(8u, 8192u / std::max(rg.rw, 1u)))
-                                                          : tu.spatial_xcd_rows;
-        rg.xcd_cols = tu.spatial_xcd_cols == kXcdColsAuto ? 0u : tu.spatial_xcd_cols;
-        if (rg.xcd_rows) grid = xcd_grid(rg, ntx, nty);
+        const uint32_t grid = lean_grid(rg, tu, 1u, XcdChunks::kL2Rows);
         auto k = f.spatial_vis ? (odbg ? k_spatial1u_vis_dbg : k_spatial1u_vis) : (odbg ? k_spatial1u_dbg : k_spatial1u);
         uint8_t* vo = f.spatial_vis ? vis_out : nullptr;   // the own-pixel shadow ray, for final shading (N = 1)
         ROMIS_LAUNCH(k, dim3(grid), dim3(kBlock), f.spatial_vis ? bvh_bytes : 0, stream, s, rg, f, key, o[0], o[1], o[2],
@@ -2913,16 +2881,11 @@ hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDe
     if (lean2 && !f.unbiased && f.R <= kLdsSpatialR) {
         // N = 2 biased: one block per tile in the XCD chunk order (xcd_tile); spatial.lds != 3 selects the general
         // kernel for A/B runs, as for N = 1.  No pdf cache at N = 2 (*rp_written stays false)
-        const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW, nty = (rg.rh + kTileH - 1) / kTileH;
-        rg.xcd_rows = tu.spatial_xcd_rows == kXcdRowsAuto ? std::max(1u, std::min(8u, 8192u / std::max(rg.rw, 1u)))
-                                                          : tu.spatial_xcd_rows;
-        rg.xcd_cols = tu.spatial_xcd_cols == kXcdColsAuto ? 0u : tu.spatial_xcd_cols;
         if (hin.w) {
             // handle records (k_spatial2hg[_t2], spatial_handle_kind 2): 32 x 8 TH tiles, TH = spatial.th (auto 1)
             if (s.light_types != 1u) return hipErrorInvalidValue;
-            const uint32_t th = tu.spatial_th == 2u ? 2u : 1u, ntyh = (rg.rh + th * kTileH - 1) / (th * kTileH);
-            if (th == 2u && rg.xcd_rows && tu.spatial_xcd_rows == kXcdRowsAuto) rg.xcd_rows = std::max(1u, rg.xcd_rows / 2u);
-            grid = rg.xcd_rows ? xcd_grid(rg, ntx, ntyh) : ntx * ntyh;
+            const uint32_t th = tu.spatial_th == 2u ? 2u : 1u;
+            const uint32_t grid = lean_grid(rg, tu, th, XcdChunks::kL2Rows);
             const size_t lds = (size_t)apron_max(th) * 16u + (size_t)(2u * s.num_lights + 2u) * 16u;
             auto k = th == 2u ? (odbg ? k_spatial2hg_t2_dbg : k_spatial2hg_t2) : (odbg ? k_spatial2hg_dbg : k_spatial2hg);
             ROMIS_LAUNCH(k, dim3(grid), dim3(th * kBlock), lds, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat,
@@ -2930,43 +2893,20 @@ hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDe
                          hout.res_dead);
             return hipGetLastError();
         }
-        if (rg.xcd_rows) grid = xcd_grid(rg, ntx, nty);
+        const uint32_t grid = lean_grid(rg, tu, 1u, XcdChunks::kL2Rows);
         ROMIS_LAUNCH(odbg ? k_spatial2_ntl_dbg : k_spatial2_ntl, dim3(grid), dim3(kBlock), kApronMax * 16u, stream, s, rg, f,
                      key, o[0], o[1], o[2], n_t, p_mat, ia, ib, oa, ob, odbg, mt);
         return hipGetLastError();
     }
     if (lean && !f.unbiased && f.R <= kLdsSpatialR) {
-        // one block per tile (the lean kernels do not loop over tiles, so spatial.blocks does not apply here),
-        // grid rounded to the XCD that owns the most tiles (xcd_tile)
-        const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW, nty = (rg.rh + kTileH - 1) / kTileH;
-        rg.xcd_rows = tu.spatial_xcd_rows;
-        if (rg.xcd_rows == kXcdRowsAuto) {
-            // a chunk's records (n_t, p_mat, res_a, res_b: 64 B/px over 8-px tile rows) within one XCD's 4 MB L2:
-            // 4 tile rows at 1920 px, 2 at 3840 (kbench: 4K 239 -> 225 us with 2, 1080p best with 4; r2bb)
-            rg.xcd_rows = std::max(1u, std::min(8u, 8192u / std::max(rg.rw, 1u)));
-        }
-        rg.xcd_cols = tu.spatial_xcd_cols == kXcdColsAuto ? 0u : tu.spatial_xcd_cols;
-        if (rg.xcd_rows) grid = xcd_grid(rg, ntx, nty);
+        // one block per tile (the lean kernels do not loop over tiles, so spatial.blocks does not apply here)
         // 32x16 tiles (k_spatial1_ntl_t2) where the auto XCD chunk is at most 2 tile rows (wide images): C4 222 ->
         // 203 us, C2 76.8 -> 79.0 (cfg_kbench, profiles/r3/r3k); spatial.th = 1 / 2 forces either
         const uint32_t th = tu.spatial_th ? tu.spatial_th : (8192u / std::max(rg.rw, 1u) <= 2u ? 2u : 1u);
         if (hin.w && s.light_types != 1u) {
-            // light-grid handles (spatial_handle_kind 1): k_spatial1_ntl_t2's grid, the colours behind the window
+            // light-grid handles (spatial_handle_kind 1): k_spatial1_ntl_t2's tiles, the colours behind the window
             if (tu.spatial_th == 1u) return hipErrorInvalidValue;
-            const uint32_t nty2 = (rg.rh + 2u * kTileH - 1) / (2u * kTileH);
-            if (rg.xcd_rows) {
-                if (tu.spatial_xcd_rows == kXcdRowsAuto) rg.xcd_rows = std::max(1u, rg.xcd_rows / 2u);
-                if (tu.spatial_xcd_rows == kXcdRowsAuto && tu.spatial_xcd_cols == kXcdColsAuto && ntx >= 64u) {
-                    // wide frames: 2-D chunks of 4 x 8 tiles (128 x 64 px), so the +-R window rows of vertically
-                    // adjacent tiles are re-read from one XCD's L2: C4f HBM traffic 1.30 -> 1.01x algorithmic (FETCH
-                    // 770 -> 541 MB a launch), spatial 404.5 -> 398.2 us (round 6, profiles/r6/probes/s4)
-                    rg.xcd_rows = 4u;
-                    rg.xcd_cols = 8u;
-                }
-                grid = xcd_grid(rg, ntx, nty2);
-            } else {
-                grid = ntx * nty2;
-            }
+            const uint32_t grid = lean_grid(rg, tu, 2u, XcdChunks::kGrid4x8);
             ROMIS_LAUNCH(odbg ? k_spatial1g_t2_dbg : k_spatial1g_t2, dim3(grid), dim3(2u * kBlock),
                          apron_max(2) * 16u + s.num_lights * 16u, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat, oa,
                          ob, odbg, rp_in, rp_out, mt, reinterpret_cast<const float4*>(hin.w),
@@ -2974,13 +2914,7 @@ hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDe
         } else if (hin.w && tu.spatial_gather && tu.spatial_th != 1u) {
             // sample handles gathered instead of staged (k_spatial1hg_t2, spatial.gather; round 6): 32 x 16 tiles, the
             // automatic XCD chunk one tile row as for k_spatial1h_t2
-            const uint32_t ntyh = (rg.rh + 2u * kTileH - 1) / (2u * kTileH);
-            if (rg.xcd_rows) {
-                if (tu.spatial_xcd_rows == kXcdRowsAuto) rg.xcd_rows = 1u;
-                grid = xcd_grid(rg, ntx, ntyh);
-            } else {
-                grid = ntx * ntyh;
-            }
+            const uint32_t grid = lean_grid(rg, tu, 2u, XcdChunks::kOneRow);
             const size_t lds = (size_t)apron_max(2) * 16u + (size_t)(2u * s.num_lights + 2u) * 16u;
             const HandlesIn hi{hin.w, hin.m};
             // final shading in the same kernel (FusedFinal, launch.h): launch_final's conditions for k_final_n1_sorted,
@@ -2999,50 +2933,21 @@ hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDe
                          hout.res_dead);
         } else if (hin.w) {
             // sample handles (k_spatial1h[_t2]): 32 x 8 TH tiles, TH = spatial.th (auto: 2 -- C2 66.9 us against 76.2 for
-            // 32 x 8, 70.6 / 68.4 for 32 x 24 / 32 x 32, kbench, profiles/r5); the XCD chunks hold xcd_rows tile rows,
-            // automatically one 32 x 16 row (C2: 66.1 / 65.7 us against 66.7 / 66.3 with two, 72.9 / 72.5 with four;
-            // profiles/r5/probes/r5p23)
+            // 32 x 8, 70.6 / 68.4 for 32 x 24 / 32 x 32, kbench, profiles/r5); 32 x 8 tiles take k_spatial1_ntl's chunks
             const uint32_t hth = tu.spatial_th ? tu.spatial_th : 2u;
-            if (hth > 1u) {
-                const uint32_t ntyh = (rg.rh + hth * kTileH - 1) / (hth * kTileH);
-                if (rg.xcd_rows) {
-                    if (tu.spatial_xcd_rows == kXcdRowsAuto) rg.xcd_rows = 1u;
-                    grid = xcd_grid(rg, ntx, ntyh);
-                } else {
-                    grid = ntx * ntyh;
-                }
-            } else if (tu.spatial_xcd_cols == kXcdColsAuto && rg.xcd_rows && ntx >= 24u) {
-                if (tu.spatial_xcd_rows == kXcdRowsAuto) rg.xcd_rows = 8u;
-                rg.xcd_cols = (ntx + 2u) / 3u;
-                grid = xcd_grid(rg, ntx, nty);
-            }
+            const uint32_t grid = lean_grid(rg, tu, hth, hth > 1u ? XcdChunks::kOneRow : XcdChunks::kThirds);
             const size_t lds = (size_t)h_lds_f4(hth) * 16u + (size_t)(2u * s.num_lights + 2u) * 16u;
             const HandlesIn hi{hin.w, hin.m};
             auto k = hth == 2u ? (odbg ? k_spatial1h_t2_dbg : k_spatial1h_t2) : (odbg ? k_spatial1h_dbg : k_spatial1h);
             ROMIS_LAUNCH(k, dim3(grid), dim3(hth * kBlock), lds, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat, hi, oa,
                          ob, odbg, rp_in, rp_out, hout.w, hout.m, mt, hout.res_dead);
         } else if (th >= 2u) {
-            // 32x16 tiles: the chunks hold half as many (twice as tall) tile rows
-            const uint32_t nty2 = (rg.rh + 2u * kTileH - 1) / (2u * kTileH);
-            if (rg.xcd_rows) {
-                // an explicit spatial.xcd_rows counts 32 x 16 tile rows here; the automatic one is halved
-                if (tu.spatial_xcd_rows == kXcdRowsAuto) rg.xcd_rows = std::max(1u, rg.xcd_rows / 2u);
-                grid = xcd_grid(rg, ntx, nty2);
-            } else {
-                grid = ntx * nty2;
-            }
+            const uint32_t grid = lean_grid(rg, tu, 2u, XcdChunks::kL2Rows);   // 32x16 tiles
             ROMIS_LAUNCH(odbg ? k_spatial1_ntl_t2_dbg : k_spatial1_ntl_t2, dim3(grid), dim3(2u * kBlock),
                          apron_max(2) * 16u, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat, ia, ib, oa, ob, odbg,
                          rp_in, rp_out, mt);
         } else {
-            if (tu.spatial_xcd_cols == kXcdColsAuto && rg.xcd_rows && ntx >= 24u) {
-                // 2-D chunks: 8 tile rows x a third of the tile row (an odd number of chunks per chunk row, so the
-                // round-robin XCDs cover every column).  C2: fetch 83 -> 66 B/px at the same time (profiles/r4/r4g,
-                // r4h): the window rows a chunk's consecutive tile rows share stay in the XCD's L2.
-                if (tu.spatial_xcd_rows == kXcdRowsAuto) rg.xcd_rows = 8u;
-                rg.xcd_cols = (ntx + 2u) / 3u;
-                grid = xcd_grid(rg, ntx, nty);
-            }
+            const uint32_t grid = lean_grid(rg, tu, 1u, XcdChunks::kThirds);
             ROMIS_LAUNCH(odbg ? k_spatial1_ntl_dbg : k_spatial1_ntl, dim3(grid), dim3(kBlock),
                          kApronMax * 16u, stream,
                          s, rg, f, key, o[0], o[1], o[2], n_t, p_mat, ia, ib, oa, ob, odbg, rp_in, rp_out, mt);
@@ -3054,8 +2959,8 @@ hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDe
     auto k = f.unbiased ? (f.N == 1 ? k_spatial_n1_unbiased : (f.N == 2 ? k_spatial_n2_unbiased : k_spatial_n0_unbiased))
                         : (f.N == 1 ? k_spatial_n1_biased : (f.N == 2 ? k_spatial_n2_biased : k_spatial_n0_biased));
     const uint32_t bvh_lds = (f.unbiased && f.spatial_vis && bvh_bytes <= kLdsBudget) ? 1u : 0u;
-    ROMIS_LAUNCH(k, dim3(grid), dim3(kBlock), bvh_lds ? bvh_bytes : 0, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat,
-                       ia, ib, oa, ob, odbg, bvh_lds);
+    ROMIS_LAUNCH(k, dim3(items_of(rg)), dim3(kBlock), bvh_lds ? bvh_bytes : 0, stream, s, rg, f, key, o[0], o[1], o[2], n_t,
+                 p_mat, ia, ib, oa, ob, odbg, bvh_lds);
     return hipGetLastError();
 }
 
