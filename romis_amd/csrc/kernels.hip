@@ -1081,12 +1081,15 @@ struct LeanWindow {
     int xlo, xhi, ylo, yhi;   // neighbour clamp bounds (render_utils.cpp:109-110: the image; here also the stored view)
     int ax0, ay0;             // the window's first pixel
     uint32_t AW, n_apron;     // entries per row, entries
-    uint32_t magic;           // 0xFFFFFFFF / AW + 1
+    uint32_t magic;           // 0xFFFFFFFF / AW
     __device__ __forceinline__ uint32_t at(int x, int y) const { return (uint32_t)(y - ay0) * AW + (uint32_t)(x - ax0); }
-    // the row i / AW of entry i < 2^16, by the reciprocal instead of a division
+    // the row i / AW of entry i < 2^16, by the reciprocal instead of a division; exact for every AW >= 1 (the windows
+    // have 1 .. 52).  2^32 / AW - 1 <= magic <= 2^32 / AW, so the product's high word lies in (i / AW - 2^-16, i / AW]:
+    // one row short at the most, which the comparison adds back.  (Rounding magic up and stepping down instead wraps
+    // magic to 0 at AW = 1 -- R = 0 on a one-pixel-wide last tile column -- and made every row 0.)
     __device__ __forceinline__ uint32_t row(uint32_t i) const {
         uint32_t r = __umulhi(i, magic);
-        if (r * AW > i) r--;
+        if ((r + 1u) * AW <= i) r++;
         return r;
     }
 };
@@ -1101,7 +1104,7 @@ __device__ __forceinline__ LeanWindow lean_window(const Region& rg, const Featur
     const int ax1 = min(t.tx0 + (int)kTileW - 1 + R, wn.xhi), ay1 = min(t.ty0 + (int)(kTileH * TH) - 1 + R, wn.yhi);
     wn.AW = (uint32_t)(ax1 - wn.ax0 + 1);
     wn.n_apron = wn.AW * (uint32_t)(ay1 - wn.ay0 + 1);
-    wn.magic = 0xFFFFFFFFu / wn.AW + 1u;
+    wn.magic = 0xFFFFFFFFu / wn.AW;
     return wn;
 }
 
