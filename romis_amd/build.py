@@ -39,12 +39,13 @@ SOURCES = [
     ("bvh.cpp", ["-x", "c++"]),
     ("screen.cpp", ["-x", "c++"]),
 ]
-HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h"]
+HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
+           "route.h"]
 
 
 def source_hash() -> str:
-    """sha256 over the device sources, the launcher (restir.cpp decides which buffers a pass reads and writes) and
-    the flags: identifies the kernels a profile was measured on (bench.py reports a committed PMC traffic figure
+    """sha256 over the device sources, the launcher (restir.cpp and route.h decide which buffers a pass reads and writes)
+    and the flags: identifies the kernels a profile was measured on (bench.py reports a committed PMC traffic figure
     only when it matches)."""
     import hashlib
     h = hashlib.sha256()
@@ -84,9 +85,24 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if os.path.exists(src) and (force or _stale(tool, [src, os.path.join(CSRC, "device_math.h"), __file__])):
         os.makedirs(os.path.dirname(tool), exist_ok=True)
         subprocess.check_call([HIPCC] + COMMON + DEVICE + ["-x", "hip", src, "-o", tool])
+    build_route_check(force)
     if verbose:
         print(LIB)
     return LIB
+
+
+def build_route_check(force: bool = False) -> str:
+    """tools/route_check: the route functions of csrc/route.h as a host program that replays tests/golden/launch_routes.txt
+    (tests/test_launch_routes.py); plain C++ over the headers, no device code."""
+    tool = os.path.join(OUT, "tools", "route_check")
+    srcs = [os.path.join(ROOT, "tests", "cpp", f) for f in ("route_check.cpp", "route_rows.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in ("route.h", "launch_shape.h", "restir_types.h")] + [__file__]
+    if os.path.exists(srcs[0]) and (force or _stale(tool, deps)):
+        os.makedirs(os.path.dirname(tool), exist_ok=True)
+        rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))), "include")
+        subprocess.check_call([HIPCC, "-x", "c++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__",
+                               f"-I{rocm_include}", f"-I{CSRC}", f"-I{os.path.dirname(srcs[0])}", srcs[0], "-o", tool])
+    return tool
 
 
 def build_variant(name: str, defines: list[str], flags: list[str] | None = None) -> str:

@@ -188,11 +188,7 @@ struct Combiner {
 //               the drawn light's corner is (start + s01 x) + s02 y, x = i >> log2(ny), y = i & (ny - 1), evaluated in
 //               float as the reference built it; only its colour is read, from SceneDev::light_col (one float4 per
 //               light instead of kLtGrid's two: C4 / C5's 1,024 / 4,096-light grids).
-constexpr int kLtGeneral = 0, kLtPoint = 1, kLtGrid = 2, kLtPgram = 3, kLtRegular = 4;
-// float4s per light of the table form LT
-__host__ __device__ constexpr uint32_t lt_stride(int lt) {
-    return lt == kLtGeneral ? 7u : lt == kLtPgram ? 4u : lt == kLtRegular ? 1u : 2u;
-}
+// (launch_shape.h: kLtGeneral .. kLtRegular and lt_stride, the float4s per light of a form)
 template <int NT, int LT = kLtGeneral, bool TEMP = false>
 __device__ __forceinline__ void ris_pixel(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key, v3 origin,
                                           const float4* lights, const Bvh& bvh, float4 nt, float4 pm, uint32_t x,
@@ -890,7 +886,6 @@ ROMIS_SPATIAL_KERNEL(0, true, k_spatial_n0_unbiased)
 // spatial_pixel, laid out for a short VALU stream -- 32-bit byte offsets from the plane bases, neighbour clamping by
 // v_med3, one shared double reciprocal of the pixel's depth for the depth tests, a fully unrolled consume sequence
 // behind branches the wave skips when no lane accepted that neighbour.  SoA planes (Region ps = 1), K <= kLeanK.
-constexpr uint32_t kLeanK = 5;
 
 template <class T>
 __device__ __forceinline__ T ld_at(const T* __restrict__ base, uint32_t byte_ofs) {
@@ -925,8 +920,7 @@ struct Comb1 {
 // Light-grid sample handles (round 5; SceneDev::lights_regular, the reference's regularLightGrid with RIS's kLtRegular
 // form): a sample is a point of light i's parallelogram at the fractions (a, b) of its two RIS draws, its colour mixed
 // at a and b -- a function of (i, a, b).  The handle is one float4 plane, (W, bits(M | i << 19), a, b): 16 B per pixel
-// instead of the reservoir's 32, index L the initial (0, 0) sample.
-constexpr uint32_t kHandleMG = 0x0007FFFFu;
+// instead of the reservoir's 32, index L the initial (0, 0) sample (kHandleMG, launch_shape.h).
 // the (position, colour) of grid sample (i, a, b), evaluated as kLtRegular's sample_reg (ris_pixel) does; col_tab = the
 // light colours (light_col or an LDS copy)
 __device__ __forceinline__ void grid_sample(const SceneDev& s, const float4* __restrict__ col_tab, uint32_t i, float a,
@@ -979,15 +973,6 @@ __device__ __forceinline__ bool xcd_tile(const Region& rg, uint32_t T, uint32_t 
     return col < ntx && tile < T;
 }
 
-// Blocks for xcd_tile's order over ntx x nty tiles (rg.xcd_rows, rg.xcd_cols set): every XCD gets as many as the one
-// that owns the most chunks.
-inline uint32_t xcd_grid(const Region& rg, uint32_t ntx, uint32_t nty) {
-    if (rg.xcd_rows == 0u) return ntx * nty;
-    const uint32_t cw = (rg.xcd_cols == 0u || rg.xcd_cols >= ntx) ? ntx : rg.xcd_cols;
-    const uint32_t chunks = ((nty + rg.xcd_rows - 1u) / rg.xcd_rows) * ((ntx + cw - 1u) / cw);
-    return 8u * ((chunks + 7u) / 8u) * rg.xcd_rows * cw;
-}
-
 // MissTiles (restir_types.h): every RIS tile (32 x 8, numbered row-major over the view) meeting the pixel rect
 // [x0, x1] x [y0, y1] (global coordinates inside the view) is a background tile.  Block-uniform; the flags of the
 // rect's tile rows are OR-ed without early exits so their loads issue together.
@@ -1025,16 +1010,13 @@ __device__ __forceinline__ uint32_t tile_flag_at(const MissTiles& mt, const Regi
 // Screen-tile staging for the N = 1 / 2 biased passes: the tile's neighbourhood window, R <= kLdsSpatialR (host check).
 // (Round 4 removed k_spatial1_lds / k_spatial1_ldsr, which staged the reservoirs too -- 70 / 46 KB per block, measured
 // 130 / 106 us against 82 for n_t alone at C2, profiles/r2 -- their source is profiles/r4/pruned/spatial1_lds.diff.)
-constexpr uint32_t kLdsSpatialR = 10;
-constexpr uint32_t kApronMax = (kTileW + 2u * kLdsSpatialR) * (kTileH + 2u * kLdsSpatialR);   // 1456 px
 
 // ---------------------------------------------------------------------------------------------------------
 // The prologue the lean spatial kernels share.  The four windowed bodies (spatial1_ntl_body, spatial1h_body,
 // spatialn_ntl_body, spatial2hg_body) run it in this order: lean_tile, lean_background_exit, lean_window, their own
 // loads and the window's staging, lean_draws, lean_window_ready; then lean_primary_miss and LeanSimilar decide what
 // the combine reads.  spatial1u_body, which stages no window, takes lean_tile, lean_background_exit and lean_draw.
-// TH: tile height in 8-row units (blocks of 256 TH threads, a (32 + 2R) x (8 TH + 2R) window).
-constexpr uint32_t apron_max(uint32_t TH) { return (kTileW + 2u * kLdsSpatialR) * (kTileH * TH + 2u * kLdsSpatialR); }
+// TH: tile height in 8-row units (blocks of 256 TH threads, a (32 + 2R) x (8 TH + 2R) window; apron_max).
 
 // A block's 32 x 8 TH tile (xcd_tile's order over the pass's rect) and the lane's pixel in it: wave w is the 8 x 8
 // pixels (w % 4, w / 4) of the tile.  Global coordinates.
@@ -1416,7 +1398,6 @@ ROMIS_SPATIAL1G_T2_KERNEL(true, k_spatial1g_t2_dbg)
 // spatial1_ntl_body's (render_utils.cpp:102-133, reservoir.cpp:40-66): the same (position, colour, W, M) values, in
 // the same operations.  The host launches it only when every M the passes can produce fits 24 bits and L <= 254.
 struct HandlesIn { const float* w; const uint32_t* m; };
-constexpr uint32_t kHandleM = 0x00FFFFFFu;
 
 // The combine state over handles: Comb1 with the held sample's light index instead of its (position, colour).
 struct Comb1h {
@@ -1433,9 +1414,6 @@ struct Comb1h {
         if (accept_u(u, w, wsum)) { li = l; chosen = w; pd = pd_in; has_pd = true; }
     }
 };
-
-// LDS of a handle block: the n_t window, the two handle windows, then the light table (2 (L + 1) float4)
-__host__ __device__ constexpr uint32_t h_lds_f4(uint32_t TH) { return apron_max(TH) + apron_max(TH) / 2u; }
 
 // The point-light table of a handle block by LDS-DMA (kThreads threads): entries d = 0 .. L positions, L + 1 .. 2L + 1
 // colours (the light_c2 planes); d = L and 2L + 1 are the zero sample's, stored by two threads
@@ -1483,10 +1461,7 @@ __device__ __forceinline__ void h_stage(const SceneDev& s, const Region& rg, con
 // The final-shading output of a fused last pass (k_spatial1hg_t2_final): the RGB rows of the pass's rect (row 0 = its
 // top, k_final's layout) and final.miss (launch_final's sf.miss_shade_zero)
 struct FinalOut { float* rgb; uint32_t miss; };
-// LDS of the fused kernel's ray phase, in float4 behind the staged BVH: s_from and s_to (512 rays), s_vis (512 words),
-// the 256 bin counts, the four wave totals of their scan
-constexpr uint32_t kFinRays = 512u;
-constexpr uint32_t kFinLdsF4 = 2u * kFinRays + kFinRays / 4u + 256u / 4u + 1u;
+// (the LDS of its ray phase: kFinRays, kFinLdsF4, launch_shape.h)
 // (defined with final shading below)
 __device__ __forceinline__ void fin_store_background(const Region& rg, const FeaturesDev& f, const FinalOut& fin, int x, int y);
 __device__ __forceinline__ void fin_shade_block(const SceneDev& s, const Region& rg, const FeaturesDev& f, const FinalOut& fin,
@@ -2012,7 +1987,7 @@ ROMIS_SPATIALN_NTL_KERNEL(true, 2, k_spatial2_ntl_dbg)
 //    where the producer did not write it (a halo pass's border strips read the exchanged ring, whose reservoirs
 //    arrive without their pdfs), and the term is then evaluated;
 //  - the shadow rays (VIS) traverse the block's LDS copy of the BVH.
-// Only SoA planes (Region ps = 1) and K <= kLeanK take this path (launch_spatial checks).
+// Only SoA planes (Region ps = 1) and K <= kLeanK take this path (route_spatial checks).
 template <bool DBG, bool VIS>
 __device__ __forceinline__ void spatial1u_body(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key,
                                                v3 origin, const float4* __restrict__ n_t, const float4* __restrict__ p_mat,
@@ -2633,8 +2608,7 @@ extern "C" __global__ __launch_bounds__(256) void k_read_stream(const float4* __
 #include "launch.h"
 #include "launch_events.h"
 
-#include <mutex>
-#include <set>
+#include <cassert>
 
 namespace romis {
 
@@ -2646,359 +2620,178 @@ void set_launch_events(hipEvent_t start, hipEvent_t stop) {
 bool launch_events_used() { return g_launched; }
 
 namespace {
-static_assert(kTileW * kTileH == kBlock, "one lane per tile pixel");
-
-inline uint32_t items_of(const Region& rg) {
-    return rg.map2d ? ((rg.rw + kTileW - 1) / kTileW) * ((rg.rh + kTileH - 1) / kTileH) : (rg.rw * rg.rh + kBlock - 1) / kBlock;
+// a route names a buffer: the caller must have passed it
+template <class T>
+T* named(bool by_route, T* p) {
+    assert(!by_route || p);
+    return by_route ? p : nullptr;
 }
-inline size_t lights_lds_bytes(const SceneDev& s) { return (size_t)7 * s.num_lights * 16; }
-// The RIS light-table form (ris_pixel's LT) for this scene and N: the compact tables of the _pt / _grid kernels
-// (N = 1, 2) when the scene's lights allow them and ris.compact is on, else the general records.
-inline int ris_light_form(const SceneDev& s, const FeaturesDev& f, const Tuning& tu) {
-    if (!tu.ris_compact || s.num_lights == 0 || (f.N != 1 && f.N != 2)) return kLtGeneral;
-    if (s.light_types == 1u) return kLtPoint;
-    // N = 1 (at N = 2 the form spills): ris.compact = 2 keeps the grid table (A/B runs)
-    if (s.lights_regular && tu.ris_compact == 1u && f.N == 1) return kLtRegular;
-    if (s.lights_grid) return kLtGrid;
-    if (s.lights_pgram) return kLtPgram;
-    return kLtGeneral;
-}
-inline size_t ris_lights_lds_bytes(const SceneDev& s, int lt) { return (size_t)lt_stride(lt) * s.num_lights * 16; }
-inline Region with_map(Region rg, uint32_t map2d) { rg.map2d = map2d; return rg; }
 }  // namespace
 
-hipError_t launch_primary(const SceneDev& s, const Region& rg0, const CameraDev& cam, float4* n_t, float4* p_mat,
-                          float4* n_t2, const Tuning& tu, hipStream_t stream) {
-    if (rg0.rw == 0 || rg0.rh == 0) return hipSuccess;
-    const Region rg = with_map(rg0, 1u);
-    const size_t lds = bvh_lds_bytes(s);
-    const dim3 grid(items_of(rg));
-    if (tu.primary_lds && lds <= kLdsBudget)
-        ROMIS_LAUNCH(k_primary_lds, grid, dim3(kBlock), lds, stream, s, rg, cam, n_t, p_mat, n_t2);
-    else
-        ROMIS_LAUNCH(k_primary, grid, dim3(kBlock), 0, stream, s, rg, cam, n_t, p_mat, n_t2);
+hipError_t launch_primary(const Route& r, const SceneDev& s, const Region& rg0, const LaunchBufs& b, hipStream_t stream) {
+    if (r.kernel == Kernel::kNone) return hipSuccess;
+    assert(r.kernel == Kernel::kPrimary && b.cam);
+    ROMIS_LAUNCH(r.staged ? k_primary_lds : k_primary, dim3(r.grid), dim3(r.block), r.lds, stream, s, r.region(rg0), *b.cam,
+                 b.n_t, b.p_mat, b.n_t2);
     return hipGetLastError();
 }
 
-hipError_t launch_ris(const SceneDev& s, const Region& rg0, const FeaturesDev& f, uint32_t key, const float* o,
-                      const float4* n_t, const float4* p_mat, float4* ra, float4* rb, float2* rdbg, float* rp,
-                      const Tuning& tu, hipStream_t stream) {
-    if (rg0.rw == 0 || rg0.rh == 0) return hipSuccess;
-    const Region rg = with_map(rg0, 0);
-    const dim3 grid(items_of(rg));
-    const int lt = ris_light_form(s, f, tu);
-    const size_t lds = ris_lights_lds_bytes(s, lt);
-    const bool staged = tu.ris_lds && s.num_lights > 0 && lds <= kLdsBudget;
-    auto k = lt == kLtRegular ? (staged ? k_ris_n1_lds_reg : k_ris_n1_reg)
-           : lt == kLtPoint ? (staged ? (f.N == 1 ? k_ris_n1_lds_pt : k_ris_n2_lds_pt) : (f.N == 1 ? k_ris_n1_pt : k_ris_n2_pt))
-           : lt == kLtGrid ? (staged ? (f.N == 1 ? k_ris_n1_lds_grid : k_ris_n2_lds_grid)
-                                     : (f.N == 1 ? k_ris_n1_grid : k_ris_n2_grid))
-           : lt == kLtPgram ? (staged ? (f.N == 1 ? k_ris_n1_lds_pg : k_ris_n2_lds_pg) : (f.N == 1 ? k_ris_n1_pg : k_ris_n2_pg))
-           : staged ? (f.N == 1 ? k_ris_n1_lds : (f.N == 2 ? k_ris_n2_lds : k_ris_n0_lds))
-                    : (f.N == 1 ? k_ris_n1 : (f.N == 2 ? k_ris_n2 : k_ris_n0));
-    const size_t lds_used = lds;
-    ROMIS_LAUNCH(k, grid, dim3(kBlock), staged ? lds_used : 0, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat, ra,
-                       rb, rdbg, f.N == 1 ? rp : nullptr);
+hipError_t launch_ris(const Route& r, const SceneDev& s, const Region& rg0, const FeaturesDev& f, const LaunchBufs& b,
+                      hipStream_t stream) {
+    if (r.kernel == Kernel::kNone) return hipSuccess;
+    assert(r.kernel == Kernel::kRis);
+    const bool staged = r.staged, n1 = r.n == 1;
+    auto k = r.lt == kLtRegular ? (staged ? k_ris_n1_lds_reg : k_ris_n1_reg)
+           : r.lt == kLtPoint ? (staged ? (n1 ? k_ris_n1_lds_pt : k_ris_n2_lds_pt) : (n1 ? k_ris_n1_pt : k_ris_n2_pt))
+           : r.lt == kLtGrid ? (staged ? (n1 ? k_ris_n1_lds_grid : k_ris_n2_lds_grid) : (n1 ? k_ris_n1_grid : k_ris_n2_grid))
+           : r.lt == kLtPgram ? (staged ? (n1 ? k_ris_n1_lds_pg : k_ris_n2_lds_pg) : (n1 ? k_ris_n1_pg : k_ris_n2_pg))
+           : staged ? (n1 ? k_ris_n1_lds : (r.n == 2 ? k_ris_n2_lds : k_ris_n0_lds))
+                    : (n1 ? k_ris_n1 : (r.n == 2 ? k_ris_n2 : k_ris_n0));
+    const float* o = b.origin;
+    ROMIS_LAUNCH(k, dim3(r.grid), dim3(r.block), r.lds, stream, s, r.region(rg0), f, b.key, o[0], o[1], o[2], b.n_t, b.p_mat,
+                 b.oa, b.ob, named(r.dbg, b.dbg), named(r.rp_out, b.rp_out));
     return hipGetLastError();
 }
 
-hipError_t launch_primary_ris(const SceneDev& s, const Region& rg0, const CameraDev& cam, const FeaturesDev& f, uint32_t key,
-                              float4* n_t, float4* p_mat, float4* n_t2, float4* ra, float4* rb, float2* rdbg,
-                              float* rp, const Tuning& tu, hipStream_t stream, uint8_t* tmiss, uint32_t skip_res,
-                              bool* tmiss_written, Handles h) {
-    if (tmiss_written) *tmiss_written = false;
-    if (rg0.rw == 0 || rg0.rh == 0) return hipSuccess;
-    const Region rg = with_map(rg0, 1u);
-    // MissTiles flags: one 32 x 8 tile per block, N <= 2 (the caller allocates one byte per tile and passes them on
-    // only when *tmiss_written)
-    if (!rg.map2d || f.N > 2) tmiss = nullptr;
-    if (tmiss_written) *tmiss_written = tmiss != nullptr;
-    const size_t bvh = bvh_lds_bytes(s);
-    if (bvh > kLdsBudget) return hipErrorInvalidValue;   // caller checks primary_ris_fits()
-    const int lt = ris_light_form(s, f, tu);
-    const size_t lights = ris_lights_lds_bytes(s, lt);
-    const bool use_lights = tu.ris_lds && s.num_lights > 0 && bvh + lights <= kLdsBudget;
-    auto k = lt == kLtRegular ? (use_lights ? k_primary_ris_n1_lds_reg : k_primary_ris_n1_reg)
-           : lt == kLtPoint ? (use_lights ? (f.N == 1 ? k_primary_ris_n1_lds_pt : k_primary_ris_n2_lds_pt)
-                                          : (f.N == 1 ? k_primary_ris_n1_pt : k_primary_ris_n2_pt))
-           : lt == kLtGrid ? (use_lights ? (f.N == 1 ? k_primary_ris_n1_lds_grid : k_primary_ris_n2_lds_grid)
-                                         : (f.N == 1 ? k_primary_ris_n1_grid : k_primary_ris_n2_grid))
-           : lt == kLtPgram ? (use_lights ? (f.N == 1 ? k_primary_ris_n1_lds_pg : k_primary_ris_n2_lds_pg)
-                                          : (f.N == 1 ? k_primary_ris_n1_pg : k_primary_ris_n2_pg))
-           : use_lights ? (f.N == 1 ? k_primary_ris_n1_lds : (f.N == 2 ? k_primary_ris_n2_lds : k_primary_ris_n0_lds))
-                        : (f.N == 1 ? k_primary_ris_n1 : (f.N == 2 ? k_primary_ris_n2 : k_primary_ris_n0));
-    ROMIS_LAUNCH(k, dim3(items_of(rg)), dim3(kBlock), bvh + (use_lights ? lights : 0), stream, s, rg,
-                 cam, f, key, n_t, p_mat, n_t2, ra, rb, rdbg, f.N == 1 ? rp : nullptr,
-                 (tu.ris_late ? 1u : 0u) | (tu.primary_tl ? 2u : 0u), tmiss,
-                 tmiss ? skip_res : 0u, ((lt == kLtPoint || lt == kLtRegular) && f.N == 1) || (lt == kLtPoint && f.N == 2) ? h.w : nullptr,
-                 lt == kLtPoint && f.N == 1 ? h.m : nullptr, h.w && (lt == kLtPoint || lt == kLtRegular) ? h.res_dead : 0u);
-    return hipGetLastError();
-}
-
-bool primary_ris_temporal_fits(const SceneDev& s, const FeaturesDev& f, const Tuning& tu) {
-    const int lt = ris_light_form(s, f, tu);
-    return tu.fuse_temporal && (f.N == 1 || f.N == 2) && lt == kLtPoint && tu.ris_lds && s.num_lights > 0 &&
-           bvh_lds_bytes(s) + ris_lights_lds_bytes(s, lt) <= kLdsBudget;
-}
-
-hipError_t launch_primary_ris_temporal(const SceneDev& s, const Region& rg0, const CameraDev& cam, const FeaturesDev& f,
-                                       uint32_t key, float4* n_t, float4* p_mat, float4* n_t2, float4* ra, float4* rb,
-                                       float2* rdbg, float* rp, const Tuning& tu, hipStream_t stream, TemporalIn tin,
-                                       Handles h) {
-    if (rg0.rw == 0 || rg0.rh == 0) return hipSuccess;
-    if (!primary_ris_temporal_fits(s, f, tu)) return hipErrorInvalidValue;   // the caller checks
-    if (f.N != 1 && f.N != 2 && (h.w || tin.hw)) return hipErrorInvalidValue;   // handles: N = 1 / 2
-    const Region rg = with_map(rg0, 1u);
-    const size_t lds = bvh_lds_bytes(s) + ris_lights_lds_bytes(s, kLtPoint);
-    auto k = f.N == 1 ? k_primary_ris_n1_lds_pt_temporal : k_primary_ris_n2_lds_pt_temporal;
-    ROMIS_LAUNCH(k, dim3(items_of(rg)), dim3(kBlock), lds, stream, s, rg, cam, f, key, n_t, p_mat, n_t2, ra, rb, rdbg,
-                 f.N == 1 ? rp : nullptr, (tu.ris_late ? 1u : 0u) | (tu.primary_tl ? 2u : 0u), tin, h.w, h.m,
-                 h.w ? h.res_dead : 0u);
-    return hipGetLastError();
-}
-
-bool primary_ris_fits(const SceneDev& s) { return bvh_lds_bytes(s) <= kLdsBudget; }
-
-int spatial_handle_kind(const SceneDev& s, const FeaturesDev& f, const Tuning& tu, uint32_t passes, uint64_t m0) {
-    if (!tu.spatial_handles || passes == 0 || (f.N != 1 && f.N != 2) || f.unbiased || f.K > kLeanK || f.R > kLdsSpatialR)
-        return -1;
-    if (!tu.spatial_lean || !tu.ris_compact || s.num_lights == 0) return -1;
-    int hk;
-    uint32_t mmax;
-    if (f.N == 2) {   // point lights: the 16-byte handle records of k_spatial2hg (spatial.n2h)
-        if (!tu.spatial_n2h || s.light_types != 1u || s.num_lights > 254u) return -1;
-        hk = 2; mmax = kHandleM;
-    } else if (s.light_types == 1u && s.num_lights <= 254u) {   // point lights (k_spatial1h); index L = the zero sample
-        hk = 0; mmax = kHandleM;
-    } else if (ris_light_form(s, f, tu) == kLtRegular && tu.spatial_th != 1u && s.num_lights <= 1024u) {
-        // a regular light grid (RIS's kLtRegular form; k_spatial1g_t2, 32 x 16 tiles, <= 16 KB of colours in LDS)
-        hk = 1; mmax = kHandleMG;
-    } else {
-        return -1;
+hipError_t launch_primary_ris(const Route& r, const SceneDev& s, const Region& rg0, const FeaturesDev& f, const LaunchBufs& b,
+                              hipStream_t stream) {
+    if (r.kernel == Kernel::kNone) return hipSuccess;
+    assert(r.ok && b.cam);
+    const Region rg = r.region(rg0);
+    float* const hw = named(r.how, b.hout.w);
+    uint32_t* const hm = named(r.hom, b.hout.m);
+    if (r.kernel == Kernel::kPrimaryRisTemporal) {
+        ROMIS_LAUNCH(r.n == 1 ? k_primary_ris_n1_lds_pt_temporal : k_primary_ris_n2_lds_pt_temporal, dim3(r.grid),
+                     dim3(r.block), r.lds, stream, s, rg, *b.cam, f, b.key, b.n_t, b.p_mat, b.n_t2, b.oa, b.ob,
+                     named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), r.mode, b.tin, hw, hm, r.res_dead);
+        return hipGetLastError();
     }
-    // every M: RIS M (or m0: after temporal reuse), then each biased pass sums at most K + 1 inputs
-    uint64_t m = m0 ? m0 : f.M;
-    if (m > mmax) return -1;
-    for (uint32_t p = 0; p < passes && m <= mmax; p++) m *= (uint64_t)(f.K + 1u);
-    return m <= mmax ? hk : -1;
-}
-bool spatial_handles_ok(const SceneDev& s, const FeaturesDev& f, const Tuning& tu, uint32_t passes) {
-    return spatial_handle_kind(s, f, tu, passes) >= 0;
-}
-
-// launch_spatial's N = 1 pass reads background tiles through MissTiles (k_spatial1_ntl / _t2 biased, k_spatial1u[_vis]
-// unbiased) for these features and knobs, SoA planes -- the condition for RIS's skip_res
-// launch_final's k_final_n1_sorted writes background tiles from the flags without reading them
-bool final_reads_flags(const SceneDev& s, const FeaturesDev& f, const Tuning& tu) {
-    return f.N == 1 && tu.final_sort && tu.final_lds && bvh_lds_bytes(s) <= kLdsBudget;
-}
-
-bool spatial_reads_flags(const SceneDev& s, const FeaturesDev& f, const Tuning& tu) {
-    if (f.N != 1 || f.K > kLeanK || !tu.spatial_lean) return false;
-    if (f.unbiased) return !f.spatial_vis || bvh_lds_bytes(s) <= kLdsBudget;   // k_spatial1u[_vis]
-    return f.R <= kLdsSpatialR;                                               // k_spatial1_ntl / _t2, k_spatial1h
+    assert(r.kernel == Kernel::kPrimaryRis);
+    const bool staged = r.staged, n1 = r.n == 1;
+    auto k = r.lt == kLtRegular ? (staged ? k_primary_ris_n1_lds_reg : k_primary_ris_n1_reg)
+           : r.lt == kLtPoint ? (staged ? (n1 ? k_primary_ris_n1_lds_pt : k_primary_ris_n2_lds_pt)
+                                        : (n1 ? k_primary_ris_n1_pt : k_primary_ris_n2_pt))
+           : r.lt == kLtGrid ? (staged ? (n1 ? k_primary_ris_n1_lds_grid : k_primary_ris_n2_lds_grid)
+                                       : (n1 ? k_primary_ris_n1_grid : k_primary_ris_n2_grid))
+           : r.lt == kLtPgram ? (staged ? (n1 ? k_primary_ris_n1_lds_pg : k_primary_ris_n2_lds_pg)
+                                        : (n1 ? k_primary_ris_n1_pg : k_primary_ris_n2_pg))
+           : staged ? (n1 ? k_primary_ris_n1_lds : (r.n == 2 ? k_primary_ris_n2_lds : k_primary_ris_n0_lds))
+                    : (n1 ? k_primary_ris_n1 : (r.n == 2 ? k_primary_ris_n2 : k_primary_ris_n0));
+    ROMIS_LAUNCH(k, dim3(r.grid), dim3(r.block), r.lds, stream, s, rg, *b.cam, f, b.key, b.n_t, b.p_mat, b.n_t2, b.oa, b.ob,
+                 named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), r.mode, named(r.flags, b.flags), r.skip, hw, hm, r.res_dead);
+    return hipGetLastError();
 }
 
 hipError_t launch_temporal(const SceneDev& s, const Region& rg0, const FeaturesDev& f, uint32_t key, const float* o,
                            const float4* n_t, const float4* p_mat, const float4* ca, const float4* cb,
                            const float4* pa, const float4* pb, float4* oa, float4* ob, float2* odbg,
-                           const float* rp_in, float* rp_out, const Tuning& tu, hipStream_t stream) {
-    (void)tu;
+                           const float* rp_in, float* rp_out, hipStream_t stream) {
     if (rg0.rw == 0 || rg0.rh == 0) return hipSuccess;
-    const Region rg = with_map(rg0, 0);
+    Region rg = rg0;
+    rg.map2d = 0;
     auto k = f.N == 1 ? k_temporal_n1 : (f.N == 2 ? k_temporal_n2 : k_temporal_n0);
-    ROMIS_LAUNCH(k, dim3(items_of(rg)), dim3(kBlock), 0, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat, ca, cb,
-                       pa, pb, oa, ob, odbg, f.N == 1 ? rp_in : nullptr, f.N == 1 ? rp_out : nullptr);
+    ROMIS_LAUNCH(k, dim3((rg.rw * rg.rh + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, s, rg, f, key, o[0], o[1], o[2], n_t,
+                 p_mat, ca, cb, pa, pb, oa, ob, odbg, f.N == 1 ? rp_in : nullptr, f.N == 1 ? rp_out : nullptr);
     return hipGetLastError();
 }
 
-// The automatic XCD chunks (spatial.xcd_rows / spatial.xcd_cols left at auto) of a lean spatial kernel
-enum class XcdChunks {
-    kL2Rows,    // whole tile rows, as many as one XCD's L2 holds
-    kOneRow,    // one tile row (the staged and gathered sample-handle kernels on 32 x 16 tiles)
-    kThirds,    // 32 x 8 tiles: from 24 tiles a row 2-D chunks of 8 rows x a third of the row, else kL2Rows
-    kGrid4x8,   // light-grid handles, 32 x 16 tiles: from 64 tiles a row 2-D chunks of 4 x 8 tiles, else kL2Rows
-};
-// The grid of a lean spatial kernel: one block per 32 x 8 th tile of the rect in xcd_tile's order, rounded to the XCD
-// that owns the most tiles.  Sets rg.xcd_rows / rg.xcd_cols: the knobs where they are explicit (an explicit
-// spatial.xcd_rows counts rows of the kernel's own tiles), else the kernel's rule.
-static uint32_t lean_grid(Region& rg, const Tuning& tu, uint32_t th, XcdChunks rule) {
-    const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW, nty = (rg.rh + th * kTileH - 1) / (th * kTileH);
-    const bool auto_rows = tu.spatial_xcd_rows == kXcdRowsAuto, auto_cols = tu.spatial_xcd_cols == kXcdColsAuto;
-    rg.xcd_rows = tu.spatial_xcd_rows;
-    rg.xcd_cols = auto_cols ? 0u : tu.spatial_xcd_cols;
-    if (auto_rows) {
-        // a chunk's records (n_t, p_mat, res_a, res_b: 64 B/px over 8-px tile rows) within one XCD's 4 MB L2:
-        // 4 tile rows at 1920 px, 2 at 3840 (kbench: 4K 239 -> 225 us with 2, 1080p best with 4; r2bb); half as many
-        // of the twice as tall 32 x 16 tile rows
-        rg.xcd_rows = std::max(1u, std::min(8u, 8192u / std::max(rg.rw, 1u)) / th);
-        // the handle kernels: one 32 x 16 row (k_spatial1h_t2 at C2: 66.1 / 65.7 us against 66.7 / 66.3 with two,
-        // 72.9 / 72.5 with four; profiles/r5/probes/r5p23)
-        if (rule == XcdChunks::kOneRow) rg.xcd_rows = 1u;
+hipError_t launch_spatial(const Route& r, const SceneDev& s, const Region& rg0, const FeaturesDev& f, const LaunchBufs& b,
+                          hipStream_t stream) {
+    if (r.kernel == Kernel::kNone) return hipSuccess;
+    const Region rg = r.region(rg0);
+    const dim3 grid(r.grid), block(r.block);
+    const float* o = b.origin;
+    const bool dbg = r.dbg, t2 = r.th == 2u;
+    const float4* const ia = named(r.res_in, b.ia);
+    const float4* const ib = named(r.res_in, b.ib);
+    float2* const odbg = named(r.dbg, b.dbg);
+    const float* const rp_in = named(r.rp_in, b.rp_in);
+    float* const rp_out = named(r.rp_out, b.rp_out);
+    const MissTiles mt{named(r.flags, b.flags), r.flags_m, r.gbuf};
+    // handles: the w plane also carries the 16-byte records of kinds 1 and 2
+    const HandlesIn hi{named(r.hin >= 0, b.hin.w), named(r.hin_m, b.hin.m)};
+    const float4* const hrec = reinterpret_cast<const float4*>(hi.w);
+    float* const how = named(r.how, b.hout.w);
+    uint32_t* const hom = named(r.hom, b.hout.m);
+    switch (r.kernel) {
+    case Kernel::kSpatial: {
+        auto k = r.unbiased ? (r.n == 1 ? k_spatial_n1_unbiased : (r.n == 2 ? k_spatial_n2_unbiased : k_spatial_n0_unbiased))
+                            : (r.n == 1 ? k_spatial_n1_biased : (r.n == 2 ? k_spatial_n2_biased : k_spatial_n0_biased));
+        ROMIS_LAUNCH(k, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], b.n_t, b.p_mat, ia, ib, b.oa, b.ob, odbg,
+                     r.bvh_lds);
+        break;
     }
-    if (rule == XcdChunks::kThirds && auto_cols && rg.xcd_rows && ntx >= 24u) {
-        // 2-D chunks: 8 tile rows x a third of the tile row (an odd number of chunks per chunk row, so the
-        // round-robin XCDs cover every column).  C2: fetch 83 -> 66 B/px at the same time (profiles/r4/r4g,
-        // r4h): the window rows a chunk's consecutive tile rows share stay in the XCD's L2.
-        if (auto_rows) rg.xcd_rows = 8u;
-        rg.xcd_cols = (ntx + 2u) / 3u;
+    case Kernel::kSpatial1u: {
+        auto k = r.vis_kernel ? (dbg ? k_spatial1u_vis_dbg : k_spatial1u_vis) : (dbg ? k_spatial1u_dbg : k_spatial1u);
+        ROMIS_LAUNCH(k, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], b.n_t, b.p_mat, ia, ib, b.oa, b.ob, odbg,
+                     rp_in, named(r.rp_nb, b.rp_in), rp_out, named(r.vis, b.vis), mt);
+        break;
     }
-    if (rule == XcdChunks::kGrid4x8 && auto_rows && auto_cols && ntx >= 64u) {
-        // wide frames: 2-D chunks of 4 x 8 tiles (128 x 64 px), so the +-R window rows of vertically adjacent tiles
-        // are re-read from one XCD's L2: C4f HBM traffic 1.30 -> 1.01x algorithmic (FETCH 770 -> 541 MB a launch),
-        // spatial 404.5 -> 398.2 us (round 6, profiles/r6/probes/s4)
-        rg.xcd_rows = 4u;
-        rg.xcd_cols = 8u;
+    case Kernel::kSpatial2hg: {
+        auto k = t2 ? (dbg ? k_spatial2hg_t2_dbg : k_spatial2hg_t2) : (dbg ? k_spatial2hg_dbg : k_spatial2hg);
+        ROMIS_LAUNCH(k, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], b.n_t, b.p_mat, hrec, b.oa, b.ob, odbg,
+                     reinterpret_cast<float4*>(how), mt, r.res_dead);
+        break;
     }
-    return rg.xcd_rows ? xcd_grid(rg, ntx, nty) : ntx * nty;
-}
-
-hipError_t launch_spatial(const SceneDev& s, const Region& rg0, const FeaturesDev& f, uint32_t key, const float* o,
-                          const float4* n_t, const float4* p_mat, const float4* ia, const float4* ib, float4* oa,
-                          float4* ob, float2* odbg, const float* rp_in, const float* rp_nb, float* rp_out,
-                          bool* rp_written, const Tuning& tu, hipStream_t stream, uint8_t* vis_out, bool* vis_written,
-                          MissTiles mt, Handles hin, Handles hout, FusedFinal fin) {
-    if (rp_written) *rp_written = false;
-    if (fin.done) *fin.done = false;
-    if (!mt.flags) mt.m = mt.gbuf = 0u;
-    if (vis_written) *vis_written = false;
-    if (rg0.rw == 0 || rg0.rh == 0) return hipSuccess;
-    Region rg = with_map(rg0, 2u);   // 32 x 8 tiles of 8 x 8 waves (the lean kernels' XCD tile order, xcd_tile)
-    const size_t bvh_bytes = bvh_lds_bytes(s);
-    const bool lean = tu.spatial_lean && f.N == 1 && f.K <= kLeanK && rg.ps == 1u && rg.map2d == 2u &&
-                      (size_t)rg.vw * rg.vh * 16u <= 0xFFFFFFFFull;
-    // N = 2 planes: byte offsets of both sub-reservoir planes within 32 bits
-    const bool lean2 = tu.spatial_lean && f.N == 2 && f.K <= kLeanK && rg.ps == 1u && rg.map2d == 2u &&
-                       (size_t)rg.js * 16u + (size_t)rg.vw * rg.vh * 16u <= 0xFFFFFFFFull;
-    if (lean && f.unbiased && (!f.spatial_vis || bvh_bytes <= kLdsBudget)) {
-        // combineUnbiased, N = 1: one block per tile in the XCD order of the biased pass (xcd_tile)
-        const uint32_t grid = lean_grid(rg, tu, 1u, XcdChunks::kL2Rows);
-        auto k = f.spatial_vis ? (odbg ? k_spatial1u_vis_dbg : k_spatial1u_vis) : (odbg ? k_spatial1u_dbg : k_spatial1u);
-        uint8_t* vo = f.spatial_vis ? vis_out : nullptr;   // the own-pixel shadow ray, for final shading (N = 1)
-        ROMIS_LAUNCH(k, dim3(grid), dim3(kBlock), f.spatial_vis ? bvh_bytes : 0, stream, s, rg, f, key, o[0], o[1], o[2],
-                     n_t, p_mat, ia, ib, oa, ob, odbg, rp_in, rp_in ? rp_nb : nullptr, rp_out, vo, mt);
-        if (rp_written) *rp_written = rp_out != nullptr;
-        if (vis_written) *vis_written = vo != nullptr;
-        return hipGetLastError();
+    case Kernel::kSpatial2Ntl:
+        ROMIS_LAUNCH(dbg ? k_spatial2_ntl_dbg : k_spatial2_ntl, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2],
+                     b.n_t, b.p_mat, ia, ib, b.oa, b.ob, odbg, mt);
+        break;
+    case Kernel::kSpatial1g:
+        ROMIS_LAUNCH(dbg ? k_spatial1g_t2_dbg : k_spatial1g_t2, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2],
+                     b.n_t, b.p_mat, b.oa, b.ob, odbg, rp_in, rp_out, mt, hrec, reinterpret_cast<float4*>(how), r.res_dead);
+        break;
+    case Kernel::kSpatial1hgFinal:
+        assert(b.rgb);
+        ROMIS_LAUNCH(k_spatial1hg_t2_final, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], b.n_t, b.p_mat, hi,
+                     b.oa, b.ob, rp_in, how, hom, mt, r.res_dead, FinalOut{b.rgb, r.miss});
+        break;
+    case Kernel::kSpatial1hg:
+        ROMIS_LAUNCH(dbg ? k_spatial1hg_t2_dbg : k_spatial1hg_t2, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2],
+                     b.n_t, b.p_mat, hi, b.oa, b.ob, odbg, rp_in, rp_out, how, hom, mt, r.res_dead);
+        break;
+    case Kernel::kSpatial1h: {
+        auto k = t2 ? (dbg ? k_spatial1h_t2_dbg : k_spatial1h_t2) : (dbg ? k_spatial1h_dbg : k_spatial1h);
+        ROMIS_LAUNCH(k, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], b.n_t, b.p_mat, hi, b.oa, b.ob, odbg,
+                     rp_in, rp_out, how, hom, mt, r.res_dead);
+        break;
     }
-    if (lean2 && !f.unbiased && f.R <= kLdsSpatialR) {
-        // N = 2 biased: one block per tile in the XCD chunk order (xcd_tile); spatial.lds != 3 selects the general
-        // kernel for A/B runs, as for N = 1.  No pdf cache at N = 2 (*rp_written stays false)
-        if (hin.w) {
-            // handle records (k_spatial2hg[_t2], spatial_handle_kind 2): 32 x 8 TH tiles, TH = spatial.th (auto 1)
-            if (s.light_types != 1u) return hipErrorInvalidValue;
-            const uint32_t th = tu.spatial_th == 2u ? 2u : 1u;
-            const uint32_t grid = lean_grid(rg, tu, th, XcdChunks::kL2Rows);
-            const size_t lds = (size_t)apron_max(th) * 16u + (size_t)(2u * s.num_lights + 2u) * 16u;
-            auto k = th == 2u ? (odbg ? k_spatial2hg_t2_dbg : k_spatial2hg_t2) : (odbg ? k_spatial2hg_dbg : k_spatial2hg);
-            ROMIS_LAUNCH(k, dim3(grid), dim3(th * kBlock), lds, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat,
-                         reinterpret_cast<const float4*>(hin.w), oa, ob, odbg, reinterpret_cast<float4*>(hout.w), mt,
-                         hout.res_dead);
-            return hipGetLastError();
-        }
-        const uint32_t grid = lean_grid(rg, tu, 1u, XcdChunks::kL2Rows);
-        ROMIS_LAUNCH(odbg ? k_spatial2_ntl_dbg : k_spatial2_ntl, dim3(grid), dim3(kBlock), kApronMax * 16u, stream, s, rg, f,
-                     key, o[0], o[1], o[2], n_t, p_mat, ia, ib, oa, ob, odbg, mt);
-        return hipGetLastError();
+    case Kernel::kSpatial1Ntl: {
+        auto k = t2 ? (dbg ? k_spatial1_ntl_t2_dbg : k_spatial1_ntl_t2) : (dbg ? k_spatial1_ntl_dbg : k_spatial1_ntl);
+        ROMIS_LAUNCH(k, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], b.n_t, b.p_mat, ia, ib, b.oa, b.ob, odbg,
+                     rp_in, rp_out, mt);
+        break;
     }
-    if (lean && !f.unbiased && f.R <= kLdsSpatialR) {
-        // one block per tile (the lean kernels do not loop over tiles, so spatial.blocks does not apply here)
-        // 32x16 tiles (k_spatial1_ntl_t2) where the auto XCD chunk is at most 2 tile rows (wide images): C4 222 ->
-        // 203 us, C2 76.8 -> 79.0 (cfg_kbench, profiles/r3/r3k); spatial.th = 1 / 2 forces either
-        const uint32_t th = tu.spatial_th ? tu.spatial_th : (8192u / std::max(rg.rw, 1u) <= 2u ? 2u : 1u);
-        if (hin.w && s.light_types != 1u) {
-            // light-grid handles (spatial_handle_kind 1): k_spatial1_ntl_t2's tiles, the colours behind the window
-            if (tu.spatial_th == 1u) return hipErrorInvalidValue;
-            const uint32_t grid = lean_grid(rg, tu, 2u, XcdChunks::kGrid4x8);
-            ROMIS_LAUNCH(odbg ? k_spatial1g_t2_dbg : k_spatial1g_t2, dim3(grid), dim3(2u * kBlock),
-                         apron_max(2) * 16u + s.num_lights * 16u, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat, oa,
-                         ob, odbg, rp_in, rp_out, mt, reinterpret_cast<const float4*>(hin.w),
-                         reinterpret_cast<float4*>(hout.w), hout.res_dead);
-        } else if (hin.w && tu.spatial_gather && tu.spatial_th != 1u) {
-            // sample handles gathered instead of staged (k_spatial1hg_t2, spatial.gather; round 6): 32 x 16 tiles, the
-            // automatic XCD chunk one tile row as for k_spatial1h_t2
-            const uint32_t grid = lean_grid(rg, tu, 2u, XcdChunks::kOneRow);
-            const size_t lds = (size_t)apron_max(2) * 16u + (size_t)(2u * s.num_lights + 2u) * 16u;
-            const HandlesIn hi{hin.w, hin.m};
-            // final shading in the same kernel (FusedFinal, launch.h): launch_final's conditions for k_final_n1_sorted,
-            // and the ray phase's LDS -- the BVH, the rays, the histogram, in the bytes of the window and the light table
-            const size_t lds_fin = bvh_bytes + (size_t)kFinLdsF4 * 16u;
-            if (fin.rgb && fin.done && tu.final_fuse && !odbg && !rp_out && tu.final_sort && tu.final_lds &&
-                bvh_bytes <= kLdsBudget && !(tu.final_qbvh == 1u && s.nodes_q_ok) && std::max(lds, lds_fin) <= kLdsBudget) {
-                ROMIS_LAUNCH(k_spatial1hg_t2_final, dim3(grid), dim3(2u * kBlock), std::max(lds, lds_fin), stream, s, rg, f,
-                             key, o[0], o[1], o[2], n_t, p_mat, hi, oa, ob, rp_in, hout.w, hout.m, mt,
-                             (fin.res_dead || hout.res_dead) ? 1u : 0u, FinalOut{fin.rgb, tu.final_miss ? 1u : 0u});
-                *fin.done = true;
-                return hipGetLastError();   // (*rp_written stays false: the last pass writes no pdf cache)
-            }
-            ROMIS_LAUNCH(odbg ? k_spatial1hg_t2_dbg : k_spatial1hg_t2, dim3(grid), dim3(2u * kBlock), lds, stream, s, rg, f,
-                         key, o[0], o[1], o[2], n_t, p_mat, hi, oa, ob, odbg, rp_in, rp_out, hout.w, hout.m, mt,
-                         hout.res_dead);
-        } else if (hin.w) {
-            // sample handles (k_spatial1h[_t2]): 32 x 8 TH tiles, TH = spatial.th (auto: 2 -- C2 66.9 us against 76.2 for
-            // 32 x 8, 70.6 / 68.4 for 32 x 24 / 32 x 32, kbench, profiles/r5); 32 x 8 tiles take k_spatial1_ntl's chunks
-            const uint32_t hth = tu.spatial_th ? tu.spatial_th : 2u;
-            const uint32_t grid = lean_grid(rg, tu, hth, hth > 1u ? XcdChunks::kOneRow : XcdChunks::kThirds);
-            const size_t lds = (size_t)h_lds_f4(hth) * 16u + (size_t)(2u * s.num_lights + 2u) * 16u;
-            const HandlesIn hi{hin.w, hin.m};
-            auto k = hth == 2u ? (odbg ? k_spatial1h_t2_dbg : k_spatial1h_t2) : (odbg ? k_spatial1h_dbg : k_spatial1h);
-            ROMIS_LAUNCH(k, dim3(grid), dim3(hth * kBlock), lds, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat, hi, oa,
-                         ob, odbg, rp_in, rp_out, hout.w, hout.m, mt, hout.res_dead);
-        } else if (th >= 2u) {
-            const uint32_t grid = lean_grid(rg, tu, 2u, XcdChunks::kL2Rows);   // 32x16 tiles
-            ROMIS_LAUNCH(odbg ? k_spatial1_ntl_t2_dbg : k_spatial1_ntl_t2, dim3(grid), dim3(2u * kBlock),
-                         apron_max(2) * 16u, stream, s, rg, f, key, o[0], o[1], o[2], n_t, p_mat, ia, ib, oa, ob, odbg,
-                         rp_in, rp_out, mt);
-        } else {
-            const uint32_t grid = lean_grid(rg, tu, 1u, XcdChunks::kThirds);
-            ROMIS_LAUNCH(odbg ? k_spatial1_ntl_dbg : k_spatial1_ntl, dim3(grid), dim3(kBlock),
-                         kApronMax * 16u, stream,
-                         s, rg, f, key, o[0], o[1], o[2], n_t, p_mat, ia, ib, oa, ob, odbg, rp_in, rp_out, mt);
-        }
-        if (rp_written) *rp_written = rp_out != nullptr;
-        return hipGetLastError();
+    default:
+        assert(!"a spatial route");
+        return hipErrorInvalidValue;
     }
-    if (hin.w) return hipErrorInvalidValue;   // handles without a handle pass: the producer skipped the reservoirs
-    auto k = f.unbiased ? (f.N == 1 ? k_spatial_n1_unbiased : (f.N == 2 ? k_spatial_n2_unbiased : k_spatial_n0_unbiased))
-                        : (f.N == 1 ? k_spatial_n1_biased : (f.N == 2 ? k_spatial_n2_biased : k_spatial_n0_biased));
-    const uint32_t bvh_lds = (f.unbiased && f.spatial_vis && bvh_bytes <= kLdsBudget) ? 1u : 0u;
-    ROMIS_LAUNCH(k, dim3(items_of(rg)), dim3(kBlock), bvh_lds ? bvh_bytes : 0, stream, s, rg, f, key, o[0], o[1], o[2], n_t,
-                 p_mat, ia, ib, oa, ob, odbg, bvh_lds);
     return hipGetLastError();
 }
 
-hipError_t launch_final(const SceneDev& s, const Region& rg0, const FeaturesDev& f, const float* o, const float4* n_t,
-                        const float4* p_mat, const float4* ra, const float4* rb, float* rgb, const Tuning& tu,
-                        hipStream_t stream, const uint8_t* vis_in, MissTiles mt) {
-    if (rg0.rw == 0 || rg0.rh == 0) return hipSuccess;
-    const Region rg = with_map(rg0, 1u);
-    const size_t lds = bvh_lds_bytes(s);
-    const bool use_lds = tu.final_lds && lds <= kLdsBudget;
-    auto k = use_lds ? (f.N == 1 ? k_final_n1_lds : (f.N == 2 ? k_final_n2_lds : k_final_n0_lds))
-                     : (f.N == 1 ? k_final_n1 : (f.N == 2 ? k_final_n2 : k_final_n0));
-    if (tu.final_sort && use_lds && (f.N == 1 || f.N == 2) && rg.map2d) {   // one tile per block
-        SceneDev sf = s;
-        if (!tu.final_miss) sf.miss_shade_zero = 0u;   // final.miss = 0: no miss shortcut (A/B runs)
-        if ((tu.final_qbvh == 1u || (tu.final_qbvh == 2u && f.N == 2)) && s.nodes_q_ok) {   // 16-byte nodes (occluded_q)
-            const size_t lq = ((size_t)s.num_nodes + (size_t)3 * s.num_tris) * 16;
-            if (f.N == 1)
-                ROMIS_LAUNCH(k_final_n1_sorted_q, dim3(items_of(rg)), dim3(kBlock), lq, stream, sf, rg, f, o[0], o[1], o[2],
-                             n_t, p_mat, ra, rb, rgb, vis_in, rg.map2d ? mt : MissTiles{nullptr, 0u, 0u});
-            else
-                ROMIS_LAUNCH(k_final_n2_sorted_q, dim3(items_of(rg)), dim3(kBlock), lq, stream, sf, rg, f, o[0], o[1], o[2],
-                             n_t, p_mat, ra, rb, rgb, rg.map2d ? mt : MissTiles{nullptr, 0u, 0u});
-            return hipGetLastError();
-        }
-        if (f.N == 1)
-            ROMIS_LAUNCH(k_final_n1_sorted, dim3(items_of(rg)), dim3(kBlock), lds, stream, sf, rg, f, o[0], o[1], o[2], n_t,
-                         p_mat, ra, rb, rgb, vis_in, rg.map2d ? mt : MissTiles{nullptr, 0u, 0u});
-        else
-            ROMIS_LAUNCH(k_final_n2_sorted, dim3(items_of(rg)), dim3(kBlock), lds, stream, sf, rg, f, o[0], o[1], o[2], n_t,
-                         p_mat, ra, rb, rgb, rg.map2d ? mt : MissTiles{nullptr, 0u, 0u});
+hipError_t launch_final(const Route& r, const SceneDev& s, const Region& rg0, const FeaturesDev& f, const LaunchBufs& b,
+                        hipStream_t stream) {
+    if (r.kernel == Kernel::kNone) return hipSuccess;
+    const Region rg = r.region(rg0);
+    const dim3 grid(r.grid), block(r.block);
+    const float* o = b.origin;
+    if (r.kernel == Kernel::kFinal) {
+        auto k = r.staged ? (r.n == 1 ? k_final_n1_lds : (r.n == 2 ? k_final_n2_lds : k_final_n0_lds))
+                          : (r.n == 1 ? k_final_n1 : (r.n == 2 ? k_final_n2 : k_final_n0));
+        ROMIS_LAUNCH(k, grid, block, r.lds, stream, s, rg, f, o[0], o[1], o[2], b.n_t, b.p_mat, b.ia, b.ib, b.rgb);
         return hipGetLastError();
     }
-    ROMIS_LAUNCH(k, dim3(items_of(rg)), dim3(kBlock), use_lds ? lds : 0, stream, s, rg, f,
-                       o[0], o[1], o[2], n_t, p_mat, ra, rb, rgb);
+    assert(r.kernel == Kernel::kFinalSorted || r.kernel == Kernel::kFinalSortedQ);
+    const bool q = r.kernel == Kernel::kFinalSortedQ;
+    SceneDev sf = s;
+    if (!r.miss) sf.miss_shade_zero = 0u;
+    const MissTiles mt{named(r.flags, b.flags), 0u, 0u};
+    if (r.n == 1)
+        ROMIS_LAUNCH(q ? k_final_n1_sorted_q : k_final_n1_sorted, grid, block, r.lds, stream, sf, rg, f, o[0], o[1], o[2], b.n_t,
+                     b.p_mat, b.ia, b.ib, b.rgb, named(r.vis, b.vis), mt);
+    else
+        ROMIS_LAUNCH(q ? k_final_n2_sorted_q : k_final_n2_sorted, grid, block, r.lds, stream, sf, rg, f, o[0], o[1], o[2], b.n_t,
+                     b.p_mat, b.ia, b.ib, b.rgb, mt);
     return hipGetLastError();
 }
 

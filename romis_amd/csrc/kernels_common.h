@@ -3,6 +3,7 @@
 // powf, reservoir state, tile / work mappings.  One translation unit per kernel family, compiled side by side.
 #pragma once
 #include "device_math.h"
+#include "launch_shape.h"
 #include "restir_c.h"
 #include "restir_types.h"
 
@@ -637,9 +638,7 @@ __device__ __forceinline__ size_t neighbour_index(const Region& rg, uint32_t x, 
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Work mapping.  Tiles of 32x8 pixels, one 256-lane block each (a wave = 32x2 pixels).
-constexpr uint32_t kTileW = 32, kTileH = 8;
-
+// Work mapping (launch_shape.h: tiles of kTileW x kTileH pixels).
 __device__ __forceinline__ uint32_t num_tiles(const Region& rg) {
     return ((rg.rw + kTileW - 1) / kTileW) * ((rg.rh + kTileH - 1) / kTileH);
 }

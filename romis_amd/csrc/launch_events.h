@@ -1,10 +1,10 @@
 // launch_events.h -- host side shared by the launchers of kernels.hip and mis.hip: the timed-launch event pair and the
-// launch shape constants.
+// launch shape constants (launch_shape.h).
 #pragma once
 
 #include <hip/hip_ext.h>
 
-#include "restir_types.h"
+#include "launch_shape.h"
 
 namespace romis {
 
@@ -20,9 +20,5 @@ inline thread_local bool g_launched = false;
                               __VA_ARGS__);                                                                   \
         g_launched = true;                                                                                    \
     } while (0)
-
-constexpr uint32_t kBlock = 256;
-constexpr size_t kLdsBudget = 64 * 1024;   // LDS a kernel may stage a BVH / light table into
-inline size_t bvh_lds_bytes(const SceneDev& s) { return ((size_t)2 * s.num_nodes + (size_t)3 * s.num_tris) * 16; }
 
 }  // namespace romis

@@ -886,41 +886,47 @@ struct FrameBufs {
     bool records;
     size_t npx;
     uint32_t N;
-    DevBuf* rec_() const { return c->rec; }
-    DevBuf& n_t_() const { return c->n_t; }
-    DevBuf* rp_() const { return c->rp; }
     float4* pm() const { return c->p_mat.as<float4>(); }
     DevBuf& rgb() const { return c->rgb; }
     DevBuf& uv() const { return c->uv; }
     DevBuf& vis() const { return c->vis; }
-    DevBuf& tmiss() const { return c->tmiss; }
-    DevBuf* hnd_() const { return c->hnd; }
     // the sample-handle planes of rec[i]: W then M | index << 24, one 4-byte plane each (ensure_handles)
     Handles h(int i) const {
-        float* w = hnd_()[i].as<float>();
-        return w ? Handles{w, reinterpret_cast<uint32_t*>(w + npx), 0u} : Handles{nullptr, nullptr, 0u};
+        float* w = c->hnd[i].as<float>();
+        return w ? Handles{w, reinterpret_cast<uint32_t*>(w + npx)} : Handles{nullptr, nullptr};
     }
     // frame handles: the same planes at the tail of rec[i] (planes layout, ensure_records), handed on with the records to
     // the frame restir_render returns -- the next frame's fused temporal reuse reads them: N = 1 the W and M | index
     // planes (8 B / px, not 32), N = 2 the 16-byte handle records (not 64 B)
     Handles fh(int i) const {
-        if (records || (N != 1 && N != 2)) return Handles{nullptr, nullptr, 0u};
-        float* w = reinterpret_cast<float*>(rec_()[i].as<float4>() + 2 * N * npx);
-        return Handles{w, N == 1 ? reinterpret_cast<uint32_t*>(w + npx) : nullptr, 0u};
+        if (records || (N != 1 && N != 2)) return Handles{nullptr, nullptr};
+        float* w = reinterpret_cast<float*>(c->rec[i].as<float4>() + 2 * N * npx);
+        return Handles{w, N == 1 ? reinterpret_cast<uint32_t*>(w + npx) : nullptr};
     }
     const float* fhw(const restir_frame* f) const { return reinterpret_cast<const float*>(f->rec.as<float4>() + 2 * N * npx); }
     const uint32_t* fhm(const restir_frame* f) const {
         return N == 1 ? reinterpret_cast<const uint32_t*>(fhw(f) + npx) : nullptr;
     }
-    float4* nt(int i) const { return records ? rec_()[i].as<float4>() : n_t_().as<float4>(); }
-    float4* ra(int i) const { return rec_()[i].as<float4>() + (records ? 1 : 0); }
-    float4* rb(int i) const { return rec_()[i].as<float4>() + (records ? 2 : npx * N); }
-    float4* nt2() const { return records ? rec_()[1].as<float4>() : nullptr; }
+    float4* nt(int i) const { return records ? c->rec[i].as<float4>() : c->n_t.as<float4>(); }
+    float4* ra(int i) const { return c->rec[i].as<float4>() + (records ? 1 : 0); }
+    float4* rb(int i) const { return c->rec[i].as<float4>() + (records ? 2 : npx * N); }
+    float4* nt2() const { return records ? c->rec[1].as<float4>() : nullptr; }
     // the target-pdf cache planes (N = 1 planes layout only)
-    float* rp(int i) const { return (!records && N == 1) ? rp_()[i].as<float>() : nullptr; }
+    float* rp(int i) const { return (!records && N == 1) ? c->rp[i].as<float>() : nullptr; }
     const float4* pa(const restir_frame* f) const { return f->rec.as<float4>() + (records ? 1 : 0); }
     const float4* pb(const restir_frame* f) const { return f->rec.as<float4>() + (records ? 2 : npx * N); }
     Region region(Region r) const { return records ? with_records(r, N) : r; }
+    // a launch that reads grid `in` (its G-buffer, reservoirs, pdf cache and handles) and writes grid `out`
+    LaunchBufs bufs(const CameraDev& cam, uint32_t key, int in, int out) const {
+        LaunchBufs b;
+        b.key = key; b.cam = &cam; b.origin = cam.origin;
+        b.n_t = nt(in); b.p_mat = pm(); b.n_t2 = nt2();
+        b.ia = ra(in); b.ib = rb(in); b.oa = ra(out); b.ob = rb(out);
+        b.rp_in = rp(in); b.rp_out = rp(out);
+        b.hin = h(in); b.hout = h(out);
+        b.rgb = c->rgb.as<float>();
+        return b;
+    }
 };
 
 restir_status ensure_records(restir_ctx* c, uint32_t vw, uint32_t vh, uint32_t N, FrameBufs& fb) {
@@ -928,19 +934,19 @@ restir_status ensure_records(restir_ctx* c, uint32_t vw, uint32_t vh, uint32_t N
     fb = FrameBufs{c, c->tuning.records != 0, npx, N};
     const hipStream_t st = c->stream;
     ST_TRY(c->p_mat.ensure(npx * 16));
-    if (!fb.records) ST_TRY(fb.n_t_().ensure(npx * 16));
+    if (!fb.records) ST_TRY(c->n_t.ensure(npx * 16));
     // (planes, N = 1: + the frame handles' two 4-byte planes and 16 B of slack; N = 2: + the 16-byte handle records and
     // 16 B; FrameBufs::fh)
     const size_t rec_bytes = npx * (fb.records ? 1u + 2u * N : 2u * N) * 16 +
                              (fb.records ? 0 : N == 1 ? npx * 8 + 16 : N == 2 ? npx * 16 + 16 : 0);
-    DevBuf* rec = fb.rec_();
+    DevBuf* rec = c->rec;
     for (int i = 0; i < 2; i++) {
         // a buffer handed to a frame comes back through the pool (stream-ordered against its past users)
         if (!rec[i].p && c->pool->take(rec_bytes, st, rec[i])) continue;
         ST_TRY(rec[i].ensure(rec_bytes));
     }
     if (!fb.records && N == 1)
-        for (int i = 0; i < 2; i++) ST_TRY(fb.rp_()[i].ensure(npx * 4));
+        for (int i = 0; i < 2; i++) ST_TRY(c->rp[i].ensure(npx * 4));
     c->vw = vw; c->vh = vh; c->N = N;
     return RESTIR_OK;
 }
@@ -1438,15 +1444,20 @@ static restir_status render_mis(restir_ctx* c, const restir_camera* cam, const r
     ST_TRY(scene_for(c, f, (size_t)W * H, s));
     float4* nt = c->n_t.as<float4>();
     float4* pm = c->p_mat.as<float4>();
-    TIMED(c, RESTIR_K_PRIMARY, launch_primary(s, view, camd, nt, pm, nullptr, c->tuning, c->stream));
+    LaunchBufs b;
+    b.cam = &camd; b.origin = camd.origin; b.n_t = nt; b.p_mat = pm;
+    b.oa = c->ra[0].as<float4>(); b.ob = c->rb[0].as<float4>(); b.dbg = c->dbg[0].as<float2>();
+    TIMED(c, RESTIR_K_PRIMARY, launch_primary(route_primary(s, view, c->tuning), s, view, b, c->stream));
+    Ask ris_ask;
+    ris_ask.dbg = true;
+    const Route ris = route_ris(s, view, f, c->tuning, ris_ask);
     TIMED(c, RESTIR_K_MIS, launch_mis_neighbours(s, W, H, f, restir_rng_key(c->seed, frame, RESTIR_STAGE_NEIGHBOURS, 0),
                                                  restir_rng_key(c->seed, frame, RESTIR_STAGE_NEIGHBOURS, 1), nt, pm,
                                                  c->mis_nbr.as<uint32_t>(), c->stream));
     HIP_TRY(hipMemsetAsync(c->mis_acc.p, 0, (size_t)c->mis_rows * W * H * 4, c->stream));
     for (uint32_t it = 0; it < features->max_iterations_mis; it++) {
-        TIMED(c, RESTIR_K_RIS, launch_ris(s, view, f, restir_rng_key(c->seed, frame, RESTIR_STAGE_RIS, it), camd.origin, nt, pm,
-                                          c->ra[0].as<float4>(), c->rb[0].as<float4>(), c->dbg[0].as<float2>(), nullptr,
-                                          c->tuning, c->stream));
+        b.key = restir_rng_key(c->seed, frame, RESTIR_STAGE_RIS, it);
+        TIMED(c, RESTIR_K_RIS, launch_ris(ris, s, view, f, b, c->stream));
         TIMED(c, RESTIR_K_MIS, launch_mis_accumulate(s, W, H, f, camd.origin, nt, pm, c->mis_nbr.as<uint32_t>(),
                                                      c->ra[0].as<float4>(), c->rb[0].as<float4>(), c->dbg[0].as<float2>(), it,
                                                      c->mis_acc.as<float>(), c->mis_smp.as<float>(), c->mis_smp_samples,
@@ -1459,6 +1470,27 @@ static restir_status render_mis(restir_ctx* c, const restir_camera* cam, const r
         HIP_TRY(hipMemcpyAsync(out_rgb, c->rgb.p, (size_t)W * H * 12, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
+    return RESTIR_OK;
+}
+
+// What both frame paths ask of primary rays + RIS over the view: the pdf cache where the layout has one, and
+// background-tile flags (MissTiles; knob miss.tiles) -- not with temporal reuse (its output is not the RIS result); the
+// spatial shortcuts also need bounded normals (their miss tests)
+static Ask frame_ris_ask(const restir_ctx* c, const SceneDev& s, const FrameBufs& fb, bool temporal) {
+    Ask a;
+    a.rp_out = fb.rp(0) != nullptr;
+    a.flags = c->tuning.miss_tiles && !temporal && s.normals_bounded && !fb.records;
+    return a;
+}
+
+// The flags the fused primary + RIS kernel writes when its route says so: one byte per 32 x 8 tile of the view, in
+// whole words (the spatial pass reads its flag's word)
+static restir_status ensure_tile_flags(restir_ctx* c, const Route& ris, const Region& view, uint8_t*& flags) {
+    flags = nullptr;
+    if (!ris.flags) return RESTIR_OK;
+    const size_t tiles = (size_t)((view.vw + 31u) / 32u) * ((view.vh + 7u) / 8u);
+    ST_TRY(c->tmiss.ensure((tiles + 3u) & ~(size_t)3u));
+    flags = c->tmiss.as<uint8_t>();
     return RESTIR_OK;
 }
 
@@ -1477,7 +1509,7 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
         if (tile && (tile->global_width != width || tile->global_height != height || tile->x0 || tile->y0 ||
                      tile->width != width || tile->height != height))
             return fail(RESTIR_ERR_UNSUPPORTED, "R-MIS / R-OMIS render whole images only (no screen tiles)");
-            return render_mis(c, cam, features, width, height, out_rgb);
+        return render_mis(c, cam, features, width, height, out_rgb);
     }
 
     restir_tile t{};
@@ -1500,14 +1532,12 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
     const uint32_t passes = features->spatial_reuse ? features->spatial_resampling_passes : 0u;
     // the computed region must hold the ghost zone the spatial passes read (clipped at the image border)
     {
-        restir_tile need{};
         const uint64_t g = (uint64_t)passes * f.R;
         uint32_t gx0 = t.x0 > g ? (uint32_t)(t.x0 - g) : 0u, gy0 = t.y0 > g ? (uint32_t)(t.y0 - g) : 0u;
         uint64_t gx1 = std::min<uint64_t>((uint64_t)t.x0 + t.width + g, width);
         uint64_t gy1 = std::min<uint64_t>((uint64_t)t.y0 + t.height + g, height);
         if (t.gx0 > gx0 || t.gy0 > gy0 || (uint64_t)t.gx0 + t.gwidth < gx1 || (uint64_t)t.gy0 + t.gheight < gy1)
             return fail(RESTIR_ERR_INVALID, "tile ghost zone narrower than passes * radius = %llu", (unsigned long long)g);
-        (void)need;
     }
     const bool temporal = features->temporal_reuse && prev != nullptr;
     if (temporal) {
@@ -1538,82 +1568,106 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
     float4* pm = fb.pm();
     int cur = 0;
 
-    const uint32_t ris_key = restir_rng_key(c->seed, frame, RESTIR_STAGE_RIS, 0);
-    // background tiles (MissTiles): N <= 2, no temporal reuse (its output is not the RIS result), the fused kernel with
-    // one 32 x 8 tile per block; the spatial shortcuts also need bounded normals (their miss tests)
-    uint8_t* tmiss = nullptr;
-    const bool fused = c->tuning.fuse_primary_ris && primary_ris_fits(s);
-    if (c->tuning.miss_tiles && fused && N <= 2 && !temporal &&
-        s.normals_bounded && !fb.records) {
-        const size_t tiles = (size_t)((t.gwidth + 31u) / 32u) * ((t.gheight + 7u) / 8u);
-        ST_TRY(fb.tmiss().ensure((tiles + 3u) & ~(size_t)3u));   // whole words: the spatial pass reads its flag's word
-        tmiss = fb.tmiss().as<uint8_t>();
-    }
-    // the first spatial pass substitutes a background tile's known reservoirs (k_spatial1_ntl / _t2, k_spatial1u); the
-    // later passes and final shading read the passes' outputs, and with no ghost ring the last pass overwrites the
-    // whole returned grid: RIS need not store those reservoirs
-    const bool skip_res = tmiss && passes > 0 && t.gwidth == t.width && t.gheight == t.height &&
-                          spatial_reads_flags(s, f, c->tuning) &&
-                          (size_t)t.gwidth * t.gheight * 16u <= 0xFFFFFFFFull;
-    // a single unbiased pass (k_spatial1u) also substitutes a background pixel's G-buffer records (own and the Z loop's
-    // neighbours); final shading reads none of them (its tiles are the RIS tiles here): nor are those stored
-    // Biased passes (every pass reads the flags) fix their window up instead (MissTiles::gbuf); knob miss.gbuf.
-    const uint32_t mg = c->tuning.miss_gbuf;
-    const bool gbuf_ok = mg && final_reads_flags(s, f, c->tuning) &&
-                         (f.unbiased ? passes == 1u : (mg == 1u || t.gwidth >= 2048u));
-    uint32_t skip_mode = skip_res ? (1u | (gbuf_ok ? 2u : 0u)) : 0u;
+    Ask ris_ask = frame_ris_ask(c, s, fb, temporal);
+    Route ris = route_primary_ris(s, view, f, c->tuning, ris_ask);
+    const bool fused = c->tuning.fuse_primary_ris && ris.ok;   // same region: one kernel (kernels.hip k_primary_ris)
+    // temporal reuse inside the fused kernel (k_primary_ris_n{1,2}_lds_pt_temporal): the predecessor's reservoirs are
+    // combined while the RIS reservoirs are still in registers (no store / reload, no G-buffer re-read, one launch less)
+    const bool temporal_fused = temporal && fused && route_primary_ris_temporal(s, view, f, c->tuning, ris_ask).ok;
     // sample handles (k_spatial1h): N = 1 biased passes over a point-light scene, written by the fused RIS kernel and by
     // every pass but the last; 4 + 4 B per pixel and 16 B of slack (the planes are read a word at a time)
     // (point lights: two 4-byte planes; a regular light grid: one float4 plane, k_spatial1g)
     // With temporal reuse the passes read handles when the fused temporal kernel can rebuild the predecessor from its
     // frame handles (point lights, the same scene upload): every M then bounded by RIS's plus the clamp's
     const bool no_ghost = t.gwidth == t.width && t.gheight == t.height;
-    const bool temporal_handles = temporal && fused && !fb.records && (N == 1 || N == 2) && no_ghost && prev->hgen != 0 &&
-                                  prev->hgen == c->scene_gen && primary_ris_temporal_fits(s, f, c->tuning);
+    const bool temporal_handles = temporal_fused && no_ghost && prev->hgen != 0 && prev->hgen == c->scene_gen;
     // the M every sub-reservoir can hold entering the passes after temporal reuse: the current M plus each of the N
     // predecessor sub-reservoirs clamped to clampM M + 1 (kernels.hip ris_pixel TEMP)
     const uint64_t m_temporal = (uint64_t)f.M + (uint64_t)N * ((uint64_t)f.clamp_m * f.M + 1u);
-    const uint64_t m_in = temporal ? m_temporal : 0u;
-    const int hkind = (temporal && !temporal_handles) ? -1 : spatial_handle_kind(s, f, c->tuning, passes, m_in);
-    const bool handles = fused && !fb.records && hkind >= 0 && (!temporal || hkind == 0 || hkind == 2) &&
-                         (size_t)t.gwidth * t.gheight * 16u <= 0xFFFFFFFFull;
+    const int hkind = (!fused || (temporal && !temporal_handles))
+                          ? -1
+                          : spatial_handle_kind(s, view, f, c->tuning, passes, temporal ? m_temporal : 0u);
+    const bool handles = hkind >= 0 && (!temporal || hkind == 0 || hkind == 2);
     // the last pass also writes the returned grid's handles (point lights, no ghost ring) for the next frame, bounded as
     // if that frame's temporal reuse had run (its M bound)
     const bool frame_handles = handles && (hkind == 0 || hkind == 2) && out_next && no_ghost &&
-                               spatial_handle_kind(s, f, c->tuning, passes, m_temporal) == hkind;
+                               spatial_handle_kind(s, view, f, c->tuning, passes, m_temporal) == hkind;
     if (handles)
-        for (int i = 0; i < 2; i++) ST_TRY(fb.hnd_()[i].ensure((size_t)t.gwidth * t.gheight * (hkind ? 16u : 8u) + 16u));
+        for (int i = 0; i < 2; i++) ST_TRY(c->hnd[i].ensure((size_t)t.gwidth * t.gheight * (hkind ? 16u : 8u) + 16u));
+    // the last pass's own-pixel shadow rays (unbiased + visibility reuse, N = 1) go on to final shading
+    uint8_t* vis = nullptr;
+    if (passes && features->unbiased_combination && features->spatial_reuse_visibility_check && N == 1) {
+        ST_TRY(fb.vis().ensure((size_t)t.gwidth * t.gheight));
+        vis = fb.vis().as<uint8_t>();
+    }
+    uint8_t* tmiss = nullptr;
+    if (fused && !temporal_fused) ST_TRY(ensure_tile_flags(c, ris, view, tmiss));
+    uint32_t skip_mode = 0u;
+    auto pass_ask = [&](uint32_t pass, bool rp_ok) {
+        const bool last = pass + 1 == passes;
+        Ask a;
+        a.hin = handles ? hkind : -1;
+        // a pass before the last is read by the next one's handles alone: no reservoir planes
+        a.hout = handles ? (!last || frame_handles) : false;
+        a.hout_dead = handles && !last;
+        // every neighbour of this pass lies in the region the cache's producer covered (RIS / temporal: the whole view;
+        // pass p - 1: the owned rect grown by (P - p) R)
+        a.rp_in = a.rp_nb = rp_ok;
+        // the last pass's pdf cache has no reader (final shading re-shades; the next frame's temporal pass evaluates its
+        // own): not written
+        a.rp_out = !last && fb.rp(0) != nullptr;
+        a.vis = last && vis;
+        a.flags = tmiss != nullptr;
+        // a background pixel holds M = f.M after RIS and after every biased pass; an unbiased pass sums its neighbours'
+        // M, which only pass 0 knows
+        a.flags_m = (!f.unbiased || pass == 0) ? f.M : 0u;
+        a.gbuf = (skip_mode & 2u) ? 1u : 0u;
+        // final shading inside the last pass (final.fuse), offered where launch_final would read the pass's grid
+        // without an own-pixel ray plane; the last pass's rect is the owned rect (grow_rect(owned, 0)), also on
+        // ghost-zoned tiles.  Without a returned grid nothing else reads that pass's reservoir planes (the stage and
+        // halo paths keep their own buffers and the separate kernels): they are not stored
+        a.fin = last && !vis;
+        a.fin_dead = out_next == nullptr;
+        return a;
+    };
+    auto pass_rect = [&](uint32_t pass) { return grow_rect(owned, (passes - 1u - pass) * f.R); };
+    if (tmiss && passes > 0 && no_ghost) {
+        // the first spatial pass substitutes a background tile's known reservoirs (Route::bg_known); the later passes and
+        // final shading read the passes' outputs, and with no ghost ring the last pass overwrites the whole returned
+        // grid: RIS need not store those reservoirs
+        const bool skip_res = route_spatial(s, pass_rect(0), f, c->tuning, pass_ask(0, ris.rp_out)).bg_known;
+        // a single unbiased pass (k_spatial1u) also substitutes a background pixel's G-buffer records (own and the Z
+        // loop's neighbours); final shading writes background tiles from the flags without reading them (its tiles are
+        // the RIS tiles here): nor are those stored.  Biased passes (every pass reads the flags) fix their window up
+        // instead (MissTiles::gbuf); knob miss.gbuf.
+        const uint32_t mg = c->tuning.miss_gbuf;
+        Ask with_flags;
+        with_flags.flags = true;
+        const bool gbuf_ok = mg && route_final(s, owned, f, c->tuning, with_flags).flags &&
+                             (f.unbiased ? passes == 1u : (mg == 1u || t.gwidth >= 2048u));
+        skip_mode = skip_res ? (1u | (gbuf_ok ? 2u : 0u)) : 0u;
+    }
     // the handle passes read RIS's samples through the handles alone, and a pass's output is read by the next pass's
     // handles alone: their reservoir planes are dead (the last pass writes the returned grid's owned rect; a tile's
     // ghost ring holds intermediate values, include/restir_c.h)
-    Handles ris_handles = fb.h(cur);
-    ris_handles.res_dead = 1u;
-    // temporal reuse inside the fused kernel (k_primary_ris_n{1,2}_lds_pt_temporal): the predecessor's reservoirs are
-    // combined while the RIS reservoirs are still in registers (no store / reload, no G-buffer re-read, one launch less)
-    const bool temporal_fused = temporal && fused && primary_ris_temporal_fits(s, f, c->tuning);
+    ris_ask.hout = ris_ask.hout_dead = handles;
+    ris_ask.skip = skip_mode;
+    LaunchBufs b = fb.bufs(camd, restir_rng_key(c->seed, frame, RESTIR_STAGE_RIS, 0), 0, cur);
+    b.flags = tmiss;
     if (temporal_fused) {
+        ris = route_primary_ris_temporal(s, view, f, c->tuning, ris_ask);
         ST_TRY(use_prev(prev, c->device, st, c->pool.get()));   // the predecessor's records are complete (its producer's stream)
-        TIMED(c, RESTIR_K_PRIMARY_RIS,
-              launch_primary_ris_temporal(s, view, camd, f, ris_key, fb.nt(0), pm, fb.nt2(), fb.ra(cur), fb.rb(cur), nullptr,
-                                          fb.rp(cur), c->tuning, st,
-                                          TemporalIn{fb.pa(prev), fb.pb(prev),
-                                                     restir_rng_key(c->seed, frame, RESTIR_STAGE_TEMPORAL, 0),
-                                                     handles ? fb.fhw(prev) : nullptr, handles ? fb.fhm(prev) : nullptr},
-                                          handles ? ris_handles : Handles{nullptr, nullptr, 0u}));
+        b.tin = TemporalIn{fb.pa(prev), fb.pb(prev), restir_rng_key(c->seed, frame, RESTIR_STAGE_TEMPORAL, 0),
+                           handles ? fb.fhw(prev) : nullptr, handles ? fb.fhm(prev) : nullptr};
+        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ris, s, view, f, b, st));
         used_prev(prev, st, c->pool.get());
-    } else if (fused) {   // same region: one kernel (kernels.hip k_primary_ris)
-        bool written = false;
-        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(s, view, camd, f, ris_key, fb.nt(0), pm, fb.nt2(), fb.ra(cur),
-                                                          fb.rb(cur), nullptr, fb.rp(cur), c->tuning, st, tmiss, skip_mode,
-                                                          &written, handles ? ris_handles : Handles{nullptr, nullptr, 0u}));
-        if (!written) {   // (then RIS skipped nothing either: its skips need the flags)
-            tmiss = nullptr;
-            skip_mode = 0u;
-        }
+    } else if (fused) {
+        ris = route_primary_ris(s, view, f, c->tuning, ris_ask);
+        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ris, s, view, f, b, st));
     } else {
-        TIMED(c, RESTIR_K_PRIMARY, launch_primary(s, view, camd, fb.nt(0), pm, fb.nt2(), c->tuning, st));
-        TIMED(c, RESTIR_K_RIS, launch_ris(s, view, f, ris_key, camd.origin, fb.nt(cur), pm, fb.ra(cur), fb.rb(cur), nullptr,
-                                          fb.rp(cur), c->tuning, st));
+        ris = route_ris(s, view, f, c->tuning, ris_ask);
+        TIMED(c, RESTIR_K_PRIMARY, launch_primary(route_primary(s, view, c->tuning), s, view, b, st));
+        TIMED(c, RESTIR_K_RIS, launch_ris(ris, s, view, f, b, st));
     }
     c->last_px = (uint64_t)t.gwidth * t.gheight;   // restir_background_pixels
     c->tmiss_w = tmiss ? t.gwidth : 0u;
@@ -1623,59 +1677,38 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
         TIMED(c, RESTIR_K_TEMPORAL,
               launch_temporal(s, view, f, restir_rng_key(c->seed, frame, RESTIR_STAGE_TEMPORAL, 0), camd.origin, fb.nt(cur), pm,
                               fb.ra(cur), fb.rb(cur), fb.pa(prev), fb.pb(prev), fb.ra(cur), fb.rb(cur), nullptr,
-                              fb.rp(cur), fb.rp(cur), c->tuning, st));
+                              fb.rp(cur), fb.rp(cur), st));
         used_prev(prev, st, c->pool.get());
     }
-    bool rp_ok = fb.rp(cur) != nullptr;   // the current grid's target-pdf cache holds its samples' pdfs
-    // the last pass's own-pixel shadow rays (unbiased + visibility reuse, N = 1) go on to final shading
-    uint8_t* vis = nullptr;
-    bool vis_ok = false;
-    if (passes && features->unbiased_combination && features->spatial_reuse_visibility_check && N == 1) {
-        ST_TRY(fb.vis().ensure((size_t)t.gwidth * t.gheight));
-        vis = fb.vis().as<uint8_t>();
-    }
-    // final shading inside the last pass (final.fuse; launch.h FusedFinal), offered where launch_final would read the
-    // pass's grid without an own-pixel ray plane; the last pass's rect is the owned rect (grow_rect(owned, 0)), also on
-    // ghost-zoned tiles.  Without a returned grid nothing else reads that pass's reservoir planes (the stage and halo
-    // paths keep their own buffers and the separate kernels): they are not stored
-    bool final_done = false;
+    // for each pass: route, launch.  rp_ok: the current grid's target-pdf cache holds its samples' pdfs
+    Route last = ris;
     for (uint32_t pass = 0; pass < passes; pass++) {
-        const Region pr = grow_rect(owned, (passes - 1u - pass) * f.R);
+        const Region pr = pass_rect(pass);
         const int nxt = cur ^ 1;
-        const bool offer = pass + 1 == passes && c->tuning.final_fuse && N == 1 && !vis;
-        TIMED(c, RESTIR_K_SPATIAL,
-              launch_spatial(s, pr, f, restir_rng_key(c->seed, frame, RESTIR_STAGE_SPATIAL, pass), camd.origin, fb.nt(cur), pm,
-                             fb.ra(cur), fb.rb(cur), fb.ra(nxt), fb.rb(nxt), nullptr, rp_ok ? fb.rp(cur) : nullptr,
-                             // every neighbour of this pass lies in the region the cache's producer covered (RIS /
-                             // temporal: the whole view; pass p - 1: the owned rect grown by (P - p) R)
-                             rp_ok ? fb.rp(cur) : nullptr,
-                             // the last pass's pdf cache has no reader (final shading re-shades; the next frame's
-                             // temporal pass evaluates its own): not written
-                             pass + 1 < passes ? fb.rp(nxt) : nullptr, &rp_ok, c->tuning, st,
-                             pass + 1 == passes ? vis : nullptr, &vis_ok,
-                             // a background pixel holds M = f.M after RIS and after every biased pass; an unbiased pass
-                             // sums its neighbours' M, which only pass 0 knows
-                             MissTiles{tmiss, (!f.unbiased || pass == 0) ? f.M : 0u, (skip_mode & 2u) ? 1u : 0u},
-                             handles ? fb.h(cur) : Handles{nullptr, nullptr, 0u},
-                             // a pass before the last is read by the next one's handles alone: no reservoir planes
-                             handles && pass + 1 < passes ? Handles{fb.h(nxt).w, fb.h(nxt).m, 1u}
-                             : frame_handles              ? fb.fh(nxt)
-                                                          : Handles{nullptr, nullptr, 0u},
-                             offer ? FusedFinal{fb.rgb().as<float>(), out_next == nullptr, &final_done}
-                                   : FusedFinal{nullptr, false, nullptr}));
+        last = route_spatial(s, pr, f, c->tuning, pass_ask(pass, last.rp_out));
+        b = fb.bufs(camd, restir_rng_key(c->seed, frame, RESTIR_STAGE_SPATIAL, pass), cur, nxt);
+        b.vis = vis;
+        b.flags = tmiss;
+        if (pass + 1 == passes) b.hout = fb.fh(nxt);   // (frame_handles; the route names them)
+        TIMED(c, RESTIR_K_SPATIAL, launch_spatial(last, s, pr, f, b, st));
         cur = nxt;
     }
-    if (!final_done)
-        TIMED(c, RESTIR_K_FINAL, launch_final(s, owned, f, camd.origin, fb.nt(cur), pm, fb.ra(cur), fb.rb(cur),
-                                              fb.rgb().as<float>(), c->tuning, st, vis_ok ? vis : nullptr,
-                                              MissTiles{tmiss, 0u, 0u}));
+    if (!last.final_done) {
+        Ask fin_ask;
+        fin_ask.vis = last.vis;
+        fin_ask.flags = tmiss != nullptr;
+        b = fb.bufs(camd, 0u, cur, cur);
+        b.vis = vis;
+        b.flags = tmiss;
+        TIMED(c, RESTIR_K_FINAL, launch_final(route_final(s, owned, f, c->tuning, fin_ask), s, owned, f, b, st));
+    }
     c->cur = cur;
 
     if (out_next) {
         restir_frame* fr = make_frame(c->pool, c->device, st);   // after the final kernel, the records' last reader
         fr->W = width; fr->H = height; fr->vx0 = t.gx0; fr->vy0 = t.gy0; fr->vw = t.gwidth; fr->vh = t.gheight; fr->N = N;
         // hand the final grid's records to the frame (no copy); the context re-allocates lazily
-        std::swap(fr->rec, fb.rec_()[cur]);
+        std::swap(fr->rec, c->rec[cur]);
         fr->records = fb.records;
         fr->hgen = frame_handles ? c->scene_gen : 0u;
         *out_next = fr;
@@ -1845,6 +1878,19 @@ restir_status restir_stage_download(restir_ctx* c, restir_buffer which, void* ho
     if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_set_scene first");      \
     HIP_TRY(hipSetDevice(c->device));                                               \
 
+// The stage API's buffers: a stage reads the current grid and writes it in place (RIS) or, `advance`, its partner
+static LaunchBufs stage_bufs(restir_ctx* c, const CameraDev& cam, uint32_t key, bool advance) {
+    const int cur = c->cur, out = advance ? cur ^ 1 : cur;
+    LaunchBufs b;
+    b.key = key; b.cam = &cam; b.origin = cam.origin;
+    b.n_t = c->n_t.as<float4>(); b.p_mat = c->p_mat.as<float4>();
+    b.ia = c->ra[cur].as<float4>(); b.ib = c->rb[cur].as<float4>();
+    b.oa = c->ra[out].as<float4>(); b.ob = c->rb[out].as<float4>();
+    b.dbg = c->dbg[out].as<float2>();
+    b.rgb = c->rgb.as<float>();
+    return b;
+}
+
 restir_status restir_stage_primary(restir_ctx* c, const restir_camera* cam) {
     if (!cam) return fail(RESTIR_ERR_INVALID, "camera is NULL");
     STAGE_PRELUDE();
@@ -1853,8 +1899,8 @@ restir_status restir_stage_primary(restir_ctx* c, const restir_camera* cam) {
     d.texture = 1u;
     SceneDev sd;
     ST_TRY(scene_for(c, d, (size_t)c->vw * c->vh, sd));
-    TIMED(c, RESTIR_K_PRIMARY, launch_primary(sd, c->stage_rg, camd, c->n_t.as<float4>(), c->p_mat.as<float4>(), nullptr,
-                                              c->tuning, c->stream));
+    TIMED(c, RESTIR_K_PRIMARY, launch_primary(route_primary(sd, c->stage_rg, c->tuning), sd, c->stage_rg,
+                                              stage_bufs(c, camd, 0u, false), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RESTIR_OK;
 }
@@ -1875,10 +1921,10 @@ restir_status restir_stage_ris(restir_ctx* c, const restir_camera* cam, const re
     SceneDev sd;
     ST_TRY(scene_for(c, d, (size_t)c->vw * c->vh, sd));
     const CameraDev camd = camera_dev(cam);
-    const int cur = c->cur;
-    TIMED(c, RESTIR_K_RIS, launch_ris(sd, c->stage_rg, d, key, camd.origin, c->n_t.as<float4>(), c->p_mat.as<float4>(),
-                                      c->ra[cur].as<float4>(), c->rb[cur].as<float4>(),
-                                      debug ? c->dbg[cur].as<float2>() : nullptr, nullptr, c->tuning, c->stream));
+    Ask ask;
+    ask.dbg = debug != 0;
+    TIMED(c, RESTIR_K_RIS, launch_ris(route_ris(sd, c->stage_rg, d, c->tuning, ask), sd, c->stage_rg, d,
+                                      stage_bufs(c, camd, key, false), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RESTIR_OK;
 }
@@ -1897,7 +1943,7 @@ restir_status restir_stage_temporal(restir_ctx* c, const restir_camera* cam, con
           launch_temporal(sd, c->stage_rg, d, key, camd.origin, c->n_t.as<float4>(), c->p_mat.as<float4>(),
                           c->ra[cur].as<float4>(), c->rb[cur].as<float4>(), c->ra[prv].as<float4>(), c->rb[prv].as<float4>(),
                           c->ra[cur].as<float4>(), c->rb[cur].as<float4>(), debug ? c->dbg[cur].as<float2>() : nullptr,
-                          nullptr, nullptr, c->tuning, c->stream));
+                          nullptr, nullptr, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RESTIR_OK;
 }
@@ -1912,11 +1958,10 @@ restir_status restir_stage_spatial(restir_ctx* c, const restir_camera* cam, cons
     ST_TRY(scene_for(c, d, (size_t)c->vw * c->vh, sd));
     const CameraDev camd = camera_dev(cam);
     const int cur = c->cur, nxt = cur ^ 1;
-    TIMED(c, RESTIR_K_SPATIAL,
-          launch_spatial(sd, c->stage_rg, d, key, camd.origin, c->n_t.as<float4>(), c->p_mat.as<float4>(),
-                         c->ra[cur].as<float4>(), c->rb[cur].as<float4>(), c->ra[nxt].as<float4>(), c->rb[nxt].as<float4>(),
-                         debug ? c->dbg[nxt].as<float2>() : nullptr, nullptr, nullptr, nullptr, nullptr, c->tuning,
-                         c->stream));
+    Ask ask;
+    ask.dbg = debug != 0;
+    TIMED(c, RESTIR_K_SPATIAL, launch_spatial(route_spatial(sd, c->stage_rg, d, c->tuning, ask), sd, c->stage_rg, d,
+                                              stage_bufs(c, camd, key, true), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->cur = nxt;   // the pass output becomes "current" (RES_*), its input "prev" (PREV_*)
     return RESTIR_OK;
@@ -1930,9 +1975,8 @@ restir_status restir_stage_final(restir_ctx* c, const restir_camera* cam, const 
     SceneDev sd;
     ST_TRY(scene_for(c, d, (size_t)c->vw * c->vh, sd));
     const CameraDev camd = camera_dev(cam);
-    const int cur = c->cur;
-    TIMED(c, RESTIR_K_FINAL, launch_final(sd, c->stage_rg, d, camd.origin, c->n_t.as<float4>(), c->p_mat.as<float4>(),
-                                          c->ra[cur].as<float4>(), c->rb[cur].as<float4>(), c->rgb.as<float>(), c->tuning, c->stream));
+    TIMED(c, RESTIR_K_FINAL, launch_final(route_final(sd, c->stage_rg, d, c->tuning, Ask{}), sd, c->stage_rg, d,
+                                          stage_bufs(c, camd, 0u, false), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RESTIR_OK;
 }
@@ -2176,31 +2220,23 @@ restir_status restir_halo_begin_layout(restir_ctx* c, const restir_camera* cam, 
     // the first pass overwrites them with those same values), so the passes and final shading write background tiles
     // without reading them; the ring's RIS costs (ring / tile) of the RIS time.  Otherwise primary rays on the view
     // and RIS / temporal reuse on the owned rectangle.
-    const bool fused = !temporal && c->tuning.fuse_primary_ris && primary_ris_fits(s);
+    const Ask ris_ask = frame_ris_ask(c, s, fb, temporal);
+    const Route ris = route_primary_ris(s, h.view, f, c->tuning, ris_ask);
+    LaunchBufs b = fb.bufs(h.camd, restir_rng_key(c->seed, h.frame, RESTIR_STAGE_RIS, 0), 0, 0);
     h.tmiss = nullptr;
-    if (fused) {
-        uint8_t* tm = nullptr;
-        if (c->tuning.miss_tiles && f.N <= 2 && s.normals_bounded && !fb.records) {
-            const size_t tiles = (size_t)((t.gwidth + 31u) / 32u) * ((t.gheight + 7u) / 8u);
-            ST_TRY(c->tmiss.ensure((tiles + 3u) & ~(size_t)3u));   // whole words (the spatial pass reads its flag's word)
-            tm = c->tmiss.as<uint8_t>();
-        }
-        bool written = false;
-        TIMED(c, RESTIR_K_PRIMARY_RIS,
-              launch_primary_ris(s, h.view, h.camd, f, restir_rng_key(c->seed, h.frame, RESTIR_STAGE_RIS, 0), fb.nt(0), pm,
-                                 fb.nt2(), fb.ra(0), fb.rb(0), nullptr, fb.rp(0), c->tuning, c->stream, tm, 0u, &written));
-        if (written) h.tmiss = tm;
+    if (!temporal && c->tuning.fuse_primary_ris && ris.ok) {
+        ST_TRY(ensure_tile_flags(c, ris, h.view, h.tmiss));
+        b.flags = h.tmiss;
+        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ris, s, h.view, f, b, c->stream));
     } else {
-        TIMED(c, RESTIR_K_PRIMARY, launch_primary(s, h.view, h.camd, fb.nt(0), pm, fb.nt2(), c->tuning, c->stream));
-        TIMED(c, RESTIR_K_RIS, launch_ris(s, h.owned, f, restir_rng_key(c->seed, h.frame, RESTIR_STAGE_RIS, 0),
-                                          h.camd.origin, fb.nt(0), pm, fb.ra(0), fb.rb(0), nullptr, fb.rp(0), c->tuning,
-                                          c->stream));
+        TIMED(c, RESTIR_K_PRIMARY, launch_primary(route_primary(s, h.view, c->tuning), s, h.view, b, c->stream));
+        TIMED(c, RESTIR_K_RIS, launch_ris(route_ris(s, h.owned, f, c->tuning, ris_ask), s, h.owned, f, b, c->stream));
     }
     if (temporal)
         TIMED(c, RESTIR_K_TEMPORAL,
               launch_temporal(s, h.owned, f, restir_rng_key(c->seed, h.frame, RESTIR_STAGE_TEMPORAL, 0), h.camd.origin, fb.nt(0),
                               pm, fb.ra(0), fb.rb(0), fb.pa(prev), fb.pb(prev), fb.ra(0), fb.rb(0), nullptr, fb.rp(0),
-                              fb.rp(0), c->tuning, c->stream));
+                              fb.rp(0), c->stream));
     if (temporal) used_prev(prev, c->stream, c->pool.get());
     h.rp_ok = fb.rp(0) != nullptr;
     h.active = true;
@@ -2283,16 +2319,19 @@ static restir_status halo_spatial_part(restir_ctx* c, const Region& rg, bool int
     const FrameBufs fb{c, h.fb_records, (size_t)h.view.vw * h.view.vh, h.f.N};
     SceneDev sd;
     ST_TRY(scene_for(c, h.f, (size_t)h.view.vw * h.view.vh, sd));
-    bool wrote = false;
-    TIMED(c, RESTIR_K_SPATIAL,
-          launch_spatial(sd, rg, h.f, restir_rng_key(c->seed, h.frame, RESTIR_STAGE_SPATIAL, h.pass), h.camd.origin,
-                         fb.nt(h.cur), c->p_mat.as<float4>(), fb.ra(h.cur), fb.rb(h.cur), fb.ra(nxt), fb.rb(nxt), nullptr,
-                         h.rp_ok ? fb.rp(h.cur) : nullptr, h.rp_ok && interior ? fb.rp(h.cur) : nullptr, fb.rp(nxt),
-                         &wrote, c->tuning, c->stream, nullptr, nullptr,
-                         // background tiles (restir_render's MissTiles): every ring pixel holds its owner's value, which
-                         // for a background tile is the known one
-                         MissTiles{h.tmiss, (!h.f.unbiased || h.pass == 0) ? h.f.M : 0u, 0u}));
-    rp_written = rp_written && wrote;
+    Ask ask;
+    ask.rp_in = h.rp_ok;
+    ask.rp_nb = h.rp_ok && interior;
+    ask.rp_out = fb.rp(nxt) != nullptr;
+    // background tiles (restir_render's MissTiles): every ring pixel holds its owner's value, which for a background
+    // tile is the known one
+    ask.flags = h.tmiss != nullptr;
+    ask.flags_m = (!h.f.unbiased || h.pass == 0) ? h.f.M : 0u;
+    const Route r = route_spatial(sd, rg, h.f, c->tuning, ask);
+    LaunchBufs b = fb.bufs(h.camd, restir_rng_key(c->seed, h.frame, RESTIR_STAGE_SPATIAL, h.pass), h.cur, nxt);
+    b.flags = h.tmiss;
+    TIMED(c, RESTIR_K_SPATIAL, launch_spatial(r, sd, rg, h.f, b, c->stream));
+    rp_written = rp_written && r.rp_out;
     return RESTIR_OK;
 }
 
@@ -2592,9 +2631,11 @@ restir_status restir_halo_end(restir_ctx* c, restir_frame** out_next, float* out
     const FrameBufs fb{c, h.fb_records, (size_t)h.view.vw * h.view.vh, h.f.N};
     SceneDev sd;
     ST_TRY(scene_for(c, h.f, (size_t)h.view.vw * h.view.vh, sd));
-    TIMED(c, RESTIR_K_FINAL, launch_final(sd, h.owned, h.f, h.camd.origin, fb.nt(h.cur), c->p_mat.as<float4>(),
-                                          fb.ra(h.cur), fb.rb(h.cur), c->rgb.as<float>(), c->tuning, c->stream, nullptr,
-                                          MissTiles{h.tmiss, 0u, 0u}));
+    Ask ask;
+    ask.flags = h.tmiss != nullptr;
+    LaunchBufs b = fb.bufs(h.camd, 0u, h.cur, h.cur);
+    b.flags = h.tmiss;
+    TIMED(c, RESTIR_K_FINAL, launch_final(route_final(sd, h.owned, h.f, c->tuning, ask), sd, h.owned, h.f, b, c->stream));
     c->cur = h.cur;
     h.active = false;
     if (out_next) {

@@ -121,7 +121,7 @@ struct MissTiles {
 
 // Sample handles (N = 1, point-light scenes, kernels.hip k_spatial1h): per view pixel the held sample's W (w) and
 // M | light index << 24 (m; index L = the initial zero sample), written beside the reservoir planes by the producer.
-// The predecessor grid of a temporal pass fused into primary rays + RIS (launch_primary_ris_temporal)
+// The predecessor grid of a temporal pass fused into primary rays + RIS (route_primary_ris_temporal)
 struct TemporalIn {
     const float4* pa;
     const float4* pb;
@@ -135,7 +135,6 @@ struct TemporalIn {
 struct Handles {
     float* w;
     uint32_t* m;
-    uint32_t res_dead;   // (an output) the handles are the reservoir planes' only reader: RIS / the pass skips their stores
 };
 
 // Launch-shape knobs (restir_set_tuning); they never change results, only speed.
@@ -145,7 +144,7 @@ struct Tuning {
     uint32_t primary_lds = 1;      // stage the BVH in LDS when it fits
     uint32_t ris_lds = 1;          // stage the light table in LDS when it fits
     uint32_t ris_compact = 1;      // N <= 2: compact light tables for point-light-only scenes and light grids (_pt /
-                                   // _grid RIS kernels, kernels.hip ris_light_form)
+                                   // _grid RIS kernels, route.h ris_light_form)
     uint32_t miss_tiles = 1;       // restir_render: background-tile flags (MissTiles) from RIS to the spatial passes
                                    // and final shading
     uint32_t miss_gbuf = 2;        // RIS skips background tiles' G-buffer stores: 0 never, 1 whenever the passes and final

@@ -21,7 +21,8 @@ def main():
     with tempfile.TemporaryDirectory() as td:
         src = os.path.join(td, "csrc")
         os.makedirs(src)
-        for f in [s for s, _ in build.SOURCES] + build.HEADERS:
+        at_rev = subprocess.check_output(["git", "-C", ROOT, "ls-tree", "--name-only", f"{rev}:romis_amd/csrc"]).decode().split()
+        for f in [s for s, _ in build.SOURCES] + [h for h in build.HEADERS if h in at_rev]:   # (a header may be newer than rev)
             with open(os.path.join(src, f), "wb") as fh:
                 fh.write(subprocess.check_output(["git", "-C", ROOT, "show", f"{rev}:romis_amd/csrc/{f}"]))
         objs = []

@@ -13,7 +13,7 @@ Sizes: 65 x 35 has three tile columns, the last one pixel wide, so AW takes 1 + 
 heights; 97 x 41 of the nightclub and 65 x 35 of cornell_1024's default camera have all-background, mixed and
 all-geometry tiles.
 
-Routes, by the condition of launch_spatial / spatial_handle_kind that selects the kernel (lean: spatial.lean, N = 1,
+Routes, by the condition of route_spatial / spatial_handle_kind (csrc/route.h) that selects the kernel (lean: spatial.lean, N = 1,
 K <= 5, SoA planes; lean2: the same at N = 2; hin: the pass reads handles, spatial_handle_kind >= 0):
 
 stage API (no handles, no background flags; debug on: the _dbg instantiation, off: the shipped one)
@@ -283,7 +283,7 @@ def test_frame_sweep(gpu, oracle, route, K, R):
 def test_background_tiles_sweep(gpu, oracle, name, w, h, N, K, R):
     """Frames with all-background, mixed and all-geometry tiles, the flags (miss.tiles) on and off, RIS's G-buffer skip
     forced (miss.gbuf = 1: the window fix-up of lean_window_ready, whose flag lookups go through row()) and at its default,
-    both tile heights.  (6,10) and (5,11) are the fallback: spatial_reads_flags turns false, so RIS must store the
+    both tile heights.  (6,10) and (5,11) are the fallback: the pass route's bg_known turns false, so RIS must store the
     reservoirs of its background tiles for the general kernels."""
     s, _, cam, _, _, hit = inputs(oracle, name, None, w, h)
     bg, mixed, _ = tile_census(hit, w, h)
