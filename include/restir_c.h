@@ -522,6 +522,10 @@ restir_status restir_measure_read_bandwidth(restir_ctx* ctx, uint64_t bytes, uin
  * "miss.tiles" off).  Synchronises the context's stream. */
 restir_status restir_background_pixels(restir_ctx* ctx, uint64_t* background, uint64_t* computed);
 
+/* restir_render frames of this context so far that read the kept G-buffer (tuning "gbuf.reuse") instead of tracing
+ * their primary rays; restir_timings counts both kinds under RESTIR_K_PRIMARY_RIS. */
+restir_status restir_gbuf_reuses(restir_ctx* ctx, uint64_t* out_frames);
+
 /* ---- timing ----------------------------------------------------------------------------------------- */
 /* When enabled, every kernel of restir_render / restir_stage_* is bracketed by HIP events on the
  * context's stream; restir_timings returns the accumulated milliseconds and launch counts per kernel. */
@@ -556,7 +560,11 @@ restir_status restir_enable_timing(restir_ctx* ctx, int enable);
  * "final.miss" (final shading reads only p_mat and
  * (pos, W) for a primary-ray miss), "miss.tiles" (background-tile flags from RIS to the spatial passes and final
  * shading, N <= 2 without temporal reuse), "miss.gbuf" (0 / 1 / 2 = auto: RIS also skips background tiles' G-buffer
- * stores), "timing.every" / "timing.fence" (event sampling), "mis.chunk" (R-OMIS samples per launch pair).  All default
+ * stores), "gbuf.reuse" (a context keeps the G-buffer and tile flags of the last view restir_render traced -- scene
+ * upload, camera, image size, tile -- and a frame of the same view runs the k_gbuf_ris family over them instead of
+ * tracing the primary rays again, timed as RESTIR_K_PRIMARY_RIS like the kernel it stands in for; setting any knob, a
+ * scene upload, a stage or halo call make the next frame trace; SoA planes only; 0: every frame traces; default 1),
+ * "timing.every" / "timing.fence" (event sampling), "mis.chunk" (R-OMIS samples per launch pair).  All default
  * on where measured faster.  Round 5 removed the knobs measured slower in two rounds (persistent *.blocks grids, the
  * RIS work queue, the gather-only spatial pass, non-XCD / row-wave tile orders, 1-D primary / final maps, frames in
  * flight): unknown keys are RESTIR_ERR_INVALID. */

@@ -256,6 +256,7 @@ SIGNATURES = {
     "restir_halo_begin_layout": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Features), C.POINTER(TileLayout), C.c_uint32,
                                            _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "restir_background_pixels": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "restir_gbuf_reuses": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "restir_enable_timing": (C.c_int, [_P, C.c_int]),
     "restir_set_tuning": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "restir_timings": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),

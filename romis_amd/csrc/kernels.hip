@@ -661,6 +661,99 @@ ROMIS_PRIMARY_RIS_KERNEL_LT(2, false, kLtPgram, k_primary_ris_n2_pg, ROMIS_RIS_A
 ROMIS_PRIMARY_RIS_TEMPORAL_KERNEL(1, k_primary_ris_n1_lds_pt_temporal, ROMIS_RIS1_ATTR)
 ROMIS_PRIMARY_RIS_TEMPORAL_KERNEL(2, k_primary_ris_n2_lds_pt_temporal, ROMIS_RIS_ATTR)
 
+// k_gbuf_ris: the fused kernel's frame over a view whose G-buffer and tile flags an earlier frame of the same context
+// left in memory (restir_render's GbufView: the same scene upload, camera, image size and region -- none of them
+// depends on the frame's RNG key).  One 32 x 8 tile per block, as the fused kernel's one-tile form: the block takes its
+// flag from tmiss and its pixels' records from n_t / p_mat and traces nothing -- no candidate-triangle list, no BVH
+// unless the initial visibility rays need it, no G-buffer or flag stores.  ris_pixel gets the values primary_pixel
+// would have produced, so every result is the fused kernel's bit for bit.
+template <int NT, bool LDS_LIGHTS, int LT = kLtGeneral, bool TEMP = false>
+__device__ __forceinline__ void gbuf_ris_body(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key,
+                                              v3 origin, const float4* __restrict__ n_t, const float4* __restrict__ p_mat,
+                                              float4* __restrict__ ra, float4* __restrict__ rb, float2* __restrict__ rdbg,
+                                              float* __restrict__ rp, const uint8_t* __restrict__ tmiss, uint32_t skip_res,
+                                              float* __restrict__ hw, uint32_t* __restrict__ hm, uint32_t res_dead,
+                                              TemporalIn tin = TemporalIn{nullptr, nullptr, 0u}) {
+    if (blockIdx.x >= work_items(rg)) return;   // block-uniform
+    // the tile's flag: its word by a scalar load (block-uniform address, written by an earlier kernel, the buffer in
+    // whole words -- as tiles_known_miss reads it)
+    bool any = true;
+    if (tmiss) {
+        const auto* w = (const __attribute__((address_space(4))) uint32_t*)(tmiss + (blockIdx.x & ~3u));
+        any = ((*w >> (8u * (blockIdx.x & 3u))) & 0xFFu) != 0u;
+    }
+    // a background tile whose known reservoirs no reader needs (skip_res bit 0): nothing to do
+    if (!any && (skip_res & 1u)) return;
+    uint32_t x, y;
+    size_t p;
+    const bool live = work_pixel(rg, blockIdx.x, x, y, p);
+    // the pixel's records, in flight while the block stages its tables (a background tile that stores its known
+    // reservoirs reads them too: ris_pixel's miss test and the held sample's pdf are functions of them)
+    float4 nt = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pm = nt;
+    if (live) {
+        nt = n_t[gidx(rg, p)];
+        pm = p_mat[p];
+    }
+    // the BVH only for the initial visibility rays; the light table behind it, for the tiles that run the candidate
+    // loop (ris.late's rule; TEMP with frame handles: every tile, the predecessor's handle may name a real light)
+    const uint32_t bvh_f4 = f.initial_vis ? 2u * s.num_nodes + 3u * s.num_tris : 0u;
+    const float4* lights = global_lights<LT>(s);
+    if (LDS_LIGHTS) {
+        if (any || (TEMP && tin.hw != nullptr)) stage_lights<LT>(s, g_lds + bvh_f4);
+        lights = g_lds + bvh_f4;
+    }
+    const GlTabs tb = gl_stage_tables<false>();
+    Bvh bvh = global_bvh(s);
+    if (f.initial_vis) bvh = stage_bvh(s, g_lds);   // (ends with the barrier)
+    else __syncthreads();
+    if (live)
+        ris_pixel<NT, LT, TEMP>(s, rg, f, key, origin, lights, bvh, nt, pm, x, y, p, ra, rb, rdbg, rp, tb, hw, hm,
+                                !(hw && res_dead), tin);
+}
+
+#define ROMIS_GBUF_RIS_KERNEL_LT(NT, LDS, LT, NAME, ATTR)                                                              \
+    extern "C" __global__ __launch_bounds__(256) ATTR void NAME(SceneDev s, Region rg, FeaturesDev f, uint32_t key,    \
+                                                          float ox, float oy, float oz, const float4* n_t,             \
+                                                          const float4* p_mat, float4* ra, float4* rb, float2* rdbg,   \
+                                                          float* rp, const uint8_t* tmiss, uint32_t skip_res,          \
+                                                          float* hw, uint32_t* hm, uint32_t res_dead) {                \
+        gbuf_ris_body<NT, LDS, LT>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, ra, rb, rdbg, rp, tmiss, skip_res, hw,   \
+                                   hm, res_dead);                                                                      \
+    }
+#define ROMIS_GBUF_RIS_KERNEL(NT, LDS, NAME, ATTR) ROMIS_GBUF_RIS_KERNEL_LT(NT, LDS, kLtGeneral, NAME, ATTR)
+#define ROMIS_GBUF_RIS_TEMPORAL_KERNEL(NT, NAME, ATTR)                                                                 \
+    extern "C" __global__ __launch_bounds__(256) ATTR void NAME(SceneDev s, Region rg, FeaturesDev f, uint32_t key,    \
+                                                          float ox, float oy, float oz, const float4* n_t,             \
+                                                          const float4* p_mat, float4* ra, float4* rb, float2* rdbg,   \
+                                                          float* rp, TemporalIn tin, float* hw, uint32_t* hm,          \
+                                                          uint32_t res_dead) {                                         \
+        gbuf_ris_body<NT, true, kLtPoint, true>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, ra, rb, rdbg, rp, nullptr,  \
+                                                0u, hw, hm, res_dead, tin);                                            \
+    }
+// the members of the k_primary_ris family, under its waves-per-SIMD caps
+ROMIS_GBUF_RIS_KERNEL(1, true, k_gbuf_ris_n1_lds, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_KERNEL(1, false, k_gbuf_ris_n1, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_KERNEL(2, true, k_gbuf_ris_n2_lds, ROMIS_RIS_ATTR)
+ROMIS_GBUF_RIS_KERNEL(2, false, k_gbuf_ris_n2, ROMIS_RIS_ATTR)
+ROMIS_GBUF_RIS_KERNEL(0, true, k_gbuf_ris_n0_lds, )
+ROMIS_GBUF_RIS_KERNEL(0, false, k_gbuf_ris_n0, )
+ROMIS_GBUF_RIS_KERNEL_LT(1, true, kLtPoint, k_gbuf_ris_n1_lds_pt, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(2, true, kLtPoint, k_gbuf_ris_n2_lds_pt, ROMIS_RIS_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(1, false, kLtPoint, k_gbuf_ris_n1_pt, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(2, false, kLtPoint, k_gbuf_ris_n2_pt, ROMIS_RIS_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(1, true, kLtGrid, k_gbuf_ris_n1_lds_grid, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(2, true, kLtGrid, k_gbuf_ris_n2_lds_grid, ROMIS_RIS_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(1, false, kLtGrid, k_gbuf_ris_n1_grid, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(2, false, kLtGrid, k_gbuf_ris_n2_grid, ROMIS_RIS_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(1, false, kLtRegular, k_gbuf_ris_n1_reg, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(1, true, kLtRegular, k_gbuf_ris_n1_lds_reg, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(1, true, kLtPgram, k_gbuf_ris_n1_lds_pg, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(2, true, kLtPgram, k_gbuf_ris_n2_lds_pg, ROMIS_RIS_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(1, false, kLtPgram, k_gbuf_ris_n1_pg, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_KERNEL_LT(2, false, kLtPgram, k_gbuf_ris_n2_pg, ROMIS_RIS_ATTR)
+ROMIS_GBUF_RIS_TEMPORAL_KERNEL(1, k_gbuf_ris_n1_lds_pt_temporal, ROMIS_RIS1_ATTR)
+ROMIS_GBUF_RIS_TEMPORAL_KERNEL(2, k_gbuf_ris_n2_lds_pt_temporal, ROMIS_RIS_ATTR)
+
 // k_temporal: temporalReuse (render_utils.cpp:142-177).  cur = (ca, cb), prev = (pa, pb); writes (oa, ob).
 template <int NT>
 __device__ __forceinline__ void temporal_body(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key,
@@ -2660,6 +2753,32 @@ hipError_t launch_primary_ris(const Route& r, const SceneDev& s, const Region& r
     const Region rg = r.region(rg0);
     float* const hw = named(r.how, b.hout.w);
     uint32_t* const hm = named(r.hom, b.hout.m);
+    if (r.kernel == Kernel::kGbufRis || r.kernel == Kernel::kGbufRisTemporal) {
+        // the G-buffer and the flags of an earlier frame (route_primary_ris with Ask::gbuf_cached): read, not written
+        const float* o = b.origin;
+        const float4* const n_t = b.n_t;
+        const float4* const p_mat = b.p_mat;
+        if (r.kernel == Kernel::kGbufRisTemporal) {
+            ROMIS_LAUNCH(r.n == 1 ? k_gbuf_ris_n1_lds_pt_temporal : k_gbuf_ris_n2_lds_pt_temporal, dim3(r.grid),
+                         dim3(r.block), r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], n_t, p_mat, b.oa, b.ob,
+                         named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), b.tin, hw, hm, r.res_dead);
+            return hipGetLastError();
+        }
+        const bool staged = r.staged, n1 = r.n == 1;
+        auto k = r.lt == kLtRegular ? (staged ? k_gbuf_ris_n1_lds_reg : k_gbuf_ris_n1_reg)
+               : r.lt == kLtPoint ? (staged ? (n1 ? k_gbuf_ris_n1_lds_pt : k_gbuf_ris_n2_lds_pt)
+                                            : (n1 ? k_gbuf_ris_n1_pt : k_gbuf_ris_n2_pt))
+               : r.lt == kLtGrid ? (staged ? (n1 ? k_gbuf_ris_n1_lds_grid : k_gbuf_ris_n2_lds_grid)
+                                           : (n1 ? k_gbuf_ris_n1_grid : k_gbuf_ris_n2_grid))
+               : r.lt == kLtPgram ? (staged ? (n1 ? k_gbuf_ris_n1_lds_pg : k_gbuf_ris_n2_lds_pg)
+                                            : (n1 ? k_gbuf_ris_n1_pg : k_gbuf_ris_n2_pg))
+               : staged ? (n1 ? k_gbuf_ris_n1_lds : (r.n == 2 ? k_gbuf_ris_n2_lds : k_gbuf_ris_n0_lds))
+                        : (n1 ? k_gbuf_ris_n1 : (r.n == 2 ? k_gbuf_ris_n2 : k_gbuf_ris_n0));
+        const uint8_t* const flags = named(r.flags, b.flags);
+        ROMIS_LAUNCH(k, dim3(r.grid), dim3(r.block), r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], n_t, p_mat, b.oa,
+                     b.ob, named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), flags, r.skip, hw, hm, r.res_dead);
+        return hipGetLastError();
+    }
     if (r.kernel == Kernel::kPrimaryRisTemporal) {
         ROMIS_LAUNCH(r.n == 1 ? k_primary_ris_n1_lds_pt_temporal : k_primary_ris_n2_lds_pt_temporal, dim3(r.grid),
                      dim3(r.block), r.lds, stream, s, rg, *b.cam, f, b.key, b.n_t, b.p_mat, b.n_t2, b.oa, b.ob,

@@ -38,7 +38,8 @@ hipError_t launch_primary(const Route& r, const SceneDev& s, const Region& rg, c
 hipError_t launch_ris(const Route& r, const SceneDev& s, const Region& rg, const FeaturesDev& f, const LaunchBufs& b,
                       hipStream_t stream);
 // genPrimaryRayHits + genCanonicalSamples in one kernel over the same region (route_primary_ris), with temporal reuse
-// too (route_primary_ris_temporal)
+// too (route_primary_ris_temporal).  A route of the k_gbuf_ris family (Kernel::kGbufRis / kGbufRisTemporal, Ask::gbuf_cached)
+// reads b.n_t, b.p_mat and b.flags as an earlier frame of the same view left them and writes none of them.
 hipError_t launch_primary_ris(const Route& r, const SceneDev& s, const Region& rg, const FeaturesDev& f, const LaunchBufs& b,
                               hipStream_t stream);
 hipError_t launch_temporal(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key, const float* origin,

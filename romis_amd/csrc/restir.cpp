@@ -244,6 +244,24 @@ struct restir_ctx {
     uint32_t tmiss_w = 0, tmiss_h = 0;              // the last frame's computed region when it kept the flags (else 0)
     uint64_t last_px = 0;                           // the last frame's computed pixels
     DevBuf hnd[2];                                  // sample handles of rec[i] (N = 1 point lights, k_spatial1h)
+    // The view whose G-buffer n_t, p_mat, uv (textured scenes) and tile flags tmiss hold (tuning "gbuf.reuse"): written
+    // after a restir_render frame's fused primary + RIS launch over the SoA planes.  They are a function of these
+    // fields and nothing else -- the frame index and the RNG key do not enter -- so a later frame whose fields are
+    // equal launches the k_gbuf_ris family over them (gbuf_reusable) instead of tracing the primary rays again.
+    // Everything else that writes those buffers, or changes what a frame would write there, clears `valid`.
+    struct GbufView {
+        bool valid = false;
+        uint64_t scene_gen = 0;
+        uint32_t cam[9] = {};                      // CameraDev: quat, origin, half_w, half_h, as bits
+        uint32_t width = 0, height = 0;
+        restir_tile tile{};
+        uint32_t tex_on = 0;
+        bool flags = false;                        // tmiss holds the view's flags
+        uint32_t skip = 0;                         // the skip_res word the tracing frame ran with
+        uint32_t map2d = 0, xcd_rows = 0, xcd_cols = 0, items = 0;   // the tile order the flags are indexed by
+        const void *n_t = nullptr, *p_mat = nullptr, *uv = nullptr, *tmiss = nullptr;   // the buffers themselves
+    } gbuf;
+    uint64_t gbuf_reuses = 0;                       // frames that took the k_gbuf_ris family (restir_gbuf_reuses)
     int cur = 0;
     uint32_t rgb_w = 0, rgb_h = 0;
 
@@ -933,8 +951,13 @@ restir_status ensure_records(restir_ctx* c, uint32_t vw, uint32_t vh, uint32_t N
     const size_t npx = (size_t)vw * vh;
     fb = FrameBufs{c, c->tuning.records != 0, npx, N};
     const hipStream_t st = c->stream;
+    // the kept G-buffer (restir_ctx::gbuf) does not survive another view size or a reallocation
+    const void* const old_nt = c->n_t.p;
+    const void* const old_pm = c->p_mat.p;
+    if (vw != c->vw || vh != c->vh) c->gbuf.valid = false;
     ST_TRY(c->p_mat.ensure(npx * 16));
     if (!fb.records) ST_TRY(c->n_t.ensure(npx * 16));
+    if (c->n_t.p != old_nt || c->p_mat.p != old_pm) c->gbuf.valid = false;
     // (planes, N = 1: + the frame handles' two 4-byte planes and 16 B of slack; N = 2: + the 16-byte handle records and
     // 16 B; FrameBufs::fh)
     const size_t rec_bytes = npx * (fb.records ? 1u + 2u * N : 2u * N) * 16 +
@@ -1124,6 +1147,7 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
             return fail(RESTIR_ERR_INVALID, "mesh %u: kd_texture %u of %u textures", m, meshes[m].material.kd_texture,
                         num_textures);
     std::lock_guard<std::mutex> lk(c->mu);
+    c->gbuf.valid = false;   // another scene: the kept G-buffer is not its view
     HIP_TRY(hipSetDevice(c->device));
 
     // flatten triangles (mesh order = original index order, like the oracle)
@@ -1432,6 +1456,7 @@ static restir_status render_mis(restir_ctx* c, const restir_camera* cam, const r
     if (W == 0 || H == 0) return fail(RESTIR_ERR_INVALID, "empty image %ux%u", W, H);
     ST_TRY(check_romis_window(features, W, H));
     const FeaturesDev f = to_dev(features);
+    c->gbuf.valid = false;   // k_primary writes n_t / p_mat below
     ST_TRY(ensure_work(c, W, H, f.N, true));
     ST_TRY(ensure_mis(c, features, W, H));
     ST_TRY(c->rgb.ensure((size_t)W * H * 12));
@@ -1492,6 +1517,40 @@ static restir_status ensure_tile_flags(restir_ctx* c, const Route& ris, const Re
     ST_TRY(c->tmiss.ensure((tiles + 3u) & ~(size_t)3u));
     flags = c->tmiss.as<uint8_t>();
     return RESTIR_OK;
+}
+
+// What a frame's fused primary + RIS launch `ris` over tile t leaves in the G-buffer planes and the flags (restir_ctx::gbuf)
+static restir_ctx::GbufView gbuf_view(const restir_ctx* c, const SceneDev& s, const CameraDev& cam, uint32_t width,
+                                      uint32_t height, const restir_tile& t, const Route& ris, const uint8_t* tmiss) {
+    restir_ctx::GbufView v;
+    v.scene_gen = c->scene_gen;
+    const float camf[9] = {cam.quat.x, cam.quat.y, cam.quat.z, cam.quat.w, cam.origin[0], cam.origin[1], cam.origin[2],
+                           cam.half_w, cam.half_h};
+    std::memcpy(v.cam, camf, sizeof(v.cam));
+    v.width = width; v.height = height;
+    v.tile = t;
+    v.tex_on = s.tex_on;
+    v.flags = ris.flags && tmiss != nullptr;
+    v.skip = ris.skip;
+    v.map2d = ris.map2d; v.xcd_rows = ris.xcd_rows; v.xcd_cols = ris.xcd_cols; v.items = ris.grid;
+    v.n_t = c->n_t.p; v.p_mat = c->p_mat.p; v.uv = s.gbuf_uv; v.tmiss = v.flags ? tmiss : nullptr;
+    return v;
+}
+
+// The planes hold view `have` (a frame that traced it); a frame that would trace `want` may read them instead when
+// every field is equal but the flags and the skip word, where `have` must hold all `want` reads: the flags if it wants
+// any, and background tiles' G-buffer records (skip bit 1: not stored) unless it skips them too.  (Bit 0, the
+// reservoirs, are every frame's own.)
+static bool gbuf_reusable(const restir_ctx::GbufView& have, const restir_ctx::GbufView& want) {
+    const restir_tile &a = have.tile, &b = want.tile;
+    return have.valid && have.scene_gen == want.scene_gen && !std::memcmp(have.cam, want.cam, sizeof(have.cam)) &&
+           have.width == want.width && have.height == want.height && a.global_width == b.global_width &&
+           a.global_height == b.global_height && a.gx0 == b.gx0 && a.gy0 == b.gy0 && a.gwidth == b.gwidth &&
+           a.gheight == b.gheight && a.x0 == b.x0 && a.y0 == b.y0 && a.width == b.width && a.height == b.height &&
+           have.tex_on == want.tex_on && have.map2d == want.map2d && have.xcd_rows == want.xcd_rows &&
+           have.xcd_cols == want.xcd_cols && have.items == want.items && have.n_t == want.n_t && have.p_mat == want.p_mat &&
+           have.uv == want.uv && (!want.flags || (have.flags && have.tmiss == want.tmiss)) &&
+           (!(have.skip & 2u) || (want.skip & 2u));
 }
 
 // renderReSTIR (render.cpp:28-62)
@@ -1654,6 +1713,18 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
     ris_ask.skip = skip_mode;
     LaunchBufs b = fb.bufs(camd, restir_rng_key(c->seed, frame, RESTIR_STAGE_RIS, 0), 0, cur);
     b.flags = tmiss;
+    // the view this frame's fused kernel would leave in the G-buffer planes; when they hold it already (the static
+    // camera of the reference's viewer loop), the k_gbuf_ris family runs over them instead (tuning "gbuf.reuse")
+    restir_ctx::GbufView gv;
+    if (fused) {
+        ris = temporal_fused ? route_primary_ris_temporal(s, view, f, c->tuning, ris_ask)
+                             : route_primary_ris(s, view, f, c->tuning, ris_ask);
+        gv = gbuf_view(c, s, camd, width, height, t, ris, tmiss);
+        ris_ask.gbuf_cached = c->tuning.gbuf_reuse && !fb.records && gbuf_reusable(c->gbuf, gv);
+    }
+    // kept by a frame that reuses it; a frame that traces replaces it once its launch is issued (any error return in
+    // between leaves none)
+    if (!ris_ask.gbuf_cached) c->gbuf.valid = false;
     if (temporal_fused) {
         ris = route_primary_ris_temporal(s, view, f, c->tuning, ris_ask);
         ST_TRY(use_prev(prev, c->device, st, c->pool.get()));   // the predecessor's records are complete (its producer's stream)
@@ -1668,6 +1739,12 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
         ris = route_ris(s, view, f, c->tuning, ris_ask);
         TIMED(c, RESTIR_K_PRIMARY, launch_primary(route_primary(s, view, c->tuning), s, view, b, st));
         TIMED(c, RESTIR_K_RIS, launch_ris(ris, s, view, f, b, st));
+    }
+    if (ris_ask.gbuf_cached) {
+        c->gbuf_reuses++;
+    } else if (fused && !fb.records) {
+        c->gbuf = gv;
+        c->gbuf.valid = true;
     }
     c->last_px = (uint64_t)t.gwidth * t.gheight;   // restir_background_pixels
     c->tmiss_w = tmiss ? t.gwidth : 0u;
@@ -1805,6 +1882,7 @@ restir_status restir_download_rgb(restir_ctx* c, float* out_rgb, size_t count) {
 restir_status restir_stage_configure(restir_ctx* c, uint32_t width, uint32_t height, uint32_t n) {
     if (!c || width == 0 || height == 0 || n < 1 || n > RESTIR_MAX_N) return fail(RESTIR_ERR_INVALID, "bad stage size");
     std::lock_guard<std::mutex> lk(c->mu);
+    c->gbuf.valid = false;   // the stages write the frame path's G-buffer planes
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(ensure_work(c, width, height, n, true));
     ST_TRY(c->rgb.ensure((size_t)width * height * 12));
@@ -1846,6 +1924,7 @@ static restir_status stage_buffer(restir_ctx* c, restir_buffer which, DevBuf** o
 restir_status restir_stage_upload(restir_ctx* c, restir_buffer which, const void* host, size_t bytes) {
     if (!c || !host) return fail(RESTIR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mu);
+    c->gbuf.valid = false;
     if (!c->stage_ok) return fail(RESTIR_ERR_STATE, "restir_stage_configure first");
     DevBuf* b;
     size_t need;
@@ -1860,6 +1939,7 @@ restir_status restir_stage_upload(restir_ctx* c, restir_buffer which, const void
 restir_status restir_stage_download(restir_ctx* c, restir_buffer which, void* host, size_t bytes) {
     if (!c || !host) return fail(RESTIR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mu);
+    c->gbuf.valid = false;   // (stage_buffer may allocate the uv plane)
     if (!c->stage_ok) return fail(RESTIR_ERR_STATE, "restir_stage_configure first");
     DevBuf* b;
     size_t need;
@@ -1874,6 +1954,7 @@ restir_status restir_stage_download(restir_ctx* c, restir_buffer which, void* ho
 #define STAGE_PRELUDE()                                                             \
     if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");                         \
     std::lock_guard<std::mutex> lk(c->mu);                                          \
+    c->gbuf.valid = false;                                                          \
     if (!c->stage_ok) return fail(RESTIR_ERR_STATE, "restir_stage_configure first"); \
     if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_set_scene first");      \
     HIP_TRY(hipSetDevice(c->device));                                               \
@@ -2094,6 +2175,13 @@ restir_status restir_background_pixels(restir_ctx* c, uint64_t* background, uint
     return RESTIR_OK;
 }
 
+restir_status restir_gbuf_reuses(restir_ctx* c, uint64_t* out_frames) {
+    if (!c || !out_frames) return fail(RESTIR_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out_frames = c->gbuf_reuses;
+    return RESTIR_OK;
+}
+
 restir_status restir_measure_read_bandwidth(restir_ctx* c, uint64_t bytes, uint32_t iters, double* out_gbps) {
     if (!c || !out_gbps || iters == 0 || bytes < (1u << 20)) return fail(RESTIR_ERR_INVALID, "bad argument");
     std::lock_guard<std::mutex> lk(c->mu);
@@ -2159,6 +2247,7 @@ restir_status restir_halo_begin_layout(restir_ctx* c, const restir_camera* cam, 
     ST_TRY(check_features(features));
     ST_TRY(layout_check(layout));
     std::lock_guard<std::mutex> lk(c->mu);
+    c->gbuf.valid = false;   // a halo frame writes the same G-buffer planes and flags (and keeps the tracing kernels)
     if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_halo_begin before restir_set_scene");
     HIP_TRY(hipSetDevice(c->device));
     const FeaturesDev f = to_dev(features);
@@ -2688,6 +2777,7 @@ restir_status restir_timings(restir_ctx* c, double* ms, uint64_t* launches) {
 restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     if (!c || !key) return fail(RESTIR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mu);
+    c->gbuf.valid = false;   // a knob may change what a frame leaves in the G-buffer planes: the next one traces
     Tuning& t = c->tuning;
     const uint32_t v = (uint32_t)value;
     if (!std::strcmp(key, "primary.lds")) t.primary_lds = v;
@@ -2723,6 +2813,7 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     else if (!std::strcmp(key, "final.qbvh")) t.final_qbvh = v;
     else if (!std::strcmp(key, "final.fuse")) t.final_fuse = v;
     else if (!std::strcmp(key, "primary.tl")) t.primary_tl = v;
+    else if (!std::strcmp(key, "gbuf.reuse")) t.gbuf_reuse = v;
     else if (!std::strcmp(key, "mis.chunk")) t.mis_chunk = v;   // applies from the next ensure_mis
     else if (!std::strcmp(key, "layout.records")) t.records = v;   // frame-path buffer layout
     else if (!std::strcmp(key, "final.lds")) t.final_lds = v;

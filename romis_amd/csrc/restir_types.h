@@ -184,7 +184,10 @@ struct Tuning {
                                    // (k_spatial1hg_t2_final) where both kernels' conditions hold; 0: always two kernels
     uint32_t primary_tl = 1;       // fused primary + RIS, one tile per block: the primary rays test the tile's candidate
                                    // triangles (tile_triangles) instead of walking the BVH
-    uint32_t mis_chunk = 0;        // R-OMIS samples per k_romis_samples / k_romis_accum pair; 0 = the scratch budget
+    uint32_t gbuf_reuse = 1;       // restir_render: a frame whose view (scene upload, camera, image size, region) is the one
+                                   // the context's G-buffer planes and tile flags hold runs the k_gbuf_ris family over
+                                   // them instead of tracing the primary rays again; 0: every frame traces
+    uint32_t mis_chunk = 0;       // R-OMIS samples per k_romis_samples / k_romis_accum pair; 0 = the scratch budget
 };
 
 // Halo segments of one exchange (restir_halo_plan), pixel prefix offsets into the packed buffer.

@@ -30,6 +30,8 @@ enum class Kernel : uint8_t {
     kFinal,                // k_final_n{N}[_lds]
     kFinalSorted,          // k_final_n{1,2}_sorted: one tile per block, the shadow rays binned by target
     kFinalSortedQ,         // k_final_n{1,2}_sorted_q: ... over the 16-byte BVH nodes
+    kGbufRis,              // k_gbuf_ris_n{N}[_lds][_pt | _grid | _pg | _reg]: kPrimaryRis over a cached G-buffer
+    kGbufRisTemporal,      // k_gbuf_ris_n{N}_lds_pt_temporal
 };
 
 // The automatic XCD chunks (spatial.xcd_rows / spatial.xcd_cols left at auto) of a lean spatial kernel
@@ -56,6 +58,9 @@ struct Ask {
     uint32_t skip = 0;        // primary + RIS: what of background tiles no reader needs (bit 0 reservoirs, 1 G-buffer)
     bool fin = false;         // spatial: final shading of the pass's rect may run in the same kernel
     bool fin_dead = false;    // ... and then nothing else reads the pass's reservoir planes
+    // primary + RIS: the view's G-buffer and tile flags are in memory from an earlier frame (restir_render's GbufView):
+    // the k_gbuf_ris family reads them and traces nothing
+    bool gbuf_cached = false;
 };
 
 struct Route {
@@ -199,7 +204,8 @@ inline Route route_ris(const SceneDev& s, const Region& rg, const FeaturesDev& f
 }
 
 // Both in one kernel over the same region, the BVH in LDS (!ok: it does not fit); asks: dbg, rp_out, flags with skip,
-// hout with hout_dead
+// hout with hout_dead, gbuf_cached (the same member of the k_gbuf_ris family: the BVH in LDS only for the initial
+// visibility rays, so the light table stands alone there otherwise)
 inline Route route_primary_ris(const SceneDev& s, const Region& rg, const FeaturesDev& f, const Tuning& tu, const Ask& ask) {
     Route r;
     const size_t bvh = bvh_lds_bytes(s);
@@ -221,6 +227,11 @@ inline Route route_primary_ris(const SceneDev& s, const Region& rg, const Featur
     if (!r.ok || route_detail::empty(rg)) return r;
     r.kernel = Kernel::kPrimaryRis;
     route_detail::items(r, rg, 1u);
+    if (ask.gbuf_cached) {
+        // the same family member (r.staged as the fused kernel decided it), its LDS without the BVH where no ray needs it
+        r.kernel = Kernel::kGbufRis;
+        r.lds = (f.initial_vis ? bvh : 0) + (r.staged ? (size_t)lt_stride(r.lt) * s.num_lights * 16 : 0);
+    }
     return r;
 }
 
@@ -233,7 +244,8 @@ inline Route route_primary_ris_temporal(const SceneDev& s, const Region& rg, con
     r.flags = false;   // (no background tiles: the output is not the RIS result)
     r.skip = 0u;
     r.hom = r.how;     // both planes at N = 1 and 2
-    if (r.kernel != Kernel::kNone) r.kernel = r.ok ? Kernel::kPrimaryRisTemporal : Kernel::kNone;
+    if (r.kernel != Kernel::kNone)
+        r.kernel = !r.ok ? Kernel::kNone : ask.gbuf_cached ? Kernel::kGbufRisTemporal : Kernel::kPrimaryRisTemporal;
     return r;
 }
 

@@ -194,6 +194,13 @@ class Renderer:
         check(self.lib, self.lib.restir_background_pixels(self.ctx, C.byref(bg), C.byref(px)), "restir_background_pixels")
         return int(bg.value), int(px.value)
 
+    def gbuf_reuses(self) -> int:
+        """render_restir frames so far that read the context's kept G-buffer instead of tracing their primary rays
+        (restir_gbuf_reuses; tuning "gbuf.reuse")."""
+        n = C.c_uint64()
+        check(self.lib, self.lib.restir_gbuf_reuses(self.ctx, C.byref(n)), "restir_gbuf_reuses")
+        return int(n.value)
+
     # ---- timing ---------------------------------------------------------------------------------------
     def enable_timing(self, on: bool = True) -> None:
         check(self.lib, self.lib.restir_enable_timing(self.ctx, 1 if on else 0), "restir_enable_timing")
