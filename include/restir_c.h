@@ -526,6 +526,24 @@ restir_status restir_background_pixels(restir_ctx* ctx, uint64_t* background, ui
  * their primary rays; restir_timings counts both kinds under RESTIR_K_PRIMARY_RIS. */
 restir_status restir_gbuf_reuses(restir_ctx* ctx, uint64_t* out_frames);
 
+/* What restir_set_scene derived from the scene it uploaded -- the facts the route functions choose kernels by -- so that a
+ * test can tell which form a scene took (a light grid the regular form, a BVH past the LDS budget).  Read-only: runs no
+ * kernel, changes nothing.  RESTIR_ERR_STATE before the first scene.  (In C++ the function hides the struct's name:
+ * write `struct restir_scene_info`.) */
+struct restir_scene_info {
+    uint32_t num_nodes, num_tris;   /* the flattened BVH (tuning "bvh.max_leaf" at the upload) */
+    uint64_t bvh_lds_bytes;         /* (2 num_nodes + 3 num_tris) * 16: staged in LDS while <= 65,536 */
+    uint32_t num_lights;
+    uint32_t light_types;           /* bit t set <=> a light of restir_light_type t is present */
+    uint32_t lights_pgram;          /* every light a parallelogram with one colour at its four corners */
+    uint32_t lights_grid;           /* ... that also shares light 0's edges */
+    uint32_t lights_regular;        /* ... laid out as regularLightGrid does, ny a power of two */
+    uint32_t grid_ny_log2;          /* log2(ny) of a regular grid, else 0 */
+    float    light_scale;           /* num_lights when it is a power of two (RIS weights pdf * L), else 0 (pdf / (1 / L)) */
+    uint32_t reserved;
+};
+restir_status restir_scene_info(restir_ctx* ctx, struct restir_scene_info* out);
+
 /* ---- timing ----------------------------------------------------------------------------------------- */
 /* When enabled, every kernel of restir_render / restir_stage_* is bracketed by HIP events on the
  * context's stream; restir_timings returns the accumulated milliseconds and launch counts per kernel. */

@@ -119,6 +119,14 @@ class Tile(C.Structure):
                 ("gx0", C.c_uint32), ("gy0", C.c_uint32), ("gwidth", C.c_uint32), ("gheight", C.c_uint32)]
 
 
+class SceneInfo(C.Structure):
+    """struct restir_scene_info: what restir_set_scene derived from the uploaded scene."""
+    _fields_ = [("num_nodes", C.c_uint32), ("num_tris", C.c_uint32), ("bvh_lds_bytes", C.c_uint64),
+                ("num_lights", C.c_uint32), ("light_types", C.c_uint32), ("lights_pgram", C.c_uint32),
+                ("lights_grid", C.c_uint32), ("lights_regular", C.c_uint32), ("grid_ny_log2", C.c_uint32),
+                ("light_scale", C.c_float), ("reserved", C.c_uint32)]
+
+
 RESTIR_MAX_TILES_X = 16
 RESTIR_MAX_TILES_Y = 16
 
@@ -149,6 +157,7 @@ class TileLayout(C.Structure):
 
 assert C.sizeof(HaloOp) == 40 and C.sizeof(HaloEvent) == 32
 assert C.sizeof(TileLayout) == 4 * (4 + 17 + 16 * 17)
+assert C.sizeof(SceneInfo) == 48
 assert C.sizeof(Light) == 88
 assert C.sizeof(Material) == 36
 assert C.sizeof(Mesh) == 80 and C.sizeof(Texture) == 16
@@ -257,6 +266,7 @@ SIGNATURES = {
                                            _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "restir_background_pixels": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "restir_gbuf_reuses": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "restir_scene_info": (C.c_int, [_P, C.POINTER(SceneInfo)]),
     "restir_enable_timing": (C.c_int, [_P, C.c_int]),
     "restir_set_tuning": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "restir_timings": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),

@@ -2182,6 +2182,25 @@ restir_status restir_gbuf_reuses(restir_ctx* c, uint64_t* out_frames) {
     return RESTIR_OK;
 }
 
+restir_status restir_scene_info(restir_ctx* c, struct restir_scene_info* out) {
+    if (!c || !out) return fail(RESTIR_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_scene_info before restir_set_scene");
+    const SceneDev& s = c->sdev;
+    *out = {};
+    out->num_nodes = s.num_nodes;
+    out->num_tris = s.num_tris;
+    out->bvh_lds_bytes = bvh_lds_bytes(s);
+    out->num_lights = s.num_lights;
+    out->light_types = s.light_types;
+    out->lights_pgram = s.lights_pgram;
+    out->lights_grid = s.lights_grid;
+    out->lights_regular = s.lights_regular;
+    out->grid_ny_log2 = s.grid_ny_log2;
+    out->light_scale = s.light_scale;
+    return RESTIR_OK;
+}
+
 restir_status restir_measure_read_bandwidth(restir_ctx* c, uint64_t bytes, uint32_t iters, double* out_gbps) {
     if (!c || !out_gbps || iters == 0 || bytes < (1u << 20)) return fail(RESTIR_ERR_INVALID, "bad argument");
     std::lock_guard<std::mutex> lk(c->mu);

@@ -77,6 +77,13 @@ class Renderer:
               "restir_set_scene_textured")
         self._scene_keep = (meshes, lights, keep, texs, tkeep)
 
+    def scene_info(self) -> _abi.SceneInfo:
+        """restir_scene_info: what set_scene derived from the scene -- BVH size and LDS bytes, the light types present,
+        the compact light-table forms it qualifies for, light_scale.  Runs no kernel."""
+        info = _abi.SceneInfo()
+        check(self.lib, self.lib.restir_scene_info(self.ctx, C.byref(info)), "restir_scene_info")
+        return info
+
     def set_seed(self, seed: int = _abi.RESTIR_DEFAULT_SEED, frame: int = 0) -> None:
         check(self.lib, self.lib.restir_set_seed(self.ctx, seed, frame), "restir_set_seed")
 

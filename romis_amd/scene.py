@@ -213,9 +213,11 @@ def _keyed_colour(i: int, seed: int = 0x5EED0001) -> list:
     return out
 
 
-def cornell_ceiling_grid(n: int) -> Scene:
+def cornell_ceiling_grid(n) -> Scene:
     """C4/C5: normalised Cornell box + n x n parallelogram lights under the ceiling covering
-    90% of the ceiling AABB, free space 0.3, y = ceiling - 0.01, per-light colours ~ U[0.2, 1]^3."""
+    90% of the ceiling AABB, free space 0.3, y = ceiling - 0.01, per-light colours ~ U[0.2, 1]^3.  n = (nx, ny): a
+    grid that is not square (light i at column i // ny, row i % ny, as regularLightGrid orders them)."""
+    nx, ny = (n, n) if isinstance(n, int) else n
     s = load_prebuilt("CornellBoxParallelogramLight")
     # the ceiling is the sub-mesh whose lowest vertex is highest
     ceiling = max(s.meshes, key=lambda m: float(np.min(m.positions[:, 1])))
@@ -225,12 +227,12 @@ def cornell_ceiling_grid(n: int) -> Scene:
     start[1] = f32(lo[1] - f32(0.01))
     e01 = np.array([ext[0] * f32(0.9), 0, 0], dtype=f32)
     e02 = np.array([0, 0, ext[2] * f32(0.9)], dtype=f32)
-    lights = regular_light_grid(start, (n, n), e01, e02, (1.0, 1.0, 1.0), 0.3)
+    lights = regular_light_grid(start, (nx, ny), e01, e02, (1.0, 1.0, 1.0), 0.3)
     for i, l in enumerate(lights):
         col = _keyed_colour(i)
         for c in ("c0", "c1", "c2", "c3"):
             getattr(l, c)[:] = col
-    return Scene(s.meshes, lights, f"cornell_{n}x{n}")
+    return Scene(s.meshes, lights, f"cornell_{nx}x{ny}")
 
 
 def bench_scene(name: str) -> Scene:

@@ -86,6 +86,7 @@ def test_context_calls_fail_cleanly_on_null(abi_lib):
     assert abi_lib.restir_set_seed(None, 1, 2) == 1
     assert abi_lib.restir_set_renders_dir(None, b"/tmp") == 1
     assert abi_lib.restir_synchronize(None) == 1
+    assert abi_lib.restir_scene_info(None, C.byref(_abi.SceneInfo())) == 1
     assert abi_lib.restir_render(None, None, None, 1, 1, None, None, None, None) == 1
 
 
