@@ -540,7 +540,8 @@ struct restir_scene_info {
     uint32_t lights_regular;        /* ... laid out as regularLightGrid does, ny a power of two */
     uint32_t grid_ny_log2;          /* log2(ny) of a regular grid, else 0 */
     float    light_scale;           /* num_lights when it is a power of two (RIS weights pdf * L), else 0 (pdf / (1 / L)) */
-    uint32_t reserved;
+    uint32_t nodes_q_ok;            /* 1: the shadow rays' 16-byte quantized nodes exist (< 65,536 nodes, leaves of < 16
+                                     * triangles within the first 4,096); 0: tuning "final.qbvh" falls back to the float nodes */
 };
 restir_status restir_scene_info(restir_ctx* ctx, struct restir_scene_info* out);
 

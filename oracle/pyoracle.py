@@ -59,6 +59,8 @@ def lib() -> C.CDLL:
             "or_expf_n": (None, [C.c_void_p, C.c_void_p, C.c_size_t]),
             "or_camera_derive": (None, [C.POINTER(_abi.Camera), C.POINTER(_abi.CameraFrame)]),
             "or_target_pdf": (C.c_float, [P, C.POINTER(_abi.Features), FP, FP, FP, FP, FP]),
+            "or_visible": (None, [P, FP, FP, u32, C.POINTER(C.c_uint8)]),
+            "or_primary_ties": (None, [P, C.POINTER(_abi.CameraFrame), u32, u32, UP, FP]),
             "or_primary": (None, [P, C.POINTER(_abi.CameraFrame), u32, u32, Rect, Rect, FP, FP]),
             "or_ris": (None, [P, C.POINTER(_abi.Features), u32, FP, u32, u32, Rect, Rect, FP, FP, FP, FP, FP]),
             "or_temporal": (None, [P, C.POINTER(_abi.Features), u32, FP, u32, u32, Rect, Rect, FP, FP, FP, FP,
@@ -144,6 +146,25 @@ def gbuffer(osc: OracleScene, cam: _abi.Camera, W: int, H: int, view: Rect | Non
     if osc.num_textures:
         osc.bind_uv(uv)
     return n_t, p_mat
+
+
+def visible(osc: OracleScene, P: np.ndarray, y: np.ndarray) -> np.ndarray:
+    """visible() (testVisibilityLightSample) per ray: P, y [n][3] float32 -> [n] bool."""
+    P = np.ascontiguousarray(P, np.float32)
+    y = np.ascontiguousarray(y, np.float32)
+    assert P.shape == y.shape and P.ndim == 2 and P.shape[1] == 3
+    out = np.zeros(P.shape[0], np.uint8)
+    lib().or_visible(osc.handle, fp(P), fp(y), P.shape[0], out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return out.astype(bool)
+
+
+def primary_ties(osc: OracleScene, cam: _abi.Camera, W: int, H: int):
+    """(ties [H*W] uint32, dirs [H*W][3]): per pixel the number of triangles that attain the closest hit's t (0 on a
+    miss), and the primary ray directions."""
+    ties = np.zeros(W * H, np.uint32)
+    dirs = np.zeros((W * H, 3), np.float32)
+    lib().or_primary_ties(osc.handle, C.byref(camera_frame(cam)), W, H, ties.ctypes.data_as(UP), fp(dirs))
+    return ties, dirs
 
 
 def acquire_texel(osc: OracleScene, texture: int, tc) -> np.ndarray:

@@ -242,6 +242,11 @@ static int visible(const or_scene* s, v3 P, v3 y) {
     return !any_hit(s, P2, dir, tfar);
 }
 
+/* visible() per ray, for tests that design their shadow rays: out[i] = 1 when y[i] is visible from P[i]. */
+void or_visible(const or_scene* s, const float* P, const float* y, uint32_t n, uint8_t* out) {
+    for (uint32_t i = 0; i < n; i++) out[i] = (uint8_t)visible(s, ld3(&P[3 * i]), ld3(&y[3 * i]));
+}
+
 /* ------------------------------------------------------------------------------------------------------ */
 /* Camera (trackball.cpp:20-29 ctor, :75-78 position, :105-114 generateRay; glm::quat(euler) type_quat.inl:208-217) */
 void or_camera_derive(const restir_camera* cam, restir_camera_frame* out) {
@@ -308,6 +313,27 @@ void or_primary_uv(const or_scene* s, const restir_camera_frame* cam, uint32_t W
 void or_primary(const or_scene* s, const restir_camera_frame* cam, uint32_t W, uint32_t H, or_rect view,
                 or_rect rect, float* n_t, float* p_mat) {
     or_primary_uv(s, cam, W, H, view, rect, n_t, p_mat, NULL);
+}
+
+/* Per pixel of the whole W x H image (index y * W + x) the number of triangles whose tri_hit attains closest_hit's t
+ * (0 on a miss, 1 for a plain hit, more where the lowest-index rule decides); dirs (nullable): the ray directions. */
+void or_primary_ties(const or_scene* s, const restir_camera_frame* cam, uint32_t W, uint32_t H, uint32_t* ties,
+                     float* dirs) {
+    v3 o = ld3(cam->origin);
+    for (uint32_t y = 0; y < H; y++)
+        for (uint32_t x = 0; x < W; x++) {
+            size_t p = (size_t)y * W + x;
+            v3 d = camera_dir(cam, x, y, W, H);
+            float t = FLT_MAX, u, v;
+            uint32_t tri = 0, n = 0;
+            if (closest_hit(s, o, d, &t, &u, &v, &tri))
+                for (uint32_t i = 0; i < s->num_tris; i++) {
+                    float ti, ui, vi;
+                    n += tri_hit(s, i, o, d, FLT_MAX, &ti, &ui, &vi) && ti == t;
+                }
+            ties[p] = n;
+            if (dirs) st3(&dirs[3 * p], d);
+        }
 }
 
 /* acquireTexel (texture.cpp:4-9): size_t discreteX = texCoord.x * (width - 1) -- the float product truncated

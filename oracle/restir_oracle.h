@@ -59,6 +59,13 @@ void  or_camera_derive(const restir_camera* cam, restir_camera_frame* out);
 float or_target_pdf(const or_scene* s, const restir_features* f, const float origin[3],
                     const float n_t[4], const float p_mat[4], const float lpos[3], const float lcol[3]);
 
+/* For tests that design rays: out[i] = visible(P[i], y[i]) (testVisibilityLightSample) for n rays of 3 floats each;
+ * per pixel (y * W + x) the number of triangles that attain the closest hit's t, and (dirs nullable) the primary ray
+ * directions.  Both call the routines the passes call. */
+void or_visible(const or_scene* s, const float* P, const float* y, uint32_t n, uint8_t* out);
+void or_primary_ties(const or_scene* s, const restir_camera_frame* cam, uint32_t W, uint32_t H, uint32_t* ties,
+                     float* dirs);
+
 /* Passes.  All grids cover `view` (row-major, index (y - view.y0) * view.w + (x - view.x0)); reservoir
  * planes are [N][view pixels]; each pass writes only the pixels of `rect` (a sub-rectangle of view). */
 void or_primary(const or_scene* s, const restir_camera_frame* cam, uint32_t W, uint32_t H, or_rect view,

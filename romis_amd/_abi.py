@@ -124,7 +124,7 @@ class SceneInfo(C.Structure):
     _fields_ = [("num_nodes", C.c_uint32), ("num_tris", C.c_uint32), ("bvh_lds_bytes", C.c_uint64),
                 ("num_lights", C.c_uint32), ("light_types", C.c_uint32), ("lights_pgram", C.c_uint32),
                 ("lights_grid", C.c_uint32), ("lights_regular", C.c_uint32), ("grid_ny_log2", C.c_uint32),
-                ("light_scale", C.c_float), ("reserved", C.c_uint32)]
+                ("light_scale", C.c_float), ("nodes_q_ok", C.c_uint32)]
 
 
 RESTIR_MAX_TILES_X = 16

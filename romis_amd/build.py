@@ -63,11 +63,14 @@ def _stale(target: str, deps: list[str]) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _deps(src: str) -> list[str]:
+    return [os.path.join(CSRC, src)] + [os.path.join(CSRC, h) for h in HEADERS] + \
+        [os.path.join(ROOT, "include", "restir_c.h"), __file__]
+
+
 def _compile(src: str, extra: list[str], force: bool) -> str:
     obj = os.path.join(OUT, os.path.basename(src) + ".o")
-    deps = [os.path.join(CSRC, src)] + [os.path.join(CSRC, h) for h in HEADERS] + \
-        [os.path.join(ROOT, "include", "restir_c.h"), __file__]
-    if force or _stale(obj, deps):
+    if force or _stale(obj, _deps(src)):
         cmd = [HIPCC] + COMMON + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
         subprocess.check_call(cmd)
     return obj
@@ -75,17 +78,20 @@ def _compile(src: str, extra: list[str], force: bool) -> str:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OUT, exist_ok=True)
-    with cf.ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
-        objs = list(ex.map(lambda s: _compile(s[0], s[1], force), SOURCES))
-    if force or _stale(LIB, objs):
-        cmd = [HIPCC, "-shared", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-o", LIB] + objs
-        subprocess.check_call(cmd)
+    # a library newer than every source stands even where its object files are gone (a tree copied without them)
+    if force or _stale(LIB, [d for s in SOURCES for d in _deps(s[0])]):
+        with cf.ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+            objs = list(ex.map(lambda s: _compile(s[0], s[1], force), SOURCES))
+        if force or _stale(LIB, objs):
+            cmd = [HIPCC, "-shared", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-o", LIB] + objs
+            subprocess.check_call(cmd)
     tool = os.path.join(OUT, "tools", "fastmath_check")
     src = os.path.join(ROOT, "tests", "hip", "fastmath_check.hip")
     if os.path.exists(src) and (force or _stale(tool, [src, os.path.join(CSRC, "device_math.h"), __file__])):
         os.makedirs(os.path.dirname(tool), exist_ok=True)
         subprocess.check_call([HIPCC] + COMMON + DEVICE + ["-x", "hip", src, "-o", tool])
     build_route_check(force)
+    build_bvh_check(force)
     if verbose:
         print(LIB)
     return LIB
@@ -102,6 +108,19 @@ def build_route_check(force: bool = False) -> str:
         rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))), "include")
         subprocess.check_call([HIPCC, "-x", "c++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__",
                                f"-I{rocm_include}", f"-I{CSRC}", f"-I{os.path.dirname(srcs[0])}", srcs[0], "-o", tool])
+    return tool
+
+
+def build_bvh_check(force: bool = False) -> str:
+    """tools/bvh_check: tests/cpp/bvh_check.cpp over csrc/bvh.cpp with the host compiler -- the BVH's invariants and the
+    ray walks' pruning against brute force (tests/test_bvh_invariants.py); no device code."""
+    tool = os.path.join(OUT, "tools", "bvh_check")
+    src = os.path.join(ROOT, "tests", "cpp", "bvh_check.cpp")
+    deps = [src, os.path.join(CSRC, "bvh.cpp"), os.path.join(CSRC, "bvh.h"), __file__]
+    if os.path.exists(src) and (force or _stale(tool, deps)):
+        os.makedirs(os.path.dirname(tool), exist_ok=True)
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off", "-pthread", f"-I{CSRC}",
+                               src, os.path.join(CSRC, "bvh.cpp"), "-o", tool])
     return tool
 
 

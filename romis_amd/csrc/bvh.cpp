@@ -170,4 +170,49 @@ FlatBvh build_bvh(const std::vector<BvhTriangle>& tris, uint32_t max_leaf) {
     return out;
 }
 
+QuantizedNodes quantize_nodes(const FlatBvh& bvh) {
+    QuantizedNodes out;
+    const std::vector<float>& nodes = bvh.nodes;
+    std::vector<uint32_t>& nq = out.words;
+    float* q_lo = out.lo;
+    float* q_s = out.s;
+    bool q_ok = bvh.num_nodes > 0 && bvh.num_nodes < 65536u;
+    for (uint32_t i = 0; q_ok && i < bvh.num_nodes; i++) {
+        const uint32_t leaf = f2u(nodes[8 * i + 7]);
+        q_ok = leaf == 0u || ((leaf >> 24) < 16u && (leaf & 0xFFFFFFu) + (leaf >> 24) <= 4096u);
+    }
+    if (q_ok) {
+        for (int a = 0; a < 3; a++) {
+            const double lo = nodes[a], hi = nodes[4 + a];   // the root's padded box
+            q_lo[a] = (float)lo;
+            if ((double)q_lo[a] > lo) q_lo[a] = std::nextafter(q_lo[a], -INFINITY);
+            q_s[a] = (float)std::max((hi - (double)q_lo[a]) / 65532.0, 1e-30);
+            q_ok = q_ok && std::isfinite(q_lo[a]) && std::isfinite(q_s[a]);
+        }
+    }
+    if (q_ok) {
+        nq.assign(4 * (size_t)bvh.num_nodes, 0u);
+        for (uint32_t i = 0; i < bvh.num_nodes && q_ok; i++) {
+            uint32_t q[6];
+            for (int a = 0; a < 3; a++) {
+                const double lo = nodes[8 * i + a], hi = nodes[8 * i + 4 + a];
+                const double ql = std::floor((lo - (double)q_lo[a]) / (double)q_s[a]);
+                const double qh = std::ceil((hi - (double)q_lo[a]) / (double)q_s[a]);
+                q_ok = q_ok && ql >= -1.0 && qh <= 65535.0;
+                q[a] = (uint32_t)std::max(ql, 0.0);
+                q[3 + a] = (uint32_t)std::min(std::max(qh, 0.0), 65535.0);
+            }
+            const uint32_t miss = f2u(nodes[8 * i + 3]), leaf = f2u(nodes[8 * i + 7]);
+            nq[4 * i + 0] = q[0] | (q[1] << 16);
+            nq[4 * i + 1] = q[2] | (q[3] << 16);
+            nq[4 * i + 2] = q[4] | (q[5] << 16);
+            // miss link (16 bits: bvh.num_nodes < 65536), first triangle (12 bits), count (4 bits; 0 = inner node)
+            nq[4 * i + 3] = std::min(miss, 65535u) | ((leaf & 0xFFFu) << 16) | ((leaf >> 24) << 28);
+        }
+    }
+    if (!q_ok) nq.assign(4, 0u);
+    out.ok = q_ok;
+    return out;
+}
+
 }  // namespace romis

@@ -24,4 +24,17 @@ struct FlatBvh {
 // Boxes are padded by `pad` in every direction so the device slab test is conservative.
 FlatBvh build_bvh(const std::vector<BvhTriangle>& tris, uint32_t max_leaf = 4);
 
+// The shadow rays' 16-byte nodes (SceneDev::nodes_q, kernels_common.h occluded_q): 4 words per node, six 16-bit bounds
+// (lo.x | lo.y << 16, lo.z | hi.x << 16, hi.y | hi.z << 16) on the grid lo + q * s over the root box, then
+// miss link | first triangle << 16 | count << 28 (count 0: inner node).
+struct QuantizedNodes {
+    std::vector<uint32_t> words;   // 4 per node; 4 zero words when !ok
+    float lo[3] = {0.0f, 0.0f, 0.0f}, s[3] = {1.0f, 1.0f, 1.0f};
+    bool ok = false;               // < 65,536 nodes, every leaf < 16 triangles ending within the first 4,096, a finite grid
+};
+
+// Snaps each padded box of `bvh` outward to the 16-bit grid, so the quantized box contains the float one: a test against
+// it accepts every box the float test accepts (and a few more), and any-hit decides by the exact triangle tests alone.
+QuantizedNodes quantize_nodes(const FlatBvh& bvh);
+
 }  // namespace romis

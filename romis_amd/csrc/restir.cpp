@@ -1239,46 +1239,12 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
     if (n0.empty()) { n0.assign(4, 0.0f); n1.assign(4, 0.0f); n2.assign(4, 0.0f); }
     std::vector<float> nodes = bvh.nodes;
     if (nodes.empty()) nodes.assign(8, 0.0f);
-    // The shadow rays' 16-byte nodes (SceneDev::nodes_q, kernels_common.h occluded_q): each padded box snapped outward to
-    // a 16-bit grid over the root box, so the quantized box contains the float one -- a test against it accepts every
-    // box the float test accepts (and a few more), and any-hit decides by the exact triangle tests alone, in any order.
-    std::vector<uint32_t> nq;
-    float q_lo[3] = {0.0f, 0.0f, 0.0f}, q_s[3] = {1.0f, 1.0f, 1.0f};
-    bool q_ok = bvh.num_nodes > 0 && bvh.num_nodes < 65536u;
-    for (uint32_t i = 0; q_ok && i < bvh.num_nodes; i++) {
-        const uint32_t leaf = f2u(nodes[8 * i + 7]);
-        q_ok = leaf == 0u || ((leaf >> 24) < 16u && (leaf & 0xFFFFFFu) + (leaf >> 24) <= 4096u);
-    }
-    if (q_ok) {
-        for (int a = 0; a < 3; a++) {
-            const double lo = nodes[a], hi = nodes[4 + a];   // the root's padded box
-            q_lo[a] = (float)lo;
-            if ((double)q_lo[a] > lo) q_lo[a] = std::nextafter(q_lo[a], -INFINITY);
-            q_s[a] = (float)std::max((hi - (double)q_lo[a]) / 65532.0, 1e-30);
-            q_ok = q_ok && std::isfinite(q_lo[a]) && std::isfinite(q_s[a]);
-        }
-    }
-    if (q_ok) {
-        nq.assign(4 * (size_t)bvh.num_nodes, 0u);
-        for (uint32_t i = 0; i < bvh.num_nodes && q_ok; i++) {
-            uint32_t q[6];
-            for (int a = 0; a < 3; a++) {
-                const double lo = nodes[8 * i + a], hi = nodes[8 * i + 4 + a];
-                const double ql = std::floor((lo - (double)q_lo[a]) / (double)q_s[a]);
-                const double qh = std::ceil((hi - (double)q_lo[a]) / (double)q_s[a]);
-                q_ok = q_ok && ql >= -1.0 && qh <= 65535.0;
-                q[a] = (uint32_t)std::max(ql, 0.0);
-                q[3 + a] = (uint32_t)std::min(std::max(qh, 0.0), 65535.0);
-            }
-            const uint32_t miss = f2u(nodes[8 * i + 3]), leaf = f2u(nodes[8 * i + 7]);
-            nq[4 * i + 0] = q[0] | (q[1] << 16);
-            nq[4 * i + 1] = q[2] | (q[3] << 16);
-            nq[4 * i + 2] = q[4] | (q[5] << 16);
-            // miss link (16 bits: bvh.num_nodes < 65536), first triangle (12 bits), count (4 bits; 0 = inner node)
-            nq[4 * i + 3] = std::min(miss, 65535u) | ((leaf & 0xFFFu) << 16) | ((leaf >> 24) << 28);
-        }
-    }
-    if (!q_ok) nq.assign(4, 0u);
+    // the shadow rays' 16-byte nodes (bvh.h quantize_nodes)
+    const QuantizedNodes qn = quantize_nodes(bvh);
+    const std::vector<uint32_t>& nq = qn.words;
+    const float* q_lo = qn.lo;
+    const float* q_s = qn.s;
+    const bool q_ok = qn.ok;
 
     HIP_TRY(hipStreamSynchronize(c->stream));   // previous frames (either slot) may still read the old scene
     ST_TRY(c->nodes.upload(nodes.data(), nodes.size() * 4, c->stream));
@@ -2198,6 +2164,7 @@ restir_status restir_scene_info(restir_ctx* c, struct restir_scene_info* out) {
     out->lights_regular = s.lights_regular;
     out->grid_ny_log2 = s.grid_ny_log2;
     out->light_scale = s.light_scale;
+    out->nodes_q_ok = s.nodes_q_ok;
     return RESTIR_OK;
 }
 

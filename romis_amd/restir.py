@@ -79,7 +79,8 @@ class Renderer:
 
     def scene_info(self) -> _abi.SceneInfo:
         """restir_scene_info: what set_scene derived from the scene -- BVH size and LDS bytes, the light types present,
-        the compact light-table forms it qualifies for, light_scale.  Runs no kernel."""
+        the compact light-table forms it qualifies for, light_scale, nodes_q_ok (the shadow rays' quantized nodes
+        exist).  Runs no kernel."""
         info = _abi.SceneInfo()
         check(self.lib, self.lib.restir_scene_info(self.ctx, C.byref(info)), "restir_scene_info")
         return info

@@ -82,6 +82,18 @@ def test_features_default_matches_reference_struct(abi_lib):
     assert f.spatial_resampling_passes == 2 and f.temporal_clamp_m == 20 and abs(f.exposure - 1.5) < 1e-7
 
 
+def test_scene_info_binding_follows_the_header():
+    """struct restir_scene_info: the binding names the header's fields in the header's order (the last one nodes_q_ok,
+    which took the reserved word's place), 48 bytes as before."""
+    with open(os.path.join(ROOT, "include", "restir_c.h")) as fh:
+        body = re.search(r"struct restir_scene_info \{(.*?)\n\};", fh.read(), flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [n for decl in re.findall(r"(?:uint32_t|uint64_t|float)\s+([^;]+);", body) for n in re.split(r"\s*,\s*", decl.strip())]
+    assert names == [n for n, _ in _abi.SceneInfo._fields_]
+    assert names[-1] == "nodes_q_ok" and "reserved" not in names
+    assert C.sizeof(_abi.SceneInfo) == 48 and _abi.SceneInfo.nodes_q_ok.offset == 44
+
+
 def test_context_calls_fail_cleanly_on_null(abi_lib):
     assert abi_lib.restir_set_seed(None, 1, 2) == 1
     assert abi_lib.restir_set_renders_dir(None, b"/tmp") == 1

@@ -48,7 +48,7 @@ NIGHT, CORNELL = "nightclub_128pt", "cornell_1024"
 
 KNOB_DEFAULTS = {"spatial.th": 0, "spatial.gather": 1, "spatial.handles": 1, "spatial.n2h": 1, "final.fuse": 1,
                  "primary.lds": 1, "final.lds": 1, "fuse.primary_ris": 1, "ris.compact": 1, "ris.lds": 1,
-                 "bvh.max_leaf": 2}
+                 "bvh.max_leaf": 2, "primary.tl": 1, "final.qbvh": 2, "final.sort": 1}
 
 
 @pytest.fixture(scope="module")
@@ -145,7 +145,9 @@ def shape_scene(name):
 
 def camera(name, cam, w, h):
     """cam: "framed" (cornell_framed_camera), "toml" (cornell_camera), None (the scene's own: the nightclub's for the
-    nightclub meshes)."""
+    nightclub meshes), or (fov_deg, dist, look_at, rot_deg) for scene.make_camera."""
+    if isinstance(cam, tuple):
+        return scene.make_camera(*cam, w, h)
     if cam == "framed":
         return scene.cornell_framed_camera(w, h)
     if cam == "toml":
