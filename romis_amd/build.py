@@ -40,7 +40,7 @@ SOURCES = [
     ("screen.cpp", ["-x", "c++"]),
 ]
 HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
-           "route.h"]
+           "route.h", "ris_members.h"]
 
 
 def source_hash() -> str:
@@ -102,7 +102,7 @@ def build_route_check(force: bool = False) -> str:
     (tests/test_launch_routes.py); plain C++ over the headers, no device code."""
     tool = os.path.join(OUT, "tools", "route_check")
     srcs = [os.path.join(ROOT, "tests", "cpp", f) for f in ("route_check.cpp", "route_rows.h")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("route.h", "launch_shape.h", "restir_types.h")] + [__file__]
+    deps = srcs + [os.path.join(CSRC, h) for h in ("route.h", "ris_members.h", "launch_shape.h", "restir_types.h")] + [__file__]
     if os.path.exists(srcs[0]) and (force or _stale(tool, deps)):
         os.makedirs(os.path.dirname(tool), exist_ok=True)
         rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))), "include")

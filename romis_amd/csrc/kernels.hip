@@ -14,6 +14,7 @@
 // read with 16-byte coalesced loads.  Visibility uses a stackless threaded BVH (no scratch stack) that the
 // ray kernels stage once per (persistent) workgroup into LDS; the light table is staged into LDS for RIS.
 #include "kernels_common.h"
+#include "ris_members.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // genPrimaryRayHits for pixel (x, y) at view index p: writes and returns the G-buffer records (n_t, p_mat)
@@ -590,76 +591,37 @@ __device__ __forceinline__ void primary_ris_body(const SceneDev& s, const Region
 #endif
 #define ROMIS_RIS_ATTR __attribute__((amdgpu_waves_per_eu(ROMIS_RIS_WPE)))
 #define ROMIS_RIS1_ATTR __attribute__((amdgpu_waves_per_eu(ROMIS_RIS1_WPE)))
-#define ROMIS_RIS_KERNEL_LT(NT, LDS, LT, NAME, ATTR)                                                                  \
-    extern "C" __global__ __launch_bounds__(256) ATTR void NAME(SceneDev s, Region rg, FeaturesDev f, uint32_t key, float ox, \
-                                                          float oy, float oz, const float4* n_t, const float4* p_mat,   \
-                                                          float4* ra, float4* rb, float2* rdbg, float* rp) {           \
-        ris_body<NT, LDS, LT>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, ra, rb, rdbg, rp);                             \
+#define ROMIS_RIS_CAP_0   // a member's cap by its N (0: the any-N kernel, uncapped)
+#define ROMIS_RIS_CAP_1 ROMIS_RIS1_ATTR
+#define ROMIS_RIS_CAP_2 ROMIS_RIS_ATTR
+#define ROMIS_RIS_KERNEL_CAP(P, NT, LDS, LT, SUFFIX, ATTR)                                                                \
+    extern "C" __global__ __launch_bounds__(256) ATTR void P##SUFFIX(SceneDev s, Region rg, FeaturesDev f, uint32_t key,  \
+        float ox, float oy, float oz, const float4* n_t, const float4* p_mat, float4* ra, float4* rb, float2* rdbg,       \
+        float* rp) {                                                                                                      \
+        ris_body<NT, LDS, LT>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, ra, rb, rdbg, rp);                               \
     }
-#define ROMIS_RIS_KERNEL(NT, LDS, NAME, ATTR) ROMIS_RIS_KERNEL_LT(NT, LDS, kLtGeneral, NAME, ATTR)
-ROMIS_RIS_KERNEL(1, false, k_ris_n1, ROMIS_RIS1_ATTR)
-ROMIS_RIS_KERNEL(2, false, k_ris_n2, ROMIS_RIS_ATTR)
-ROMIS_RIS_KERNEL(0, false, k_ris_n0, )
-ROMIS_RIS_KERNEL(1, true, k_ris_n1_lds, ROMIS_RIS1_ATTR)
-ROMIS_RIS_KERNEL(2, true, k_ris_n2_lds, ROMIS_RIS_ATTR)
-ROMIS_RIS_KERNEL(0, true, k_ris_n0_lds, )
-ROMIS_RIS_KERNEL_LT(1, true, kLtPoint, k_ris_n1_lds_pt, ROMIS_RIS1_ATTR)
-ROMIS_RIS_KERNEL_LT(2, true, kLtPoint, k_ris_n2_lds_pt, ROMIS_RIS_ATTR)
-ROMIS_RIS_KERNEL_LT(1, false, kLtPoint, k_ris_n1_pt, ROMIS_RIS1_ATTR)
-ROMIS_RIS_KERNEL_LT(2, false, kLtPoint, k_ris_n2_pt, ROMIS_RIS_ATTR)
-ROMIS_RIS_KERNEL_LT(1, true, kLtGrid, k_ris_n1_lds_grid, ROMIS_RIS_ATTR)
-ROMIS_RIS_KERNEL_LT(2, true, kLtGrid, k_ris_n2_lds_grid, ROMIS_RIS_ATTR)
-ROMIS_RIS_KERNEL_LT(1, false, kLtGrid, k_ris_n1_grid, ROMIS_RIS1_ATTR)
-ROMIS_RIS_KERNEL_LT(2, false, kLtGrid, k_ris_n2_grid, ROMIS_RIS_ATTR)
-ROMIS_RIS_KERNEL_LT(1, false, kLtRegular, k_ris_n1_reg, ROMIS_RIS1_ATTR)
-ROMIS_RIS_KERNEL_LT(1, true, kLtRegular, k_ris_n1_lds_reg, ROMIS_RIS_ATTR)
-ROMIS_RIS_KERNEL_LT(1, true, kLtPgram, k_ris_n1_lds_pg, ROMIS_RIS_ATTR)
-ROMIS_RIS_KERNEL_LT(2, true, kLtPgram, k_ris_n2_lds_pg, ROMIS_RIS_ATTR)
-ROMIS_RIS_KERNEL_LT(1, false, kLtPgram, k_ris_n1_pg, ROMIS_RIS1_ATTR)
-ROMIS_RIS_KERNEL_LT(2, false, kLtPgram, k_ris_n2_pg, ROMIS_RIS_ATTR)
+// the members (ris_members.h), each under its N's cap; X5: the unfused staged compact forms, which keep 5 waves
+#define ROMIS_RIS_KERNEL(P, NT, LDS, LT, SUFFIX) ROMIS_RIS_KERNEL_CAP(P, NT, LDS, LT, SUFFIX, ROMIS_RIS_CAP_##NT)
+#define ROMIS_RIS_KERNEL5(P, NT, LDS, LT, SUFFIX) ROMIS_RIS_KERNEL_CAP(P, NT, LDS, LT, SUFFIX, ROMIS_RIS_ATTR)
+ROMIS_RIS_MEMBERS(ROMIS_RIS_KERNEL, ROMIS_RIS_KERNEL5, k_ris_)
 
-#define ROMIS_PRIMARY_RIS_KERNEL_LT(NT, LDS, LT, NAME, ATTR)                                                           \
-    extern "C" __global__ __launch_bounds__(256) ATTR void NAME(SceneDev s, Region rg, CameraDev cam, FeaturesDev f,   \
-                                                          uint32_t key, float4* n_t, float4* p_mat, float4* n_t2,      \
-                                                          float4* ra, float4* rb, float2* rdbg, float* rp,             \
-                                                          uint32_t late_ok, uint8_t* tmiss, uint32_t skip_res,         \
-                                                          float* hw, uint32_t* hm, uint32_t res_dead) {                \
+#define ROMIS_PRIMARY_RIS_KERNEL(P, NT, LDS, LT, SUFFIX)                                                                  \
+    extern "C" __global__ __launch_bounds__(256) ROMIS_RIS_CAP_##NT void P##SUFFIX(SceneDev s, Region rg, CameraDev cam,  \
+        FeaturesDev f, uint32_t key, float4* n_t, float4* p_mat, float4* n_t2, float4* ra, float4* rb, float2* rdbg,      \
+        float* rp, uint32_t late_ok, uint8_t* tmiss, uint32_t skip_res, float* hw, uint32_t* hm, uint32_t res_dead) {     \
         primary_ris_body<NT, LDS, LT>(s, rg, cam, f, key, n_t, p_mat, n_t2, ra, rb, rdbg, rp, late_ok, tmiss, skip_res,   \
-                                      hw, hm, res_dead);                                                               \
+                                      hw, hm, res_dead);                                                                  \
     }
-#define ROMIS_PRIMARY_RIS_KERNEL(NT, LDS, NAME, ATTR) ROMIS_PRIMARY_RIS_KERNEL_LT(NT, LDS, kLtGeneral, NAME, ATTR)
 // primary rays + RIS + temporal reuse in one kernel (point lights, the table in LDS): restir_render with a predecessor
-#define ROMIS_PRIMARY_RIS_TEMPORAL_KERNEL(NT, NAME, ATTR)                                                              \
-    extern "C" __global__ __launch_bounds__(256) ATTR void NAME(SceneDev s, Region rg, CameraDev cam, FeaturesDev f,   \
-                                                          uint32_t key, float4* n_t, float4* p_mat, float4* n_t2,      \
-                                                          float4* ra, float4* rb, float2* rdbg, float* rp,             \
-                                                          uint32_t late_ok, TemporalIn tin, float* hw, uint32_t* hm,   \
-                                                          uint32_t res_dead) {                                         \
-        primary_ris_body<NT, true, kLtPoint, true>(s, rg, cam, f, key, n_t, p_mat, n_t2, ra, rb, rdbg, rp, late_ok,    \
-                                                   nullptr, 0u, hw, hm, res_dead, tin);                                \
+#define ROMIS_PRIMARY_RIS_TEMPORAL_KERNEL(P, NT, LDS, LT, SUFFIX)                                                         \
+    extern "C" __global__ __launch_bounds__(256) ROMIS_RIS_CAP_##NT void P##SUFFIX(SceneDev s, Region rg, CameraDev cam,  \
+        FeaturesDev f, uint32_t key, float4* n_t, float4* p_mat, float4* n_t2, float4* ra, float4* rb, float2* rdbg,      \
+        float* rp, uint32_t late_ok, TemporalIn tin, float* hw, uint32_t* hm, uint32_t res_dead) {                        \
+        primary_ris_body<NT, LDS, LT, true>(s, rg, cam, f, key, n_t, p_mat, n_t2, ra, rb, rdbg, rp, late_ok, nullptr, 0u, \
+                                            hw, hm, res_dead, tin);                                                       \
     }
-ROMIS_PRIMARY_RIS_KERNEL(1, true, k_primary_ris_n1_lds, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL(1, false, k_primary_ris_n1, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL(2, true, k_primary_ris_n2_lds, ROMIS_RIS_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL(2, false, k_primary_ris_n2, ROMIS_RIS_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL(0, true, k_primary_ris_n0_lds, )
-ROMIS_PRIMARY_RIS_KERNEL(0, false, k_primary_ris_n0, )
-ROMIS_PRIMARY_RIS_KERNEL_LT(1, true, kLtPoint, k_primary_ris_n1_lds_pt, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(2, true, kLtPoint, k_primary_ris_n2_lds_pt, ROMIS_RIS_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(1, false, kLtPoint, k_primary_ris_n1_pt, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(2, false, kLtPoint, k_primary_ris_n2_pt, ROMIS_RIS_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(1, true, kLtGrid, k_primary_ris_n1_lds_grid, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(2, true, kLtGrid, k_primary_ris_n2_lds_grid, ROMIS_RIS_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(1, false, kLtGrid, k_primary_ris_n1_grid, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(2, false, kLtGrid, k_primary_ris_n2_grid, ROMIS_RIS_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(1, false, kLtRegular, k_primary_ris_n1_reg, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(1, true, kLtRegular, k_primary_ris_n1_lds_reg, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(1, true, kLtPgram, k_primary_ris_n1_lds_pg, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(2, true, kLtPgram, k_primary_ris_n2_lds_pg, ROMIS_RIS_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(1, false, kLtPgram, k_primary_ris_n1_pg, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_KERNEL_LT(2, false, kLtPgram, k_primary_ris_n2_pg, ROMIS_RIS_ATTR)
-ROMIS_PRIMARY_RIS_TEMPORAL_KERNEL(1, k_primary_ris_n1_lds_pt_temporal, ROMIS_RIS1_ATTR)
-ROMIS_PRIMARY_RIS_TEMPORAL_KERNEL(2, k_primary_ris_n2_lds_pt_temporal, ROMIS_RIS_ATTR)
+ROMIS_RIS_MEMBERS(ROMIS_PRIMARY_RIS_KERNEL, ROMIS_PRIMARY_RIS_KERNEL, k_primary_ris_)
+ROMIS_RIS_TEMPORAL_MEMBERS(ROMIS_PRIMARY_RIS_TEMPORAL_KERNEL, k_primary_ris_)
 
 // k_gbuf_ris: the fused kernel's frame over a view whose G-buffer and tile flags an earlier frame of the same context
 // left in memory (restir_render's GbufView: the same scene upload, camera, image size and region -- none of them
@@ -711,48 +673,23 @@ __device__ __forceinline__ void gbuf_ris_body(const SceneDev& s, const Region& r
                                 !(hw && res_dead), tin);
 }
 
-#define ROMIS_GBUF_RIS_KERNEL_LT(NT, LDS, LT, NAME, ATTR)                                                              \
-    extern "C" __global__ __launch_bounds__(256) ATTR void NAME(SceneDev s, Region rg, FeaturesDev f, uint32_t key,    \
-                                                          float ox, float oy, float oz, const float4* n_t,             \
-                                                          const float4* p_mat, float4* ra, float4* rb, float2* rdbg,   \
-                                                          float* rp, const uint8_t* tmiss, uint32_t skip_res,          \
-                                                          float* hw, uint32_t* hm, uint32_t res_dead) {                \
-        gbuf_ris_body<NT, LDS, LT>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, ra, rb, rdbg, rp, tmiss, skip_res, hw,   \
-                                   hm, res_dead);                                                                      \
+#define ROMIS_GBUF_RIS_KERNEL(P, NT, LDS, LT, SUFFIX)                                                                     \
+    extern "C" __global__ __launch_bounds__(256) ROMIS_RIS_CAP_##NT void P##SUFFIX(SceneDev s, Region rg, FeaturesDev f,  \
+        uint32_t key, float ox, float oy, float oz, const float4* n_t, const float4* p_mat, float4* ra, float4* rb,       \
+        float2* rdbg, float* rp, const uint8_t* tmiss, uint32_t skip_res, float* hw, uint32_t* hm, uint32_t res_dead) {   \
+        gbuf_ris_body<NT, LDS, LT>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, ra, rb, rdbg, rp, tmiss, skip_res, hw, hm,  \
+                                   res_dead);                                                                             \
     }
-#define ROMIS_GBUF_RIS_KERNEL(NT, LDS, NAME, ATTR) ROMIS_GBUF_RIS_KERNEL_LT(NT, LDS, kLtGeneral, NAME, ATTR)
-#define ROMIS_GBUF_RIS_TEMPORAL_KERNEL(NT, NAME, ATTR)                                                                 \
-    extern "C" __global__ __launch_bounds__(256) ATTR void NAME(SceneDev s, Region rg, FeaturesDev f, uint32_t key,    \
-                                                          float ox, float oy, float oz, const float4* n_t,             \
-                                                          const float4* p_mat, float4* ra, float4* rb, float2* rdbg,   \
-                                                          float* rp, TemporalIn tin, float* hw, uint32_t* hm,          \
-                                                          uint32_t res_dead) {                                         \
-        gbuf_ris_body<NT, true, kLtPoint, true>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, ra, rb, rdbg, rp, nullptr,  \
-                                                0u, hw, hm, res_dead, tin);                                            \
+#define ROMIS_GBUF_RIS_TEMPORAL_KERNEL(P, NT, LDS, LT, SUFFIX)                                                            \
+    extern "C" __global__ __launch_bounds__(256) ROMIS_RIS_CAP_##NT void P##SUFFIX(SceneDev s, Region rg, FeaturesDev f,  \
+        uint32_t key, float ox, float oy, float oz, const float4* n_t, const float4* p_mat, float4* ra, float4* rb,       \
+        float2* rdbg, float* rp, TemporalIn tin, float* hw, uint32_t* hm, uint32_t res_dead) {                            \
+        gbuf_ris_body<NT, LDS, LT, true>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, ra, rb, rdbg, rp, nullptr, 0u, hw,    \
+                                         hm, res_dead, tin);                                                              \
     }
 // the members of the k_primary_ris family, under its waves-per-SIMD caps
-ROMIS_GBUF_RIS_KERNEL(1, true, k_gbuf_ris_n1_lds, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_KERNEL(1, false, k_gbuf_ris_n1, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_KERNEL(2, true, k_gbuf_ris_n2_lds, ROMIS_RIS_ATTR)
-ROMIS_GBUF_RIS_KERNEL(2, false, k_gbuf_ris_n2, ROMIS_RIS_ATTR)
-ROMIS_GBUF_RIS_KERNEL(0, true, k_gbuf_ris_n0_lds, )
-ROMIS_GBUF_RIS_KERNEL(0, false, k_gbuf_ris_n0, )
-ROMIS_GBUF_RIS_KERNEL_LT(1, true, kLtPoint, k_gbuf_ris_n1_lds_pt, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(2, true, kLtPoint, k_gbuf_ris_n2_lds_pt, ROMIS_RIS_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(1, false, kLtPoint, k_gbuf_ris_n1_pt, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(2, false, kLtPoint, k_gbuf_ris_n2_pt, ROMIS_RIS_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(1, true, kLtGrid, k_gbuf_ris_n1_lds_grid, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(2, true, kLtGrid, k_gbuf_ris_n2_lds_grid, ROMIS_RIS_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(1, false, kLtGrid, k_gbuf_ris_n1_grid, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(2, false, kLtGrid, k_gbuf_ris_n2_grid, ROMIS_RIS_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(1, false, kLtRegular, k_gbuf_ris_n1_reg, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(1, true, kLtRegular, k_gbuf_ris_n1_lds_reg, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(1, true, kLtPgram, k_gbuf_ris_n1_lds_pg, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(2, true, kLtPgram, k_gbuf_ris_n2_lds_pg, ROMIS_RIS_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(1, false, kLtPgram, k_gbuf_ris_n1_pg, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_KERNEL_LT(2, false, kLtPgram, k_gbuf_ris_n2_pg, ROMIS_RIS_ATTR)
-ROMIS_GBUF_RIS_TEMPORAL_KERNEL(1, k_gbuf_ris_n1_lds_pt_temporal, ROMIS_RIS1_ATTR)
-ROMIS_GBUF_RIS_TEMPORAL_KERNEL(2, k_gbuf_ris_n2_lds_pt_temporal, ROMIS_RIS_ATTR)
+ROMIS_RIS_MEMBERS(ROMIS_GBUF_RIS_KERNEL, ROMIS_GBUF_RIS_KERNEL, k_gbuf_ris_)
+ROMIS_RIS_TEMPORAL_MEMBERS(ROMIS_GBUF_RIS_TEMPORAL_KERNEL, k_gbuf_ris_)
 
 // k_temporal: temporalReuse (render_utils.cpp:142-177).  cur = (ca, cb), prev = (pa, pb); writes (oa, ob).
 template <int NT>
@@ -2701,6 +2638,7 @@ extern "C" __global__ __launch_bounds__(256) void k_read_stream(const float4* __
 #include "launch.h"
 #include "launch_events.h"
 
+#include <array>
 #include <cassert>
 
 namespace romis {
@@ -2713,6 +2651,16 @@ void set_launch_events(hipEvent_t start, hipEvent_t stop) {
 bool launch_events_used() { return g_launched; }
 
 namespace {
+// each RIS family's kernels in the order of ris_members.h: ris_member indexes them
+#define ROMIS_RIS_ENTRY(P, N, LDS, LT, SUFFIX) P##SUFFIX,
+const std::array kRisKernels = {ROMIS_RIS_MEMBERS(ROMIS_RIS_ENTRY, ROMIS_RIS_ENTRY, k_ris_)};
+const std::array kPrimaryRisKernels = {ROMIS_RIS_MEMBERS(ROMIS_RIS_ENTRY, ROMIS_RIS_ENTRY, k_primary_ris_)};
+const std::array kGbufRisKernels = {ROMIS_RIS_MEMBERS(ROMIS_RIS_ENTRY, ROMIS_RIS_ENTRY, k_gbuf_ris_)};
+const std::array kPrimaryRisTemporalKernels = {ROMIS_RIS_TEMPORAL_MEMBERS(ROMIS_RIS_ENTRY, k_primary_ris_)};
+const std::array kGbufRisTemporalKernels = {ROMIS_RIS_TEMPORAL_MEMBERS(ROMIS_RIS_ENTRY, k_gbuf_ris_)};
+static_assert(kRisKernels.size() == kRisMembers && kPrimaryRisKernels.size() == kRisMembers &&
+              kGbufRisKernels.size() == kRisMembers && kPrimaryRisTemporalKernels.size() == kRisTemporalMembers &&
+              kGbufRisTemporalKernels.size() == kRisTemporalMembers, "one table entry per row of ris_members.h");
 // a route names a buffer: the caller must have passed it
 template <class T>
 T* named(bool by_route, T* p) {
@@ -2733,16 +2681,12 @@ hipError_t launch_ris(const Route& r, const SceneDev& s, const Region& rg0, cons
                       hipStream_t stream) {
     if (r.kernel == Kernel::kNone) return hipSuccess;
     assert(r.kernel == Kernel::kRis);
-    const bool staged = r.staged, n1 = r.n == 1;
-    auto k = r.lt == kLtRegular ? (staged ? k_ris_n1_lds_reg : k_ris_n1_reg)
-           : r.lt == kLtPoint ? (staged ? (n1 ? k_ris_n1_lds_pt : k_ris_n2_lds_pt) : (n1 ? k_ris_n1_pt : k_ris_n2_pt))
-           : r.lt == kLtGrid ? (staged ? (n1 ? k_ris_n1_lds_grid : k_ris_n2_lds_grid) : (n1 ? k_ris_n1_grid : k_ris_n2_grid))
-           : r.lt == kLtPgram ? (staged ? (n1 ? k_ris_n1_lds_pg : k_ris_n2_lds_pg) : (n1 ? k_ris_n1_pg : k_ris_n2_pg))
-           : staged ? (n1 ? k_ris_n1_lds : (r.n == 2 ? k_ris_n2_lds : k_ris_n0_lds))
-                    : (n1 ? k_ris_n1 : (r.n == 2 ? k_ris_n2 : k_ris_n0));
+    const int m = ris_member(r.n, r.staged, r.lt);
+    assert(m >= 0 && "a member of the RIS families");
+    if (m < 0) return hipErrorInvalidValue;
     const float* o = b.origin;
-    ROMIS_LAUNCH(k, dim3(r.grid), dim3(r.block), r.lds, stream, s, r.region(rg0), f, b.key, o[0], o[1], o[2], b.n_t, b.p_mat,
-                 b.oa, b.ob, named(r.dbg, b.dbg), named(r.rp_out, b.rp_out));
+    ROMIS_LAUNCH(kRisKernels[m], dim3(r.grid), dim3(r.block), r.lds, stream, s, r.region(rg0), f, b.key, o[0], o[1], o[2], b.n_t,
+                 b.p_mat, b.oa, b.ob, named(r.dbg, b.dbg), named(r.rp_out, b.rp_out));
     return hipGetLastError();
 }
 
@@ -2753,51 +2697,36 @@ hipError_t launch_primary_ris(const Route& r, const SceneDev& s, const Region& r
     const Region rg = r.region(rg0);
     float* const hw = named(r.how, b.hout.w);
     uint32_t* const hm = named(r.hom, b.hout.m);
+    const bool temporal = r.kernel == Kernel::kPrimaryRisTemporal || r.kernel == Kernel::kGbufRisTemporal;
+    const int m = ris_member(r.n, r.staged, r.lt, temporal);
+    assert(m >= 0 && "a member of the RIS families");
+    if (m < 0) return hipErrorInvalidValue;
     if (r.kernel == Kernel::kGbufRis || r.kernel == Kernel::kGbufRisTemporal) {
         // the G-buffer and the flags of an earlier frame (route_primary_ris with Ask::gbuf_cached): read, not written
         const float* o = b.origin;
         const float4* const n_t = b.n_t;
         const float4* const p_mat = b.p_mat;
-        if (r.kernel == Kernel::kGbufRisTemporal) {
-            ROMIS_LAUNCH(r.n == 1 ? k_gbuf_ris_n1_lds_pt_temporal : k_gbuf_ris_n2_lds_pt_temporal, dim3(r.grid),
-                         dim3(r.block), r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], n_t, p_mat, b.oa, b.ob,
-                         named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), b.tin, hw, hm, r.res_dead);
+        if (temporal) {
+            ROMIS_LAUNCH(kGbufRisTemporalKernels[m], dim3(r.grid), dim3(r.block), r.lds, stream, s, rg, f, b.key, o[0], o[1],
+                         o[2], n_t, p_mat, b.oa, b.ob, named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), b.tin, hw, hm,
+                         r.res_dead);
             return hipGetLastError();
         }
-        const bool staged = r.staged, n1 = r.n == 1;
-        auto k = r.lt == kLtRegular ? (staged ? k_gbuf_ris_n1_lds_reg : k_gbuf_ris_n1_reg)
-               : r.lt == kLtPoint ? (staged ? (n1 ? k_gbuf_ris_n1_lds_pt : k_gbuf_ris_n2_lds_pt)
-                                            : (n1 ? k_gbuf_ris_n1_pt : k_gbuf_ris_n2_pt))
-               : r.lt == kLtGrid ? (staged ? (n1 ? k_gbuf_ris_n1_lds_grid : k_gbuf_ris_n2_lds_grid)
-                                           : (n1 ? k_gbuf_ris_n1_grid : k_gbuf_ris_n2_grid))
-               : r.lt == kLtPgram ? (staged ? (n1 ? k_gbuf_ris_n1_lds_pg : k_gbuf_ris_n2_lds_pg)
-                                            : (n1 ? k_gbuf_ris_n1_pg : k_gbuf_ris_n2_pg))
-               : staged ? (n1 ? k_gbuf_ris_n1_lds : (r.n == 2 ? k_gbuf_ris_n2_lds : k_gbuf_ris_n0_lds))
-                        : (n1 ? k_gbuf_ris_n1 : (r.n == 2 ? k_gbuf_ris_n2 : k_gbuf_ris_n0));
         const uint8_t* const flags = named(r.flags, b.flags);
-        ROMIS_LAUNCH(k, dim3(r.grid), dim3(r.block), r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], n_t, p_mat, b.oa,
-                     b.ob, named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), flags, r.skip, hw, hm, r.res_dead);
+        ROMIS_LAUNCH(kGbufRisKernels[m], dim3(r.grid), dim3(r.block), r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], n_t,
+                     p_mat, b.oa, b.ob, named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), flags, r.skip, hw, hm, r.res_dead);
         return hipGetLastError();
     }
-    if (r.kernel == Kernel::kPrimaryRisTemporal) {
-        ROMIS_LAUNCH(r.n == 1 ? k_primary_ris_n1_lds_pt_temporal : k_primary_ris_n2_lds_pt_temporal, dim3(r.grid),
-                     dim3(r.block), r.lds, stream, s, rg, *b.cam, f, b.key, b.n_t, b.p_mat, b.n_t2, b.oa, b.ob,
-                     named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), r.mode, b.tin, hw, hm, r.res_dead);
+    if (temporal) {
+        ROMIS_LAUNCH(kPrimaryRisTemporalKernels[m], dim3(r.grid), dim3(r.block), r.lds, stream, s, rg, *b.cam, f, b.key, b.n_t,
+                     b.p_mat, b.n_t2, b.oa, b.ob, named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), r.mode, b.tin, hw, hm,
+                     r.res_dead);
         return hipGetLastError();
     }
     assert(r.kernel == Kernel::kPrimaryRis);
-    const bool staged = r.staged, n1 = r.n == 1;
-    auto k = r.lt == kLtRegular ? (staged ? k_primary_ris_n1_lds_reg : k_primary_ris_n1_reg)
-           : r.lt == kLtPoint ? (staged ? (n1 ? k_primary_ris_n1_lds_pt : k_primary_ris_n2_lds_pt)
-                                        : (n1 ? k_primary_ris_n1_pt : k_primary_ris_n2_pt))
-           : r.lt == kLtGrid ? (staged ? (n1 ? k_primary_ris_n1_lds_grid : k_primary_ris_n2_lds_grid)
-                                       : (n1 ? k_primary_ris_n1_grid : k_primary_ris_n2_grid))
-           : r.lt == kLtPgram ? (staged ? (n1 ? k_primary_ris_n1_lds_pg : k_primary_ris_n2_lds_pg)
-                                        : (n1 ? k_primary_ris_n1_pg : k_primary_ris_n2_pg))
-           : staged ? (n1 ? k_primary_ris_n1_lds : (r.n == 2 ? k_primary_ris_n2_lds : k_primary_ris_n0_lds))
-                    : (n1 ? k_primary_ris_n1 : (r.n == 2 ? k_primary_ris_n2 : k_primary_ris_n0));
-    ROMIS_LAUNCH(k, dim3(r.grid), dim3(r.block), r.lds, stream, s, rg, *b.cam, f, b.key, b.n_t, b.p_mat, b.n_t2, b.oa, b.ob,
-                 named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), r.mode, named(r.flags, b.flags), r.skip, hw, hm, r.res_dead);
+    ROMIS_LAUNCH(kPrimaryRisKernels[m], dim3(r.grid), dim3(r.block), r.lds, stream, s, rg, *b.cam, f, b.key, b.n_t, b.p_mat,
+                 b.n_t2, b.oa, b.ob, named(r.dbg, b.dbg), named(r.rp_out, b.rp_out), r.mode, named(r.flags, b.flags), r.skip, hw,
+                 hm, r.res_dead);
     return hipGetLastError();
 }
 

@@ -11,13 +11,13 @@
 
 namespace romis {
 
-// A kernel family; Route's dbg / th / n / lt / staged / unbiased / vis_kernel select the member.
+// A kernel family; Route's dbg / th / n / lt / staged / unbiased / vis_kernel select the member (RIS: ris_members.h).
 enum class Kernel : uint8_t {
     kNone,                 // an empty rect: nothing to launch
     kPrimary,              // k_primary[_lds]
-    kRis,                  // k_ris_n{N}[_lds][_pt | _grid | _pg | _reg]
-    kPrimaryRis,           // k_primary_ris_n{N}[_lds][_pt | _grid | _pg | _reg]
-    kPrimaryRisTemporal,   // k_primary_ris_n{N}_lds_pt_temporal
+    kRis,                  // k_ris_<member>
+    kPrimaryRis,           // k_primary_ris_<member>
+    kPrimaryRisTemporal,   // k_primary_ris_<temporal member>
     kSpatial,              // k_spatial_n{N}_{biased | unbiased}: any N, K, R and layout
     kSpatial1u,            // k_spatial1u[_vis][_dbg]: N = 1 unbiased, lean
     kSpatial1Ntl,          // k_spatial1_ntl[_t2][_dbg]: N = 1 biased, lean, over the reservoir planes
@@ -30,8 +30,8 @@ enum class Kernel : uint8_t {
     kFinal,                // k_final_n{N}[_lds]
     kFinalSorted,          // k_final_n{1,2}_sorted: one tile per block, the shadow rays binned by target
     kFinalSortedQ,         // k_final_n{1,2}_sorted_q: ... over the 16-byte BVH nodes
-    kGbufRis,              // k_gbuf_ris_n{N}[_lds][_pt | _grid | _pg | _reg]: kPrimaryRis over a cached G-buffer
-    kGbufRisTemporal,      // k_gbuf_ris_n{N}_lds_pt_temporal
+    kGbufRis,              // k_gbuf_ris_<member>: kPrimaryRis over a cached G-buffer
+    kGbufRisTemporal,      // k_gbuf_ris_<temporal member>
 };
 
 // The automatic XCD chunks (spatial.xcd_rows / spatial.xcd_cols left at auto) of a lean spatial kernel

@@ -1,9 +1,11 @@
 // route_check.cpp -- replays tests/golden/launch_routes.txt over the route functions (csrc/route.h): for every row read
 // from stdin it prints the row's inputs, " | ", and what the routes decide, in the golden file's own format.
 // tests/test_launch_routes.py compares the two.  A spatial row gets two fields more: hk=<spatial_handle_kind over the
-// row's region, one pass>/<the kind the row's handles would be>.
+// row's region, one pass>/<the kind the row's handles would be>; a fused primary + RIS row that names a kernel one:
+// gb=<kernel>,<LDS bytes>,<grid>,<block>,<map2d>,<xcd_rows>,<xcd_cols> of the route over a cached G-buffer (Ask::gbuf_cached).
 //
 // Plain host C++ over the header alone (built by romis_amd/build.py as tools/route_check).
+#include "ris_members.h"
 #include "route.h"
 
 #include <iostream>
@@ -21,19 +23,12 @@ enum Ptr : uint32_t {   // the golden file's ptrs bits
     pHow = 1u << 15, pHom = 1u << 16, pRgb = 1u << 17, pPa = 1u << 18, pPb = 1u << 19, pThw = 1u << 20, pThm = 1u << 21,
 };
 
-const char* lt_suffix(int lt) {
-    return lt == kLtPoint ? "_pt" : lt == kLtGrid ? "_grid" : lt == kLtPgram ? "_pg" : lt == kLtRegular ? "_reg" : "";
-}
-
-// the kernel a route names
+// the kernel a route names (the RIS families: ris_members.h)
 std::string kernel_name(const Route& r) {
     const std::string n = std::to_string(r.n), lds = r.staged ? "_lds" : "", dbg = r.dbg ? "_dbg" : "", t2 = r.th == 2 ? "_t2" : "";
     switch (r.kernel) {
     case Kernel::kNone: return "-";
     case Kernel::kPrimary: return "k_primary" + lds;
-    case Kernel::kRis: return "k_ris_n" + n + lds + lt_suffix(r.lt);
-    case Kernel::kPrimaryRis: return "k_primary_ris_n" + n + lds + lt_suffix(r.lt);
-    case Kernel::kPrimaryRisTemporal: return "k_primary_ris_n" + n + "_lds_pt_temporal";
     case Kernel::kSpatial: return "k_spatial_n" + n + (r.unbiased ? "_unbiased" : "_biased");
     case Kernel::kSpatial1u: return std::string("k_spatial1u") + (r.vis_kernel ? "_vis" : "") + dbg;
     case Kernel::kSpatial1Ntl: return "k_spatial1_ntl" + t2 + dbg;
@@ -46,8 +41,8 @@ std::string kernel_name(const Route& r) {
     case Kernel::kFinal: return "k_final_n" + n + lds;
     case Kernel::kFinalSorted: return "k_final_n" + n + "_sorted";
     case Kernel::kFinalSortedQ: return "k_final_n" + n + "_sorted_q";
+    default: return ris_kernel_name(r);
     }
-    return "?";
 }
 
 bool handle_kernel(Kernel k) {
@@ -87,7 +82,7 @@ int main() {
         }
         Route r;
         uint32_t ptrs = pNt | pPm;
-        std::string words;
+        std::string words, cached;
         bool mt = false;
         if (row.stage == "primary") {
             r = route_primary(s, row.rg, tu);
@@ -102,6 +97,12 @@ int main() {
                     (r.how ? pHow : 0) | (r.hom ? pHom : 0);
             if (temporal) ptrs |= pPa | pPb | ((a & kThw) ? pThw | pThm : 0);
             words = std::to_string(r.mode) + (temporal ? "" : "," + std::to_string(r.skip)) + "," + std::to_string(r.res_dead);
+            if (r.ok && r.kernel != Kernel::kNone) {
+                ask.gbuf_cached = true;
+                const Route g = (temporal ? route_primary_ris_temporal : route_primary_ris)(s, row.rg, f, tu, ask);
+                cached = " gb=" + kernel_name(g) + "," + std::to_string(g.lds);
+                for (uint32_t v : {g.grid, g.block, g.map2d, g.xcd_rows, g.xcd_cols}) cached += "," + std::to_string(v);
+            }
         } else if (row.stage == "spatial") {
             r = route_spatial(s, row.rg, f, tu, ask);
             ptrs |= pOa | pOb | (r.res_in ? pIa | pIb : 0) | (r.dbg ? pDbg : 0) | (r.rp_in ? pRpi : 0) | (r.rp_nb ? pRpn : 0) |
@@ -130,7 +131,7 @@ int main() {
             if (r.final_done) std::printf(" fo=%u", r.miss);
         }
         if (row.stage == "spatial") std::printf(" hk=%d/%d", spatial_handle_kind(s, row.rg, f, tu, 1u), kind);
-        if (row.stage == "pris" || row.stage == "prist") std::printf(" ok=%d", r.ok);
+        if (row.stage == "pris" || row.stage == "prist") std::printf(" ok=%d%s", r.ok, cached.c_str());
         std::printf("\n");
     }
     return 0;

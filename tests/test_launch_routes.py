@@ -54,7 +54,7 @@ def test_every_launch_matches(rows):
     for inp, old, new in rows:
         if inp[0] == "pred" or " einval " in old:
             continue
-        new = re.sub(r"( (hk|ok)=\S+)+$", "", new)
+        new = re.sub(r"( (hk|ok|gb)=\S+)+$", "", new)
         assert new == old, " ".join(inp)
         seen.add(old.split()[0])
     assert len(seen) == 84, len(seen)   # the 83 kernels of the five launchers, and "-"
@@ -75,6 +75,34 @@ def test_invalid_value_rows_are_excluded_by_the_frame_decision(rows):
             got, asked = re.search(r" hk=(-?\d+)/(\d)$", new).groups()
             assert got != asked, " ".join(inp)
     assert n > 100
+
+
+def test_cached_gbuffer_route_names_the_fused_member(rows):
+    """Over a cached G-buffer (Ask::gbuf_cached) a fused primary + RIS route names the same member of the k_gbuf_ris
+    family in the same launch shape.  Expected from the golden row alone: its kernel under the other prefix, its grid,
+    block and map=, and its LDS less the BVH's (2 num_nodes + 3 num_tris) float4s -- the rows have no initial-visibility
+    rays, so the cached kernel stages no BVH."""
+    fused, seen, n = set(), set(), 0
+    for inp, old, new in rows:
+        if inp[0] not in ("pris", "prist"):
+            continue
+        where = " ".join(inp)
+        got = re.search(r" gb=(\S+)$", new)
+        o = old.split()
+        if o[4] != "launch":
+            assert not got, where
+            continue
+        n += 1
+        fused.add(o[0])
+        assert o[0].startswith("k_primary_ris_") and got, where
+        nodes, tris, _ = (int(v) for v in inp[2].split(","))
+        map2d, xcd_rows, xcd_cols = re.search(r" map=(\d+),(\d+),(\d+) ", old).groups()
+        want = ["k_gbuf_ris_" + o[0][len("k_primary_ris_"):], str(int(o[3]) - (2 * nodes + 3 * tris) * 16), o[1], o[2], map2d,
+                xcd_rows, xcd_cols]
+        assert got.group(1).split(",") == want, where
+        seen.add(got.group(1).split(",")[0])
+    assert n > 100
+    assert len(fused) == 22 and seen == {"k_gbuf_ris_" + k[len("k_primary_ris_"):] for k in fused}, sorted(seen)
 
 
 def test_predicates_are_reads_of_routes(rows):
