@@ -66,7 +66,9 @@ typedef enum restir_status {
     RESTIR_ERR_HIP         = 2,  /* HIP runtime failure */
     RESTIR_ERR_NO_DEVICE   = 3,  /* no usable gfx950 device */
     RESTIR_ERR_STATE       = 4,  /* call out of order (e.g. render before set_scene) */
-    RESTIR_ERR_UNSUPPORTED = 5,  /* feature combination not implemented (e.g. R-MIS / R-OMIS on a screen tile) */
+    RESTIR_ERR_UNSUPPORTED = 5,  /* feature combination not implemented (e.g. R-OMIS with more than
+                                    RESTIR_ROMIS_MAX_TECHNIQUES techniques, or an R-MIS / R-OMIS screen tile handed to
+                                    restir_render: restir_render_mis_tile renders those) */
     RESTIR_ERR_COMM        = 6   /* RCCL failure */
 } restir_status;
 
@@ -284,7 +286,8 @@ restir_status restir_set_scene_textured(restir_ctx* ctx, const restir_mesh* mesh
 /* renderRayTraced (render.cpp:268-290) by features->ray_trace_mode:
  * RMIS / ROMIS -- renderRMIS / renderROMIS (render.cpp:64-265): primary hits -> neighbour selection grid ->
  * max_iterations_mis x (initial RIS -> per-pixel MIS combination over the pixel's neighbourhood) -> screen.
- * Whole images only (tile NULL or covering the image), no temporal predecessor, *out_next = NULL (the reference
+ * Whole images only here (tile NULL or covering the image; any other tile is RESTIR_ERR_UNSUPPORTED --
+ * restir_render_mis_tile renders screen tiles), no temporal predecessor, *out_next = NULL (the reference
  * returns std::nullopt).  R-OMIS needs k + 1 <= RESTIR_ROMIS_MAX_TECHNIQUES and at least k candidates in every
  * pixel's window (the reference indexes past the neighbourhood otherwise).
  * RESTIR -- renderReSTIR (render.cpp:28-62): primary hits -> initial RIS -> [temporal if prev] -> [spatial x P] ->
@@ -297,6 +300,30 @@ restir_status restir_set_scene_textured(restir_ctx* ctx, const restir_mesh* mesh
 restir_status restir_render(restir_ctx* ctx, const restir_camera* cam, const restir_features* features,
                             uint32_t width, uint32_t height, const restir_tile* tile,
                             const restir_frame* prev, restir_frame** out_next, float* out_rgb);
+
+/* R-MIS / R-OMIS on screen tiles (multi-GPU frames, and frames whose whole-image buffers would not fit; DESIGN.md
+ * §7, §10).  A pixel's neighbourhood lies within spatial_resample_radius r of it, and every neighbour contributes only
+ * its own G-buffer record and its own RIS reservoir of the iteration, both keyed by global pixel: a tile that computes
+ * primary rays and RIS on its owned rectangle grown by r (clipped to the image) reproduces its owned pixels bit for bit,
+ * for any number of iterations, with no exchange between ranks and no state between frames.
+ *
+ * restir_render_mis_tile: renderRMIS / renderROMIS of the owned rectangle of `tile`.  out_rgb (nullable, as
+ * restir_render's): tile->width x tile->height x 3 floats, row 0 = top of the tile.  tile == NULL: the whole image (the
+ * bits of restir_render in these modes).  ray_trace_mode must be RMIS or ROMIS (RESTIR_ERR_INVALID otherwise); the tile
+ * must be consistent (as restir_render's) and its computed region must hold the owned rectangle grown by r on every
+ * side, clipped to the image (RESTIR_ERR_INVALID; restir_tile_plan / restir_layout_tile with ghost = r give such tiles).
+ * The R-OMIS window rule and the neighbourhood capacity are the global image's.  One frame index is consumed per call:
+ * after restir_set_seed(seed, f) a tile's owned pixels are the whole-image render's after the same call.  The G-buffer,
+ * reservoir and debug planes are sized by the computed region; neighbourhoods, accumulators, per-sample scratch and the
+ * image by the owned rectangle.  save_alphas_visualisation with a renders dir set is RESTIR_ERR_UNSUPPORTED on a tile
+ * that is not the whole image (the bitmaps are whole-image files). */
+restir_status restir_render_mis_tile(restir_ctx* ctx, const restir_camera* cam, const restir_features* features,
+                                     uint32_t width, uint32_t height, const restir_tile* tile, float* out_rgb);
+/* Every tile of `layout` in turn on this context (rank 0 .. n - 1, restir_layout_tile with ghost = r), all with ONE
+ * frame index (consumed once), stitched into the whole image out_rgb (global_width x global_height x 3 floats, row 0 =
+ * top): frames whose whole-image buffers would not fit.  Fails on the first tile that fails. */
+restir_status restir_render_mis_tiles(restir_ctx* ctx, const restir_camera* cam, const restir_features* features,
+                                      const restir_tile_layout* layout, float* out_rgb);
 
 restir_status restir_frame_retain(restir_frame* frame);
 /* Drops a reference.  The last one hands the grid's device records back to the producing context for re-use,

@@ -208,6 +208,15 @@ public:
         rendersDir_ = dir;
     }
     const std::filesystem::path& rendersDir() const { return rendersDir_; }
+    // renderRMIS / renderROMIS of one screen tile of a width x height image (restir_render_mis_tile; the tile's ghost
+    // zone = the resample radius, restir_tile_plan / restir_layout_tile): the owned rectangle, tile.width x tile.height
+    // x 3 floats, row 0 = its top -- bit for bit the whole image's pixels
+    std::vector<float> renderMISTile(const Camera& camera, const Features& features, uint32_t width, uint32_t height,
+                                     const restir_tile& tile) {
+        std::vector<float> rgb(size_t(tile.width) * tile.height * 3);
+        check(restir_render_mis_tile(ctx_, &camera, &features, width, height, &tile, rgb.data()), "restir_render_mis_tile");
+        return rgb;
+    }
     restir_ctx* handle() const { return ctx_; }
 
 private:

@@ -203,6 +203,10 @@ SIGNATURES = {
                                             C.POINTER(Texture), C.c_uint32]),
     "restir_render": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Features), C.c_uint32, C.c_uint32,
                                 C.POINTER(Tile), _P, C.POINTER(_P), C.POINTER(C.c_float)]),
+    "restir_render_mis_tile": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Features), C.c_uint32, C.c_uint32,
+                                         C.POINTER(Tile), C.POINTER(C.c_float)]),
+    "restir_render_mis_tiles": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Features), C.POINTER(TileLayout),
+                                          C.POINTER(C.c_float)]),
     "restir_frame_retain": (C.c_int, [_P]),
     "restir_frame_release": (None, [_P]),
     "restir_frame_info": (C.c_int, [_P] + [C.POINTER(C.c_uint32)] * 7),

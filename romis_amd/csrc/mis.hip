@@ -7,6 +7,13 @@
 // R-MIS / R-OMIS (renderRMIS / renderROMIS, render.cpp:64-265).  Whole images: the view is the W x H image and
 // pixel index p = y * W + x; reservoir planes [N][pixels], neighbourhoods in MIS_NBR, accumulators in MIS_ACC
 // (include/restir_c.h RESTIR_BUF_MIS_*).  One lane per pixel; the per-pixel loops follow the reference's order.
+// Screen tiles (restir_render_mis_tile, MisTile in restir_types.h): the template parameter TILE of the bodies below
+// splits the index space in two -- the G-buffer, reservoir and debug planes are indexed by view pixel pv, the
+// neighbourhoods, accumulators, per-sample scratch and lanes by owned pixel po, neighbourhood entries are view indices
+// (row 1 = the pixel's own) and RNG keys take the global pixel.  TILE = false is the whole image's code, where all
+// three indices are p.  The kernels that touch one owned pixel's rows only (k_romis_accum*, k_romis_alphas,
+// k_romis_vis, k_romis_solve, k_mis_combine) serve a tile as they are, launched over its ow x oh owned rectangle:
+// their screen write (H - 1 - y) * W + x is then the tile's, row 0 = top of the tile.
 
 // HitInfo::geometryId: the mesh index (rtcAttachGeometry order, embree_interface.cpp:46-47; one material per mesh);
 // a primary miss keeps genPrimaryRayHits' value-initialised HitInfo (render_utils.cpp:15): 0.
@@ -32,18 +39,21 @@ struct MisWin { int x0, y0, x1, y1; };
 // indicesSimilarity's window walk (y outer, x inner, the pixel itself skipped) appending one class (similar 1 /
 // dissimilar 0): all members, or std::sample's selection sampling of `want` of the class's `len` members (member i
 // kept iff U{0..len-1-i}, keyed slot i, < the number still needed)
+// (W = the view's row length, p = the pixel's view index; a tile: off = the view origin's vy0 * vw + vx0 and po = the
+// pixel's owned index, the neighbourhood's column)
+template <bool TILE>
 __device__ uint32_t mis_emit_class(const SceneDev& s, const FeaturesDev& f, const float4* __restrict__ n_t,
-                                   const float4* __restrict__ p_mat, uint32_t W, MisWin w, uint32_t p, float4 cn,
-                                   uint32_t cg, int cls, uint64_t len, uint64_t want, bool take_all, uint32_t ps,
-                                   uint32_t* __restrict__ nbr, size_t npx, uint32_t n) {
+                                   const float4* __restrict__ p_mat, uint32_t W, uint32_t off, MisWin w, uint32_t p,
+                                   uint32_t po, float4 cn, uint32_t cg, int cls, uint64_t len, uint64_t want,
+                                   bool take_all, uint32_t ps, uint32_t* __restrict__ nbr, size_t npx, uint32_t n) {
     uint64_t needed = take_all ? len : (want < len ? want : len);
     uint64_t i = 0;
     for (int ny = w.y0; ny <= w.y1 && needed; ny++) {
         for (int nx = w.x0; nx <= w.x1 && needed; nx++) {
-            const uint32_t q = (uint32_t)ny * W + (uint32_t)nx;
+            const uint32_t q = TILE ? (uint32_t)ny * W + (uint32_t)nx - off : (uint32_t)ny * W + (uint32_t)nx;
             if (q == p || (int)are_similar(s, f, cn, cg, n_t[q], p_mat[q]) != cls) continue;
             const bool keep = take_all || (uint64_t)uniform_index(draw(ps, (uint32_t)i), (uint32_t)(len - i)) < needed;
-            if (keep) { nbr[(size_t)(1u + n) * npx + p] = q; n++; needed--; }
+            if (keep) { nbr[(size_t)(1u + n) * npx + (TILE ? po : p)] = q; n++; needed--; }
             i++;
         }
     }
@@ -53,21 +63,22 @@ __device__ uint32_t mis_emit_class(const SceneDev& s, const FeaturesDev& f, cons
 // The same walk over the count pass's similarity bits (window member m = bit m, LDS word m / 32 of the lane, stride
 // 256): windows of up to kMisMaskBits members skip re-evaluating areSimilar in the emit passes.
 constexpr uint32_t kMisMaskWords = 14, kMisMaskBits = 32u * kMisMaskWords;   // 448 >= (2 * 10 + 1)^2 - 1
-__device__ uint32_t mis_emit_class_mask(const uint32_t* __restrict__ mask, uint32_t W, MisWin w, uint32_t p, int cls,
-                                        uint64_t len, uint64_t want, bool take_all, uint32_t ps,
+template <bool TILE>
+__device__ uint32_t mis_emit_class_mask(const uint32_t* __restrict__ mask, uint32_t W, uint32_t off, MisWin w, uint32_t p,
+                                        uint32_t po, int cls, uint64_t len, uint64_t want, bool take_all, uint32_t ps,
                                         uint32_t* __restrict__ nbr, size_t npx, uint32_t n) {
     uint64_t needed = take_all ? len : (want < len ? want : len);
     uint64_t i = 0;
     uint32_t m = 0;
     for (int ny = w.y0; ny <= w.y1 && needed; ny++) {
         for (int nx = w.x0; nx <= w.x1 && needed; nx++) {
-            const uint32_t q = (uint32_t)ny * W + (uint32_t)nx;
+            const uint32_t q = TILE ? (uint32_t)ny * W + (uint32_t)nx - off : (uint32_t)ny * W + (uint32_t)nx;
             if (q == p) continue;
             const int sim = (int)((mask[(m >> 5) * 256u] >> (m & 31u)) & 1u);
             m++;
             if (sim != cls) continue;
             const bool keep = take_all || (uint64_t)uniform_index(draw(ps, (uint32_t)i), (uint32_t)(len - i)) < needed;
-            if (keep) { nbr[(size_t)(1u + n) * npx + p] = q; n++; needed--; }
+            if (keep) { nbr[(size_t)(1u + n) * npx + (TILE ? po : p)] = q; n++; needed--; }
             i++;
         }
     }
@@ -77,26 +88,32 @@ __device__ uint32_t mis_emit_class_mask(const uint32_t* __restrict__ mask, uint3
 // generateResampleIndicesGrid (neighbour_selection.cpp:107-122): nbr[0][p] = neighbourhood size, nbr[1 + i][p] = its
 // i-th pixel (the pixel itself first).  indicesRandom (:24-43) / indicesSimilarity (:45-105) with the reference's
 // size arithmetic (Dissimilar: `k - similar.size()` as size_t; EqualSimilarDissimilar in uint32_t).
-extern "C" __global__ __launch_bounds__(256) void k_mis_neighbours(SceneDev s, uint32_t W, uint32_t H, FeaturesDev f,
-                                                                  uint32_t key_s, uint32_t key_d,
-                                                                  const float4* __restrict__ n_t,
-                                                                  const float4* __restrict__ p_mat,
-                                                                  uint32_t* __restrict__ nbr) {
-    __shared__ uint32_t s_mask[kMisMaskWords * 256u];
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= W * H) return;
-    const size_t npx = (size_t)W * H;
-    const int x = (int)(p % W), y = (int)(p / W), rc = (int)f.R;
+// A tile (TILE; t = the tile, W x H the global image): one lane per owned pixel po, the window clamped to the global
+// image (it lies inside the view: the ghost ring is the radius), the RNG keyed by the global pixel, entries and the
+// G-buffer reads by view index; the window walk and the similarity-bit mask are the whole image's.
+template <bool TILE>
+__device__ __forceinline__ void mis_neighbours_body(const SceneDev& s, uint32_t W, uint32_t H, const MisTile& t,
+                                                    const FeaturesDev& f, uint32_t key_s, uint32_t key_d,
+                                                    const float4* __restrict__ n_t, const float4* __restrict__ p_mat,
+                                                    uint32_t* __restrict__ nbr, uint32_t* s_mask) {
+    const uint32_t po = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t ow = TILE ? t.ow : W, oh = TILE ? t.oh : H;
+    if (po >= ow * oh) return;
+    const size_t npx = (size_t)ow * oh;
+    const int x = (int)(po % ow) + (TILE ? (int)t.ox0 : 0), y = (int)(po / ow) + (TILE ? (int)t.oy0 : 0), rc = (int)f.R;
+    const uint32_t vs = TILE ? t.vw : W, off = TILE ? t.vy0 * t.vw + t.vx0 : 0u;
+    const uint32_t p = TILE ? (uint32_t)y * vs + (uint32_t)x - off : po;   // view index
+    const uint32_t g = TILE ? (uint32_t)y * W + (uint32_t)x : po;          // global pixel
     const uint32_t k = f.K;
-    const uint32_t ps_s = pix_state(key_s, p), ps_d = pix_state(key_d, p);
+    const uint32_t ps_s = pix_state(key_s, g), ps_d = pix_state(key_d, g);
     const MisWin w = {max(x - rc, 0), max(y - rc, 0), min(x + rc, (int)W - 1), min(y + rc, (int)H - 1)};
-    nbr[npx + p] = p;
+    nbr[npx + po] = p;
     uint32_t n = 1;
     if (f.strategy == RESTIR_NEIGHBOURS_RANDOM) {
         for (uint32_t c = 0; c < k; c++) {
             const uint32_t nx = (uint32_t)w.x0 + uniform_index(draw(ps_s, 2u * c), (uint32_t)(w.x1 - w.x0 + 1));
             const uint32_t ny = (uint32_t)w.y0 + uniform_index(draw(ps_s, 2u * c + 1u), (uint32_t)(w.y1 - w.y0 + 1));
-            nbr[(size_t)(1u + n) * npx + p] = ny * W + nx;
+            nbr[(size_t)(1u + n) * npx + po] = TILE ? ny * vs + nx - off : ny * W + nx;
             n++;
         }
     } else {
@@ -108,7 +125,7 @@ extern "C" __global__ __launch_bounds__(256) void k_mis_neighbours(SceneDev s, u
         uint32_t m = 0, word = 0;
         for (int ny = w.y0; ny <= w.y1; ny++)
             for (int nx = w.x0; nx <= w.x1; nx++) {
-                const uint32_t q = (uint32_t)ny * W + (uint32_t)nx;
+                const uint32_t q = TILE ? (uint32_t)ny * vs + (uint32_t)nx - off : (uint32_t)ny * W + (uint32_t)nx;
                 if (q == p) continue;
                 const bool sim = are_similar(s, f, cn, cg, n_t[q], p_mat[q]);
                 if (sim) S++; else D++;
@@ -121,8 +138,9 @@ extern "C" __global__ __launch_bounds__(256) void k_mis_neighbours(SceneDev s, u
         if (use_mask && (m & 31u)) mask[(m >> 5) * 256u] = word;
         // emit one class: from the stored bits, or by re-evaluating areSimilar for windows past kMisMaskBits
         auto emit = [&](int cls, uint64_t len, uint64_t want, bool take_all, uint32_t ps, uint32_t n0) {
-            return use_mask ? mis_emit_class_mask(mask, W, w, p, cls, len, want, take_all, ps, nbr, npx, n0)
-                            : mis_emit_class(s, f, n_t, p_mat, W, w, p, cn, cg, cls, len, want, take_all, ps, nbr, npx, n0);
+            return use_mask ? mis_emit_class_mask<TILE>(mask, vs, off, w, p, po, cls, len, want, take_all, ps, nbr, npx, n0)
+                            : mis_emit_class<TILE>(s, f, n_t, p_mat, vs, off, w, p, po, cn, cg, cls, len, want, take_all,
+                                                   ps, nbr, npx, n0);
         };
         if (f.strategy == RESTIR_NEIGHBOURS_SIMILAR) {
             if (S < k) {
@@ -146,12 +164,31 @@ extern "C" __global__ __launch_bounds__(256) void k_mis_neighbours(SceneDev s, u
             n = emit(0, D, (uint32_t)(k - sS), false, ps_d, n);
         }
     }
-    nbr[p] = n;
+    nbr[po] = n;
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_mis_neighbours(SceneDev s, uint32_t W, uint32_t H, FeaturesDev f,
+                                                                  uint32_t key_s, uint32_t key_d,
+                                                                  const float4* __restrict__ n_t,
+                                                                  const float4* __restrict__ p_mat,
+                                                                  uint32_t* __restrict__ nbr) {
+    __shared__ uint32_t s_mask[kMisMaskWords * 256u];
+    mis_neighbours_body<false>(s, W, H, MisTile{}, f, key_s, key_d, n_t, p_mat, nbr, s_mask);
+}
+extern "C" __global__ __launch_bounds__(256) void k_mis_neighbours_tile(SceneDev s, MisTile t, FeaturesDev f,
+                                                                       uint32_t key_s, uint32_t key_d,
+                                                                       const float4* __restrict__ n_t,
+                                                                       const float4* __restrict__ p_mat,
+                                                                       uint32_t* __restrict__ nbr) {
+    __shared__ uint32_t s_mask[kMisMaskWords * 256u];
+    mis_neighbours_body<true>(s, t.W, t.H, t, f, key_s, key_d, n_t, p_mat, nbr, s_mask);
 }
 
 // One R-MIS iteration (render.cpp:76-112): acc[3][pixels] += the pixel's estimate over its neighbourhood.
-template <bool LDS_BVH>
-__device__ __forceinline__ void rmis_body(const SceneDev& s, uint32_t W, uint32_t H, const FeaturesDev& f, v3 origin,
+// A tile (TILE): W x H = its owned rectangle (lane, nbr and acc by owned pixel), vpx = its view's pixels (the
+// reservoir planes' stride); the pixel's own record is at its view index, neighbourhood row 1.
+template <bool LDS_BVH, bool TILE>
+__device__ __forceinline__ void rmis_body(const SceneDev& s, uint32_t W, uint32_t H, uint32_t vpx, const FeaturesDev& f, v3 origin,
                                           const float4* __restrict__ n_t, const float4* __restrict__ p_mat,
                                           const uint32_t* __restrict__ nbr, const float4* __restrict__ ra,
                                           const float4* __restrict__ rb, float* __restrict__ acc) {
@@ -159,14 +196,16 @@ __device__ __forceinline__ void rmis_body(const SceneDev& s, uint32_t W, uint32_
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= W * H) return;
     const size_t npx = (size_t)W * H;
+    const size_t rpx = TILE ? (size_t)vpx : npx;
+    const uint32_t pv = TILE ? nbr[npx + p] : p;
     const uint32_t N = f.N;
-    const Px cur = make_px(s, n_t[p], p_mat[p], origin, p);
+    const Px cur = make_px(s, n_t[pv], p_mat[pv], origin, pv);
     const uint32_t c = nbr[p];
     v3 fc = mk(0.0f, 0.0f, 0.0f);
     for (uint32_t i = 0; i < c; i++) {
         const uint32_t q = nbr[(size_t)(1u + i) * npx + p];
         for (uint32_t j = 0; j < N; j++) {
-            const float4 a = ra[(size_t)j * npx + q], b = rb[(size_t)j * npx + q];
+            const float4 a = ra[(size_t)j * rpx + q], b = rb[(size_t)j * rpx + q];
             const v3 pos = xyz(a), col = xyz(b);
             float misWeight;
             if (f.mis_weight == RESTIR_MIS_EQUAL) {
@@ -194,13 +233,25 @@ extern "C" __global__ __launch_bounds__(256) void k_rmis_accum(SceneDev s, uint3
                                                               float oy, float oz, const float4* n_t, const float4* p_mat,
                                                               const uint32_t* nbr, const float4* ra, const float4* rb,
                                                               float* acc) {
-    rmis_body<false>(s, W, H, f, mk(ox, oy, oz), n_t, p_mat, nbr, ra, rb, acc);
+    rmis_body<false, false>(s, W, H, 0u, f, mk(ox, oy, oz), n_t, p_mat, nbr, ra, rb, acc);
 }
 extern "C" __global__ __launch_bounds__(256) void k_rmis_accum_lds(SceneDev s, uint32_t W, uint32_t H, FeaturesDev f,
                                                                   float ox, float oy, float oz, const float4* n_t,
                                                                   const float4* p_mat, const uint32_t* nbr,
                                                                   const float4* ra, const float4* rb, float* acc) {
-    rmis_body<true>(s, W, H, f, mk(ox, oy, oz), n_t, p_mat, nbr, ra, rb, acc);
+    rmis_body<true, false>(s, W, H, 0u, f, mk(ox, oy, oz), n_t, p_mat, nbr, ra, rb, acc);
+}
+extern "C" __global__ __launch_bounds__(256) void k_rmis_accum_tile(SceneDev s, MisTile t, FeaturesDev f, float ox,
+                                                                   float oy, float oz, const float4* n_t,
+                                                                   const float4* p_mat, const uint32_t* nbr,
+                                                                   const float4* ra, const float4* rb, float* acc) {
+    rmis_body<false, true>(s, t.ow, t.oh, t.vw * t.vh, f, mk(ox, oy, oz), n_t, p_mat, nbr, ra, rb, acc);
+}
+extern "C" __global__ __launch_bounds__(256) void k_rmis_accum_lds_tile(SceneDev s, MisTile t, FeaturesDev f, float ox,
+                                                                       float oy, float oz, const float4* n_t,
+                                                                       const float4* p_mat, const uint32_t* nbr,
+                                                                       const float4* ra, const float4* rb, float* acc) {
+    rmis_body<true, true>(s, t.ow, t.oh, t.vw * t.vh, f, mk(ox, oy, oz), n_t, p_mat, nbr, ra, rb, acc);
 }
 
 // ---- Eigen 3 CompleteOrthogonalDecomposition<MatrixXf>::solve (render_utils.h:52) ---------------------------
@@ -419,8 +470,10 @@ __device__ __forceinline__ float aucw_reciprocal(const SceneDev& s, const Featur
 //  - k_romis_accum_t{T}[_prog]: one lane per pixel: the progressive colour, scale factor, technique matrix and
 //    contribution vector updates of those samples, in the reference's order, reading them back from smp.
 // Every value is computed by the same operations as in one pass, so the split is bit-exact.
-template <int T, bool LDS_BVH>
-__device__ __forceinline__ void romis_samples_body(const SceneDev& s, uint32_t W, uint32_t H, const FeaturesDev& f,
+// A tile (TILE): W x H = its owned rectangle (items, nbr and smp by owned pixel), vpx = its view's pixels (the
+// reservoir and debug planes' stride); the pixel's own record is at its view index, neighbourhood row 1.
+template <int T, bool LDS_BVH, bool TILE>
+__device__ __forceinline__ void romis_samples_body(const SceneDev& s, uint32_t W, uint32_t H, uint32_t vpx, const FeaturesDev& f,
                                                    v3 origin, const float4* __restrict__ n_t,
                                                    const float4* __restrict__ p_mat, const uint32_t* __restrict__ nbr,
                                                    const float4* __restrict__ ra, const float4* __restrict__ rb,
@@ -428,25 +481,27 @@ __device__ __forceinline__ void romis_samples_body(const SceneDev& s, uint32_t W
                                                    float* __restrict__ smp) {
     const Bvh bvh = LDS_BVH ? stage_bvh(s, g_lds) : global_bvh(s);
     const uint32_t npx = W * H;   // launcher: ns * npx < 2^31
+    const uint32_t rpx = TILE ? vpx : npx;
     const uint32_t N = f.N;
     const uint32_t items = ns * npx;
     for (uint32_t it = blockIdx.x * blockDim.x + threadIdx.x; it < items; it += gridDim.x * blockDim.x) {
         const uint32_t sl = it / npx, p = it - sl * npx;
         const uint32_t sg = s0 + sl, pi = sg / N, si = sg - pi * N;
         const uint32_t q = nbr[(size_t)(1u + pi) * npx + p];
-        const float4 a = ra[(size_t)si * npx + q], b4 = rb[(size_t)si * npx + q];
+        const float4 a = ra[(size_t)si * rpx + q], b4 = rb[(size_t)si * rpx + q];
         const v3 pos = xyz(a), col = xyz(b4);
         float* out = smp + (size_t)sl * (T + 3) * npx + p;
         // the T target-pdf evaluations as one rolled loop (one inlined copy of target_pdf)
 #pragma unroll 1
         for (int d = 0; d < T; d++) {
             const uint32_t qq = nbr[(size_t)(1 + d) * npx + p];
-            const float4 db = rb[(size_t)si * npx + qq];
-            const float2 dd = rdbg[(size_t)si * npx + qq];
+            const float4 db = rb[(size_t)si * rpx + qq];
+            const float2 dd = rdbg[(size_t)si * rpx + qq];
             out[(size_t)d * npx] = aucw_reciprocal(s, f, make_px(s, n_t[qq], p_mat[qq], origin, qq),
                                                    (float)__float_as_uint(db.w), dd.x, dd.y, pos, col);
         }
-        const Px cur = make_px(s, n_t[p], p_mat[p], origin, p);
+        const uint32_t pv = TILE ? nbr[npx + p] : p;
+        const Px cur = make_px(s, n_t[pv], p_mat[pv], origin, pv);
         const v3 sc = visible(bvh, cur.P, pos) ? shade(s, f, cur, pos, col) : mk(0.0f, 0.0f, 0.0f);
         out[(size_t)T * npx] = sc.x;
         out[(size_t)(T + 1) * npx] = sc.y;
@@ -584,7 +639,15 @@ __device__ __forceinline__ void romis_vis_body(uint32_t W, uint32_t H, const flo
                                                           float oy, float oz, const float4* n_t, const float4* p_mat,  \
                                                           const uint32_t* nbr, const float4* ra, const float4* rb,      \
                                                           const float2* rdbg, uint32_t s0, uint32_t ns, float* smp) {   \
-        romis_samples_body<T, LDS>(s, W, H, f, mk(ox, oy, oz), n_t, p_mat, nbr, ra, rb, rdbg, s0, ns, smp);             \
+        romis_samples_body<T, LDS, false>(s, W, H, 0u, f, mk(ox, oy, oz), n_t, p_mat, nbr, ra, rb, rdbg, s0, ns, smp);  \
+    }
+#define ROMIS_ROMIS_SAMPLES_TILE(T, LDS, NAME)                                                                      \
+    extern "C" __global__ __launch_bounds__(256) void NAME(SceneDev s, MisTile t, FeaturesDev f, float ox, float oy,    \
+                                                          float oz, const float4* n_t, const float4* p_mat,            \
+                                                          const uint32_t* nbr, const float4* ra, const float4* rb,      \
+                                                          const float2* rdbg, uint32_t s0, uint32_t ns, float* smp) {   \
+        romis_samples_body<T, LDS, true>(s, t.ow, t.oh, t.vw * t.vh, f, mk(ox, oy, oz), n_t, p_mat, nbr, ra, rb, rdbg,  \
+                                         s0, ns, smp);                                                                 \
     }
 #define ROMIS_ROMIS_ACCUM(T, PROG, NAME)                                                                             \
     extern "C" __global__ __launch_bounds__(256) void NAME(uint32_t W, uint32_t H, FeaturesDev f, uint32_t s0,           \
@@ -594,6 +657,8 @@ __device__ __forceinline__ void romis_vis_body(uint32_t W, uint32_t H, const flo
 #define ROMIS_ROMIS_KERNELS(T)                                                                                        \
     ROMIS_ROMIS_SAMPLES(T, false, k_romis_samples_t##T)                                                               \
     ROMIS_ROMIS_SAMPLES(T, true, k_romis_samples_lds_t##T)                                                            \
+    ROMIS_ROMIS_SAMPLES_TILE(T, false, k_romis_samples_tile_t##T)                                                     \
+    ROMIS_ROMIS_SAMPLES_TILE(T, true, k_romis_samples_lds_tile_t##T)                                                  \
     ROMIS_ROMIS_ACCUM(T, false, k_romis_accum_t##T)                                                                   \
     ROMIS_ROMIS_ACCUM(T, true, k_romis_accum_prog_t##T)                                                               \
     extern "C" __global__ __launch_bounds__(256) void k_romis_alphas_t##T(uint32_t W, uint32_t H, float* acc) {         \
@@ -683,6 +748,8 @@ namespace romis {
 namespace {
 typedef void (*RomisSamplesFn)(SceneDev, uint32_t, uint32_t, FeaturesDev, float, float, float, const float4*, const float4*,
                                const uint32_t*, const float4*, const float4*, const float2*, uint32_t, uint32_t, float*);
+typedef void (*RomisSamplesTileFn)(SceneDev, MisTile, FeaturesDev, float, float, float, const float4*, const float4*,
+                                   const uint32_t*, const float4*, const float4*, const float2*, uint32_t, uint32_t, float*);
 typedef void (*RomisAccumFn)(uint32_t, uint32_t, FeaturesDev, uint32_t, uint32_t, const float*, float*);
 typedef void (*RomisAlphasFn)(uint32_t, uint32_t, float*);
 typedef void (*RomisSolveFn)(uint32_t, uint32_t, FeaturesDev, const float*, float*);
@@ -691,6 +758,8 @@ typedef void (*DebugCodFn)(const float*, const float*, float*, uint32_t);
 #define ROMIS_T_TABLE(PFX) {PFX##1, PFX##2, PFX##3, PFX##4, PFX##5, PFX##6, PFX##7, PFX##8}
 const RomisSamplesFn kRomisSamples[8] = ROMIS_T_TABLE(k_romis_samples_t);
 const RomisSamplesFn kRomisSamplesLds[8] = ROMIS_T_TABLE(k_romis_samples_lds_t);
+const RomisSamplesTileFn kRomisSamplesTile[8] = ROMIS_T_TABLE(k_romis_samples_tile_t);
+const RomisSamplesTileFn kRomisSamplesLdsTile[8] = ROMIS_T_TABLE(k_romis_samples_lds_tile_t);
 const RomisAccumFn kRomisAccum[8] = ROMIS_T_TABLE(k_romis_accum_t);
 const RomisAccumFn kRomisAccumProg[8] = ROMIS_T_TABLE(k_romis_accum_prog_t);
 const RomisAlphasFn kRomisAlphas[8] = ROMIS_T_TABLE(k_romis_alphas_t);
@@ -706,16 +775,30 @@ hipError_t launch_mis_neighbours(const SceneDev& s, uint32_t W, uint32_t H, cons
     return hipGetLastError();
 }
 
-hipError_t launch_mis_accumulate(const SceneDev& s, uint32_t W, uint32_t H, const FeaturesDev& f, const float* o,
-                                 const float4* n_t, const float4* p_mat, const uint32_t* nbr, const float4* ra,
-                                 const float4* rb, const float2* rdbg, uint32_t iteration, float* acc, float* smp,
-                                 uint32_t smp_samples, const Tuning& tu, hipStream_t stream) {
+hipError_t launch_mis_neighbours(const SceneDev& s, const MisTile& t, const FeaturesDev& f, uint32_t key_s, uint32_t key_d,
+                                 const float4* n_t, const float4* p_mat, uint32_t* nbr, hipStream_t stream) {
+    ROMIS_LAUNCH(k_mis_neighbours_tile, px_grid((size_t)t.ow * t.oh), dim3(kBlock), 0, stream, s, t, f, key_s, key_d, n_t,
+                 p_mat, nbr);
+    return hipGetLastError();
+}
+
+namespace {
+// One iteration over W x H lanes: the whole image (tile null), or a tile's owned rectangle -- then the kernels that read
+// other pixels' records are the tile forms; the per-owned-pixel ones are the same kernels over the owned rectangle
+hipError_t mis_accumulate(const SceneDev& s, uint32_t W, uint32_t H, const MisTile* tile, const FeaturesDev& f, const float* o,
+                          const float4* n_t, const float4* p_mat, const uint32_t* nbr, const float4* ra, const float4* rb,
+                          const float2* rdbg, uint32_t iteration, float* acc, float* smp, uint32_t smp_samples,
+                          const Tuning& tu, hipStream_t stream) {
     const size_t lds = bvh_lds_bytes(s);
     const bool use_lds = tu.final_lds && lds <= kLdsBudget;   // shadow rays: the BVH staged like k_final's
     const dim3 grid = px_grid((size_t)W * H);
     if (f.mode == RESTIR_MODE_RMIS) {
-        ROMIS_LAUNCH(use_lds ? k_rmis_accum_lds : k_rmis_accum, grid, dim3(kBlock), use_lds ? lds : 0, stream, s, W, H, f,
-                     o[0], o[1], o[2], n_t, p_mat, nbr, ra, rb, acc);
+        if (tile)
+            ROMIS_LAUNCH(use_lds ? k_rmis_accum_lds_tile : k_rmis_accum_tile, grid, dim3(kBlock), use_lds ? lds : 0, stream, s,
+                         *tile, f, o[0], o[1], o[2], n_t, p_mat, nbr, ra, rb, acc);
+        else
+            ROMIS_LAUNCH(use_lds ? k_rmis_accum_lds : k_rmis_accum, grid, dim3(kBlock), use_lds ? lds : 0, stream, s, W, H, f,
+                         o[0], o[1], o[2], n_t, p_mat, nbr, ra, rb, acc);
     } else {
         const uint32_t T = f.K + 1u;
         if (T < 1u || T > 8u) return hipErrorInvalidValue;
@@ -723,18 +806,37 @@ hipError_t launch_mis_accumulate(const SceneDev& s, uint32_t W, uint32_t H, cons
             ROMIS_LAUNCH(kRomisAlphas[T - 1], grid, dim3(kBlock), 0, stream, W, H, acc);
         // the T x N samples in chunks of smp_samples (the scratch rows ensure_mis sized), in the reference's order
         const RomisSamplesFn ks = use_lds ? kRomisSamplesLds[T - 1] : kRomisSamples[T - 1];
+        const RomisSamplesTileFn kst = use_lds ? kRomisSamplesLdsTile[T - 1] : kRomisSamplesTile[T - 1];
         const RomisAccumFn ka = f.progressive ? kRomisAccumProg[T - 1] : kRomisAccum[T - 1];
         const uint32_t npx = W * H, S = T * f.N;
         if (smp_samples == 0u || (uint64_t)smp_samples * npx >= (1ull << 31)) return hipErrorInvalidValue;
         for (uint32_t s0 = 0; s0 < S; s0 += smp_samples) {
             const uint32_t ns = std::min(smp_samples, S - s0);
             const uint32_t blocks = std::min<uint32_t>((ns * npx + kBlock - 1u) / kBlock, 8192u);
-            ROMIS_LAUNCH(ks, dim3(blocks), dim3(kBlock), use_lds ? lds : 0, stream, s, W, H, f, o[0], o[1], o[2], n_t,
-                         p_mat, nbr, ra, rb, rdbg, s0, ns, smp);
+            if (tile)
+                ROMIS_LAUNCH(kst, dim3(blocks), dim3(kBlock), use_lds ? lds : 0, stream, s, *tile, f, o[0], o[1], o[2], n_t,
+                             p_mat, nbr, ra, rb, rdbg, s0, ns, smp);
+            else
+                ROMIS_LAUNCH(ks, dim3(blocks), dim3(kBlock), use_lds ? lds : 0, stream, s, W, H, f, o[0], o[1], o[2], n_t,
+                             p_mat, nbr, ra, rb, rdbg, s0, ns, smp);
             ROMIS_LAUNCH(ka, grid, dim3(kBlock), 0, stream, W, H, f, s0, ns, smp, acc);
         }
     }
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_mis_accumulate(const SceneDev& s, uint32_t W, uint32_t H, const FeaturesDev& f, const float* o,
+                                 const float4* n_t, const float4* p_mat, const uint32_t* nbr, const float4* ra,
+                                 const float4* rb, const float2* rdbg, uint32_t iteration, float* acc, float* smp,
+                                 uint32_t smp_samples, const Tuning& tu, hipStream_t stream) {
+    return mis_accumulate(s, W, H, nullptr, f, o, n_t, p_mat, nbr, ra, rb, rdbg, iteration, acc, smp, smp_samples, tu, stream);
+}
+hipError_t launch_mis_accumulate(const SceneDev& s, const MisTile& t, const FeaturesDev& f, const float* o,
+                                 const float4* n_t, const float4* p_mat, const uint32_t* nbr, const float4* ra,
+                                 const float4* rb, const float2* rdbg, uint32_t iteration, float* acc, float* smp,
+                                 uint32_t smp_samples, const Tuning& tu, hipStream_t stream) {
+    return mis_accumulate(s, t.ow, t.oh, &t, f, o, n_t, p_mat, nbr, ra, rb, rdbg, iteration, acc, smp, smp_samples, tu, stream);
 }
 
 hipError_t launch_mis_finish(uint32_t W, uint32_t H, const FeaturesDev& f, const float* acc, float* rgb, hipStream_t stream) {
@@ -748,6 +850,10 @@ hipError_t launch_mis_finish(uint32_t W, uint32_t H, const FeaturesDev& f, const
         ROMIS_LAUNCH(k_mis_combine, grid, dim3(kBlock), 0, stream, W, H, f, col, rgb);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_mis_finish(const MisTile& t, const FeaturesDev& f, const float* acc, float* rgb, hipStream_t stream) {
+    return launch_mis_finish(t.ow, t.oh, f, acc, rgb, stream);   // per owned pixel: the whole image's kernels
 }
 
 hipError_t launch_romis_vis(uint32_t W, uint32_t H, uint32_t T, const float* acc, uint32_t* out, hipStream_t stream) {

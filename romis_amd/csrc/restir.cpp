@@ -764,9 +764,11 @@ uint32_t mis_acc_rows(const restir_features* f) {
     return f->ray_trace_mode == RESTIR_MODE_ROMIS ? T * T + 6u * T + 3u : 3u;
 }
 constexpr uint64_t kMisSampleBudget = 4ull << 30;   // bytes of R-OMIS per-sample scratch
-restir_status ensure_mis(restir_ctx* c, const restir_features* f, uint32_t W, uint32_t H) {
+// The neighbourhoods, accumulators and per-sample scratch of ow x oh pixels of a W x H image: the whole image, or a
+// screen tile's owned rectangle (the capacity is the image's: a window is clipped to the image, not to the tile)
+restir_status ensure_mis(restir_ctx* c, const restir_features* f, uint32_t W, uint32_t H, uint32_t ow, uint32_t oh) {
     if (f->ray_trace_mode == RESTIR_MODE_RESTIR) return fail(RESTIR_ERR_INVALID, "the MIS stages need rayTraceMode RMIS or ROMIS");
-    const size_t npx = (size_t)W * H;
+    const size_t npx = (size_t)ow * oh;
     c->mis_cap = mis_capacity(f, W, H);
     c->mis_rows = mis_acc_rows(f);
     ST_TRY(c->mis_nbr.ensure((size_t)(1u + c->mis_cap) * npx * 4));
@@ -785,6 +787,7 @@ restir_status ensure_mis(restir_ctx* c, const restir_features* f, uint32_t W, ui
     }
     return RESTIR_OK;
 }
+restir_status ensure_mis(restir_ctx* c, const restir_features* f, uint32_t W, uint32_t H) { return ensure_mis(c, f, W, H, W, H); }
 // renderROMIS reads neighborhood[0..k] (render.cpp:155-181): every pixel's window must hold k candidates
 restir_status check_romis_window(const restir_features* f, uint32_t W, uint32_t H) {
     if (f->ray_trace_mode != RESTIR_MODE_ROMIS || f->neighbour_selection_strategy == RESTIR_NEIGHBOURS_RANDOM) return RESTIR_OK;
@@ -1464,6 +1467,93 @@ static restir_status render_mis(restir_ctx* c, const restir_camera* cam, const r
     return RESTIR_OK;
 }
 
+// restir_render_mis_tile's argument checks, all decided on the host before any device work: the mode, the tile (t = the
+// tile, or the whole image for a null one), its ghost ring and the image's R-OMIS window rule.
+static restir_status mis_tile_check(const restir_features* features, uint32_t width, uint32_t height, const restir_tile* tile,
+                                    restir_tile& t) {
+    if (features->ray_trace_mode != RESTIR_MODE_RMIS && features->ray_trace_mode != RESTIR_MODE_ROMIS)
+        return fail(RESTIR_ERR_INVALID, "restir_render_mis_tile needs rayTraceMode RMIS or ROMIS (restir_render renders ReSTIR tiles)");
+    if (width == 0 || height == 0) return fail(RESTIR_ERR_INVALID, "empty image %ux%u", width, height);
+    t = restir_tile{};
+    if (tile) {
+        t = *tile;
+        if (t.global_width != width || t.global_height != height)
+            return fail(RESTIR_ERR_INVALID, "tile global size %ux%u != %ux%u", t.global_width, t.global_height, width, height);
+        if (t.width == 0 || t.height == 0 || (uint64_t)t.x0 + t.width > width || (uint64_t)t.y0 + t.height > height ||
+            t.gx0 > t.x0 || t.gy0 > t.y0 || (uint64_t)t.gx0 + t.gwidth < (uint64_t)t.x0 + t.width ||
+            (uint64_t)t.gy0 + t.gheight < (uint64_t)t.y0 + t.height || (uint64_t)t.gx0 + t.gwidth > width ||
+            (uint64_t)t.gy0 + t.gheight > height)
+            return fail(RESTIR_ERR_INVALID, "inconsistent tile");
+    } else {
+        t.global_width = width; t.global_height = height;
+        t.width = width; t.height = height;
+        t.gwidth = width; t.gheight = height;
+    }
+    // every owned pixel's window, clipped to the image, lies in the computed region (any strategy: Random's window is
+    // the same radius) -- the tile kernels index the view planes with it
+    const uint64_t g = features->spatial_resample_radius;
+    const uint64_t gx0 = t.x0 > g ? t.x0 - g : 0u, gy0 = t.y0 > g ? t.y0 - g : 0u;
+    const uint64_t gx1 = std::min<uint64_t>((uint64_t)t.x0 + t.width + g, width);
+    const uint64_t gy1 = std::min<uint64_t>((uint64_t)t.y0 + t.height + g, height);
+    if (t.gx0 > gx0 || t.gy0 > gy0 || (uint64_t)t.gx0 + t.gwidth < gx1 || (uint64_t)t.gy0 + t.gheight < gy1)
+        return fail(RESTIR_ERR_INVALID, "tile ghost zone narrower than the resample radius %llu", (unsigned long long)g);
+    return check_romis_window(features, width, height);   // a property of the image, not of the tile
+}
+
+static bool tile_is_whole_image(const restir_tile& t) {
+    return t.x0 == 0 && t.y0 == 0 && t.width == t.global_width && t.height == t.global_height;
+}
+
+// renderRMIS / renderROMIS of the owned rectangle of tile t (mis_tile_check passed; not the whole image): primary rays and
+// RIS over the ghost-zoned view, the neighbourhoods, accumulation, solves and screen over the owned pixels (mis.hip's
+// tile kernels).  Consumes one frame index; the caller holds c->mu.
+static restir_status render_mis_tile(restir_ctx* c, const restir_camera* cam, const restir_features* features, uint32_t W,
+                                     uint32_t H, const restir_tile& t, float* out_rgb) {
+    const FeaturesDev f = to_dev(features);
+    if (f.mode == RESTIR_MODE_ROMIS && features->save_alphas_visualisation && !c->renders_dir.empty())
+        return fail(RESTIR_ERR_UNSUPPORTED, "alpha visualisation on a screen tile: the per-distribution bitmaps are whole-image files");
+    const size_t vpx = (size_t)t.gwidth * t.gheight, opx = (size_t)t.width * t.height;
+    c->gbuf.valid = false;   // k_primary writes n_t / p_mat below
+    ST_TRY(ensure_work(c, t.gwidth, t.gheight, f.N, true));
+    ST_TRY(ensure_mis(c, features, W, H, t.width, t.height));
+    ST_TRY(c->rgb.ensure(opx * 12));
+    c->rgb_w = t.width; c->rgb_h = t.height;
+    c->stage_ok = false;   // the stage buffers now hold this render's state
+    const CameraDev camd = camera_dev(cam);
+    const Region view = make_region(W, H, t.gx0, t.gy0, t.gwidth, t.gheight, t.gx0, t.gy0, t.gwidth, t.gheight);
+    const MisTile mt{W, H, t.gx0, t.gy0, t.gwidth, t.gheight, t.x0, t.y0, t.width, t.height};
+    const uint32_t frame = c->frame_index++;
+    SceneDev s;
+    ST_TRY(scene_for(c, f, vpx, s));
+    float4* nt = c->n_t.as<float4>();
+    float4* pm = c->p_mat.as<float4>();
+    LaunchBufs b;
+    b.cam = &camd; b.origin = camd.origin; b.n_t = nt; b.p_mat = pm;
+    b.oa = c->ra[0].as<float4>(); b.ob = c->rb[0].as<float4>(); b.dbg = c->dbg[0].as<float2>();
+    TIMED(c, RESTIR_K_PRIMARY, launch_primary(route_primary(s, view, c->tuning), s, view, b, c->stream));
+    Ask ris_ask;
+    ris_ask.dbg = true;
+    const Route ris = route_ris(s, view, f, c->tuning, ris_ask);
+    TIMED(c, RESTIR_K_MIS, launch_mis_neighbours(s, mt, f, restir_rng_key(c->seed, frame, RESTIR_STAGE_NEIGHBOURS, 0),
+                                                 restir_rng_key(c->seed, frame, RESTIR_STAGE_NEIGHBOURS, 1), nt, pm,
+                                                 c->mis_nbr.as<uint32_t>(), c->stream));
+    HIP_TRY(hipMemsetAsync(c->mis_acc.p, 0, (size_t)c->mis_rows * opx * 4, c->stream));
+    for (uint32_t it = 0; it < features->max_iterations_mis; it++) {
+        b.key = restir_rng_key(c->seed, frame, RESTIR_STAGE_RIS, it);
+        TIMED(c, RESTIR_K_RIS, launch_ris(ris, s, view, f, b, c->stream));
+        TIMED(c, RESTIR_K_MIS, launch_mis_accumulate(s, mt, f, camd.origin, nt, pm, c->mis_nbr.as<uint32_t>(),
+                                                     c->ra[0].as<float4>(), c->rb[0].as<float4>(), c->dbg[0].as<float2>(), it,
+                                                     c->mis_acc.as<float>(), c->mis_smp.as<float>(), c->mis_smp_samples,
+                                                     c->tuning, c->stream));
+    }
+    TIMED(c, RESTIR_K_MIS, launch_mis_finish(mt, f, c->mis_acc.as<float>(), c->rgb.as<float>(), c->stream));
+    if (out_rgb) {
+        HIP_TRY(hipMemcpyAsync(out_rgb, c->rgb.p, opx * 12, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return RESTIR_OK;
+}
+
 // What both frame paths ask of primary rays + RIS over the view: the pdf cache where the layout has one, and
 // background-tile flags (MissTiles; knob miss.tiles) -- not with temporal reuse (its output is not the RIS result); the
 // spatial shortcuts also need bounded normals (their miss tests)
@@ -1533,7 +1623,8 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
     if (features->ray_trace_mode != RESTIR_MODE_RESTIR) {   // renderRayTraced's switch (render.cpp:274-279)
         if (tile && (tile->global_width != width || tile->global_height != height || tile->x0 || tile->y0 ||
                      tile->width != width || tile->height != height))
-            return fail(RESTIR_ERR_UNSUPPORTED, "R-MIS / R-OMIS render whole images only (no screen tiles)");
+            return fail(RESTIR_ERR_UNSUPPORTED, "R-MIS / R-OMIS render whole images only here (no screen tiles): "
+                                                "restir_render_mis_tile renders their tiles");
         return render_mis(c, cam, features, width, height, out_rgb);
     }
 
@@ -1760,6 +1851,58 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
         HIP_TRY(hipMemcpyAsync(out_rgb, fb.rgb().p, (size_t)t.width * t.height * 12, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
+    return RESTIR_OK;
+}
+
+// One tile (validated) by the whole-image path when it is the whole image, else by the tile path; either consumes one
+// frame index.  The caller holds c->mu.
+static restir_status render_mis_any(restir_ctx* c, const restir_camera* cam, const restir_features* features, uint32_t width,
+                                    uint32_t height, const restir_tile& t, float* out_rgb) {
+    if (tile_is_whole_image(t)) return render_mis(c, cam, features, width, height, out_rgb);
+    return render_mis_tile(c, cam, features, width, height, t, out_rgb);
+}
+
+restir_status restir_render_mis_tile(restir_ctx* c, const restir_camera* cam, const restir_features* features, uint32_t width,
+                                     uint32_t height, const restir_tile* tile, float* out_rgb) {
+    // the argument checks come first: they need no device (nor a context)
+    if (!cam) return fail(RESTIR_ERR_INVALID, "camera is NULL");
+    ST_TRY(check_features(features));
+    restir_tile t;
+    ST_TRY(mis_tile_check(features, width, height, tile, t));
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_render_mis_tile before restir_set_scene");
+    HIP_TRY(hipSetDevice(c->device));
+    return render_mis_any(c, cam, features, width, height, t, out_rgb);
+}
+
+restir_status restir_render_mis_tiles(restir_ctx* c, const restir_camera* cam, const restir_features* features,
+                                      const restir_tile_layout* layout, float* out_rgb) {
+    if (!cam) return fail(RESTIR_ERR_INVALID, "camera is NULL");
+    if (!out_rgb) return fail(RESTIR_ERR_INVALID, "restir_render_mis_tiles: out_rgb is NULL");
+    ST_TRY(check_features(features));
+    restir_tile t;
+    ST_TRY(restir_layout_tile(layout, 0, features->spatial_resample_radius, &t));   // (checks the layout)
+    const uint32_t W = layout->global_width, H = layout->global_height, n = layout->tiles_x * layout->tiles_y;
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_render_mis_tiles before restir_set_scene");
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t frame = c->frame_index;   // every tile renders this frame
+    std::vector<float> part;
+    for (uint32_t q = 0; q < n; q++) {
+        restir_tile tq, tv;
+        ST_TRY(restir_layout_tile(layout, q, features->spatial_resample_radius, &tq));
+        ST_TRY(mis_tile_check(features, W, H, &tq, tv));
+        part.resize((size_t)tv.width * tv.height * 3);
+        c->frame_index = frame;
+        ST_TRY(render_mis_any(c, cam, features, W, H, tv, part.data()));
+        const uint32_t r0 = H - (tv.y0 + tv.height);   // tile rows count from the bottom, image rows from the top
+        for (uint32_t r = 0; r < tv.height; r++)
+            std::memcpy(out_rgb + ((size_t)(r0 + r) * W + tv.x0) * 3, part.data() + (size_t)r * tv.width * 3,
+                        (size_t)tv.width * 12);
+    }
+    c->frame_index = frame + 1u;
     return RESTIR_OK;
 }
 

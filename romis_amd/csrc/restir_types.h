@@ -107,6 +107,17 @@ struct Region {
     uint32_t xcd_cols;   // chunk width in tiles (xcd_tile); 0 = the whole row of tiles
 };
 
+// An R-MIS / R-OMIS screen tile (mis.hip k_*_tile): global image W x H (y = 0 bottom), the computed view
+// (the owned rectangle grown by the resample radius, clipped to the image) and the owned rectangle.  Two index spaces:
+//   view  pv = (y - vy0) * vw + (x - vx0): n_t, p_mat, the texCoord plane, reservoir planes [N][vw * vh], debug plane;
+//   owned po = (y - oy0) * ow + (x - ox0): neighbourhoods, accumulators, per-sample scratch, the lane-to-pixel map.
+// Neighbourhood entries are view indices.  RNG keys take the global pixel y * W + x.
+struct MisTile {
+    uint32_t W, H;
+    uint32_t vx0, vy0, vw, vh;
+    uint32_t ox0, oy0, ow, oh;
+};
+
 // Background tiles (restir_render, N <= 2, no temporal reuse): the fused primary + RIS kernel writes one byte per
 // 32 x 8 tile of its region (the view), 0 when every pixel of the tile is a primary-ray miss whose RIS reservoir is
 // known -- the miss material, P not NaN, finite lights, L != 0: (0, 0, 0, W = 0), (0, 0, 0, M = f.M) in sub-reservoir

@@ -7,6 +7,9 @@ device tensors and the exchange is one batched send/recv group per pass; with "g
 shared by several ranks) the library stages the bytes through host tensors.  Frames are bit-identical to the
 same pixels of a single-GPU restir_render frame, temporal reuse included -- the ghost-zone path
 (restir_render with a tile) cannot carry the predecessor's ghost zone and refuses temporal reuse on tiles.
+
+R-MIS / R-OMIS frames need none of this (MisTiles): a tile with a ghost ring of the resample radius is complete in
+itself, and the only transfer is the optional gather of the finished tiles.
 """
 from __future__ import annotations
 
@@ -120,6 +123,76 @@ class HaloFrames:
             self.r.halo_unpack(self.recvbuf.data_ptr(), rb, host)
             self.r.halo_spatial_border()
         return self.r.halo_end(self.tile, want_rgb, want_grid)
+
+
+class MisTiles:
+    """R-MIS / R-OMIS frames over the group's ranks, one screen tile each (restir_render_mis_tile).
+
+    A tile with a ghost ring of the resample radius reproduces its owned pixels bit for bit with no exchange between
+    ranks and no state between frames, so the only communication is the optional gather of the finished tiles on rank
+    0.  The gather moves the tiles' raw 32-bit words (tiles differ in size; a float reduction over padded images would
+    turn a -0.0 into +0.0)."""
+
+    def __init__(self, renderer: "restir.Renderer", width: int, height: int, tiles: tuple, rank: int, features,
+                 group=None, layout=None):
+        self.W, self.H, self.tiles, self.rank, self.f = width, height, tuple(tiles), rank, features
+        # layout: an uneven tile layout of this very image (every rank must pass the same one), else the even split
+        if layout is not None:
+            if (layout.global_width, layout.global_height) != (width, height):
+                raise ValueError(f"MisTiles: a layout of a {layout.global_width}x{layout.global_height} image for a "
+                                 f"{width}x{height} frame")
+            if (layout.tiles_x, layout.tiles_y) != self.tiles:
+                raise ValueError(f"MisTiles: a {layout.tiles_x}x{layout.tiles_y} layout for {tiles[0]}x{tiles[1]} tiles")
+        import torch
+        import torch.distributed as dist
+        self.torch, self.dist = torch, dist
+        self.r = renderer
+        self.group = group
+        self.layout = layout
+        n = self.tiles[0] * self.tiles[1]
+        if dist.get_rank(group) != rank or dist.get_world_size(group) != n:
+            raise ValueError(f"MisTiles: rank {rank} of a {tiles[0]}x{tiles[1]} tile plan, but the group's rank is "
+                             f"{dist.get_rank(group)} of {dist.get_world_size(group)}")
+        radius = features.spatial_resample_radius
+        self.plan = [restir.tile_plan(width, height, self.tiles[0], self.tiles[1], q, radius, layout=layout)
+                     for q in range(n)]
+        self.tile = self.plan[rank]
+        self.on_device = dist.get_backend(group) == "nccl"
+
+    def _peer(self, q: int) -> int:
+        return self.dist.get_global_rank(self.group, q) if self.group is not None else q
+
+    def render(self, camera, gather: bool = True):
+        """This rank's tile [h][w][3] (row 0 = top) when gather is false; else the whole [H][W][3] image on rank 0 and
+        None on the other ranks."""
+        mine = self.r.render_mis(camera, self.W, self.H, self.f, tile=self.tile)
+        return self.gather(mine) if gather else mine
+
+    def gather(self, mine):
+        """Every rank's [h][w][3] float32 tile stitched into the [H][W][3] image on rank 0 (None elsewhere), word for
+        word: point-to-point transfers of the tiles' 32-bit patterns, no arithmetic on them."""
+        import numpy as np
+        torch, dist = self.torch, self.dist
+        t = self.tile
+        mine = np.ascontiguousarray(mine, dtype=np.float32)
+        if mine.shape != (t.height, t.width, 3):
+            raise ValueError(f"MisTiles.gather: a {mine.shape} array for this rank's {t.height}x{t.width} tile")
+        dev = torch.device("cuda", torch.cuda.current_device()) if self.on_device else torch.device("cpu")
+        if self.rank != 0:
+            words = torch.from_numpy(np.ascontiguousarray(mine).view(np.int32).reshape(-1)).to(dev)
+            dist.send(words, self._peer(0), group=self.group)
+            return None
+        out = np.zeros((self.H, self.W, 3), np.float32)
+        for q, t in enumerate(self.plan):
+            if q == 0:
+                part = mine
+            else:
+                words = torch.empty(t.width * t.height * 3, dtype=torch.int32, device=dev)
+                dist.recv(words, self._peer(q), group=self.group)
+                part = words.cpu().numpy().view(np.float32).reshape(t.height, t.width, 3)
+            r0 = self.H - (t.y0 + t.height)   # tile rows count from the bottom, image rows from the top
+            out[r0:r0 + t.height, t.x0:t.x0 + t.width] = part
+        return out
 
 
 # Cost-balanced screen tiles (VERDICT r5 #2).  A frame's time on a rank follows its geometry pixels (a background

@@ -270,10 +270,33 @@ class Renderer:
               "restir_stage_final")
 
     # ---- R-MIS / R-OMIS (render.cpp:64-265) ------------------------------------------------------------
-    def render_mis(self, camera, width: int, height: int, features) -> np.ndarray:
+    def render_mis(self, camera, width: int, height: int, features, tile=None) -> np.ndarray:
         """renderRMIS / renderROMIS by features.ray_trace_mode: the screen image (row 0 = top).  No grid is
-        returned, as renderRayTraced returns std::nullopt for these modes (render.cpp:274-279)."""
-        rgb, _ = self.render_restir(None, camera, width, height, features, want_grid=False)
+        returned, as renderRayTraced returns std::nullopt for these modes (render.cpp:274-279).
+        tile: a screen tile whose ghost zone is the resample radius (tile_plan(..., ghost=radius)); the result is then
+        the tile's owned rectangle [tile.height][tile.width][3], bit for bit the whole image's pixels
+        (restir_render_mis_tile)."""
+        if tile is None:
+            rgb, _ = self.render_restir(None, camera, width, height, features, want_grid=False)
+            return rgb
+        rgb = np.zeros((tile.height, tile.width, 3), np.float32)
+        check(self.lib, self.lib.restir_render_mis_tile(self.ctx, C.byref(camera), C.byref(features), width, height,
+                                                        C.byref(tile), rgb.ctypes.data_as(C.POINTER(C.c_float))),
+              "restir_render_mis_tile")
+        return rgb
+
+    def render_mis_tiled(self, camera, width: int, height: int, features, tiles=(2, 2), layout=None) -> np.ndarray:
+        """The whole R-MIS / R-OMIS image rendered tile after tile on this one context, all tiles with one frame index
+        (restir_render_mis_tiles): frames whose whole-image buffers would not fit.  tiles: an even (tx, ty) split;
+        layout: a restir_tile_layout of the width x height image instead."""
+        if layout is None:
+            layout = layout_even(width, height, tiles[0], tiles[1])
+        elif (layout.global_width, layout.global_height) != (width, height):
+            raise ValueError(f"layout is of a {layout.global_width}x{layout.global_height} image, not {width}x{height}")
+        rgb = np.zeros((height, width, 3), np.float32)
+        check(self.lib, self.lib.restir_render_mis_tiles(self.ctx, C.byref(camera), C.byref(features), C.byref(layout),
+                                                         rgb.ctypes.data_as(C.POINTER(C.c_float))),
+              "restir_render_mis_tiles")
         return rgb
 
     def mis_capacity(self, features) -> int:
