@@ -283,6 +283,34 @@ restir_status restir_set_scene_textured(restir_ctx* ctx, const restir_mesh* mesh
                                         const restir_light* lights, uint32_t num_lights,
                                         const restir_texture* textures, uint32_t num_textures);
 
+/* ---- dynamic scenes: moving geometry and lights between frames without another upload ----
+ * New vertex positions (and optionally normals) for meshes of the uploaded scene; the topology -- triangles, vertex
+ * counts, materials, textures -- stays.  The device recomputes the triangle records, refits the BVH's boxes over the
+ * tree restir_set_scene built and re-quantizes the shadow rays' nodes; nothing is rebuilt on the host.  The tree only
+ * prunes, so every later frame equals, bit for bit, the frame a fresh restir_set_scene of the moved scene gives.  A tree
+ * refitted far from the scene it was split for walks more nodes per ray: restir_set_scene is the remedy.
+ * RESTIR_ERR_STATE before a scene exists; RESTIR_ERR_INVALID (and nothing changes) for a mesh index out of range, a
+ * vertex count that is not the upload's, NULL positions, a mesh named twice, or a position that is not finite.  The
+ * arrays may be freed on return.  The update is ordered after every frame enqueued so far and before every later one;
+ * temporal predecessors stay valid (their samples are lights).  count == 0 does nothing. */
+typedef struct restir_mesh_update {
+    uint32_t     mesh;          /* index into restir_set_scene's meshes */
+    uint32_t     num_vertices;  /* must equal the upload's */
+    const float* positions;     /* [num_vertices][3] */
+    const float* normals;       /* [num_vertices][3]; NULL = keep the uploaded normals */
+} restir_mesh_update;
+restir_status restir_update_meshes(restir_ctx* ctx, const restir_mesh_update* updates, uint32_t count);
+/* Replaces the light list (any count, any types, or none) and keeps the geometry, the BVH and the kept G-buffer: a still
+ * camera over moving lights traces no primary rays.  Everything restir_set_scene derives from the lights is derived
+ * again (restir_scene_info reports it).  A temporal predecessor rendered before the call carries its samples' old
+ * positions and colours, as the reference's previousFrameGrid does. */
+restir_status restir_set_lights(restir_ctx* ctx, const restir_light* lights, uint32_t num_lights);
+/* Tests: the device's scene arrays as they stand (any pointer NULL = skip).  Sizes from restir_scene_info: nodes
+ * 8 floats per node, nodes_q 4 words per node (untouched when !nodes_q_ok), triangle records 4 floats per triangle --
+ * v0 / e1 / e2 in BVH order, n0 / n1 / n2 in the upload's order. */
+restir_status restir_debug_scene_download(restir_ctx* ctx, float* nodes, uint32_t* nodes_q, float* tri_v0, float* tri_e1,
+                                          float* tri_e2, float* tri_n0, float* tri_n1, float* tri_n2);
+
 /* renderRayTraced (render.cpp:268-290) by features->ray_trace_mode:
  * RMIS / ROMIS -- renderRMIS / renderROMIS (render.cpp:64-265): primary hits -> neighbour selection grid ->
  * max_iterations_mis x (initial RIS -> per-pixel MIS combination over the pixel's neighbourhood) -> screen.

@@ -201,6 +201,23 @@ public:
         check(restir_set_scene(ctx_, m.data(), uint32_t(m.size()), scene.lights.data(), uint32_t(scene.lights.size())),
               "restir_set_scene");
     }
+    // New vertex positions (normals too when meshes[i].normals is not empty) for meshes of the scene set: mesh index ->
+    // a Mesh whose positions have the uploaded count; its triangles and material are not read (restir_update_meshes)
+    void updateMeshes(const std::vector<std::pair<uint32_t, const Mesh*>>& meshes) {
+        std::vector<restir_mesh_update> u(meshes.size());
+        for (size_t i = 0; i < u.size(); i++) {
+            const Mesh& src = *meshes[i].second;
+            u[i].mesh = meshes[i].first;
+            u[i].num_vertices = uint32_t(src.positions.size() / 3);
+            u[i].positions = src.positions.data();
+            u[i].normals = src.normals.size() == src.positions.size() && !src.normals.empty() ? src.normals.data() : nullptr;
+        }
+        check(restir_update_meshes(ctx_, u.data(), uint32_t(u.size())), "restir_update_meshes");
+    }
+    // Another light list over the same geometry (restir_set_lights)
+    void setLights(const std::vector<restir_light>& lights) {
+        check(restir_set_lights(ctx_, lights.data(), uint32_t(lights.size())), "restir_set_lights");
+    }
     void setSeed(uint32_t seed, uint32_t frameIndex = 0) { check(restir_set_seed(ctx_, seed, frameIndex), "restir_set_seed"); }
     // RENDERS_DIR for the file side outputs the library writes itself (R-OMIS alpha visualisation); empty = none
     void setRendersDir(const std::filesystem::path& dir) {

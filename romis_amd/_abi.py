@@ -60,6 +60,12 @@ class Mesh(C.Structure):
                 ("num_triangles", C.c_uint32), ("material", Material), ("texcoords", C.POINTER(C.c_float))]
 
 
+class MeshUpdate(C.Structure):
+    """restir_mesh_update: new vertex positions (normals: NULL keeps the uploaded ones) for one mesh of the scene."""
+    _fields_ = [("mesh", C.c_uint32), ("num_vertices", C.c_uint32), ("positions", C.POINTER(C.c_float)),
+                ("normals", C.POINTER(C.c_float))]
+
+
 class Texture(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgb", C.POINTER(C.c_float))]
 
@@ -201,6 +207,9 @@ SIGNATURES = {
     "restir_set_scene": (C.c_int, [_P, C.POINTER(Mesh), C.c_uint32, C.POINTER(Light), C.c_uint32]),
     "restir_set_scene_textured": (C.c_int, [_P, C.POINTER(Mesh), C.c_uint32, C.POINTER(Light), C.c_uint32,
                                             C.POINTER(Texture), C.c_uint32]),
+    "restir_update_meshes": (C.c_int, [_P, C.POINTER(MeshUpdate), C.c_uint32]),
+    "restir_set_lights": (C.c_int, [_P, C.POINTER(Light), C.c_uint32]),
+    "restir_debug_scene_download": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32)] + [C.POINTER(C.c_float)] * 6),
     "restir_render": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Features), C.c_uint32, C.c_uint32,
                                 C.POINTER(Tile), _P, C.POINTER(_P), C.POINTER(C.c_float)]),
     "restir_render_mis_tile": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Features), C.c_uint32, C.c_uint32,

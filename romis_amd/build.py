@@ -36,11 +36,12 @@ SOURCES = [
     ("kernels.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("restir.cpp", ["-x", "hip"] + DEVICE),
     ("mis.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
+    ("refit.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("bvh.cpp", ["-x", "c++"]),
     ("screen.cpp", ["-x", "c++"]),
 ]
 HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
-           "route.h", "ris_members.h"]
+           "route.h", "ris_members.h", "refit.h"]
 
 
 def source_hash() -> str:
@@ -92,6 +93,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         subprocess.check_call([HIPCC] + COMMON + DEVICE + ["-x", "hip", src, "-o", tool])
     build_route_check(force)
     build_bvh_check(force)
+    build_refit_check(force)
     if verbose:
         print(LIB)
     return LIB
@@ -117,6 +119,21 @@ def build_bvh_check(force: bool = False) -> str:
     tool = os.path.join(OUT, "tools", "bvh_check")
     src = os.path.join(ROOT, "tests", "cpp", "bvh_check.cpp")
     deps = [src, os.path.join(CSRC, "bvh.cpp"), os.path.join(CSRC, "bvh.h"), __file__]
+    if os.path.exists(src) and (force or _stale(tool, deps)):
+        os.makedirs(os.path.dirname(tool), exist_ok=True)
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off", "-pthread", f"-I{CSRC}",
+                               src, os.path.join(CSRC, "bvh.cpp"), "-o", tool])
+    return tool
+
+
+def build_refit_check(force: bool = False) -> str:
+    """tools/refit_check: tests/cpp/refit_check.cpp (which includes bvh_check.cpp for its invariants, walks and rays) over
+    csrc/bvh.cpp with the host compiler -- refit_bvh's trees (tests/test_bvh_refit.py) and the refitted arrays the device
+    tests compare with (tests/test_gpu_dynamic_scene.py); no device code."""
+    tool = os.path.join(OUT, "tools", "refit_check")
+    src = os.path.join(ROOT, "tests", "cpp", "refit_check.cpp")
+    deps = [src, os.path.join(ROOT, "tests", "cpp", "bvh_check.cpp"), os.path.join(CSRC, "bvh.cpp"),
+            os.path.join(CSRC, "bvh.h"), __file__]
     if os.path.exists(src) and (force or _stale(tool, deps)):
         os.makedirs(os.path.dirname(tool), exist_ok=True)
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off", "-pthread", f"-I{CSRC}",
@@ -151,7 +168,7 @@ def main(argv=None) -> int:
 # C++ programs over the C++ binding (include/romis_amd/restir.hpp): the reference-side callers the C++ wrapper tests
 # drive (tests/test_cpp_wrapper.py).  Built on the build host next to the library; the GPU box runs the prebuilt ones.
 CPP_PROGRAMS = [("render_scene.cpp", "render_scene"), ("render_threads.cpp", "render_threads"),
-                ("write_outputs.cpp", "write_outputs")]
+                ("write_outputs.cpp", "write_outputs"), ("update_scene.cpp", "update_scene")]
 CPP_DIR = os.path.join(ROOT, "tests", "cpp")
 
 

@@ -170,6 +170,37 @@ FlatBvh build_bvh(const std::vector<BvhTriangle>& tris, uint32_t max_leaf) {
     return out;
 }
 
+void refit_bvh(FlatBvh& bvh, const std::vector<BvhTriangle>& tris) {
+    const uint32_t n = bvh.num_nodes;
+    if (n == 0 || tris.size() != bvh.tri_order.size()) return;
+    // preorder: a node's children (i + 1 and the left child's miss link) come after it, so one backward sweep sees
+    // both children's boxes before their parent's
+    std::vector<Box> box(n);
+    for (uint32_t i = n; i-- > 0;) {
+        const uint32_t leaf = f2u(bvh.nodes[8 * (size_t)i + 7]);
+        Box b;
+        if (leaf) {
+            const uint32_t first = leaf & 0xFFFFFFu, count = leaf >> 24;
+            for (uint32_t k = first; k < first + count; k++) {
+                const BvhTriangle& t = tris[bvh.tri_order[k]];
+                b.grow(t.v0); b.grow(t.v1); b.grow(t.v2);
+            }
+        } else {
+            b.grow(box[i + 1]);
+            b.grow(box[f2u(bvh.nodes[8 * (size_t)(i + 1) + 3])]);
+        }
+        box[i] = b;
+    }
+    const Box& root = box[0];
+    float scale = 0.0f;
+    for (int a = 0; a < 3; a++) scale = std::max({scale, std::fabs(root.lo[a]), std::fabs(root.hi[a]), root.hi[a] - root.lo[a]});
+    const float pad = 1e-5f * scale + 1e-30f;
+    for (uint32_t i = 0; i < n; i++) {
+        float* o = &bvh.nodes[8 * (size_t)i];
+        for (int a = 0; a < 3; a++) { o[a] = box[i].lo[a] - pad; o[4 + a] = box[i].hi[a] + pad; }
+    }
+}
+
 QuantizedNodes quantize_nodes(const FlatBvh& bvh) {
     QuantizedNodes out;
     const std::vector<float>& nodes = bvh.nodes;

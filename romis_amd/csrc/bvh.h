@@ -24,6 +24,14 @@ struct FlatBvh {
 // Boxes are padded by `pad` in every direction so the device slab test is conservative.
 FlatBvh build_bvh(const std::vector<BvhTriangle>& tris, uint32_t max_leaf = 4);
 
+// Recomputes the boxes of `bvh` over moved triangles (the list build_bvh was given, same count and order, new vertex
+// positions) and leaves its topology alone: miss links, leaf words, tri_order.  Each box is what build_bvh computes for
+// the same subtree -- the unpadded min / max over its vertices, then lo - pad, hi + pad with pad = 1e-5f * scale + 1e-30f
+// and scale taken from the new root -- so refitting with the triangles the tree was built from reproduces its nodes bit
+// for bit.  The tree still only prunes; a refit tree of a scene that moved far from the one it was split for walks more
+// nodes per ray and gives the same hits.  This is the specification of the device refit (refit.hip).
+void refit_bvh(FlatBvh& bvh, const std::vector<BvhTriangle>& tris);
+
 // The shadow rays' 16-byte nodes (SceneDev::nodes_q, kernels_common.h occluded_q): 4 words per node, six 16-bit bounds
 // (lo.x | lo.y << 16, lo.z | hi.x << 16, hi.y | hi.z << 16) on the grid lo + q * s over the root box, then
 // miss link | first triangle << 16 | count << 28 (count 0: inner node).

@@ -28,6 +28,7 @@
 #include "bvh.h"
 #include "device_math.h"
 #include "launch.h"
+#include "refit.h"
 #include "restir_types.h"
 
 namespace romis {
@@ -230,7 +231,24 @@ struct restir_ctx {
         tex_dims, tri_uv, nodes_q;
     SceneDev sdev{};
     bool has_scene = false;
-    uint64_t scene_gen = 0;   // unique per scene upload (frame handles name the light table they index)
+    // Two generations, both unique per change: frame handles name the light table they index (restir_set_scene,
+    // restir_set_lights), the kept G-buffer the geometry it was traced over (restir_set_scene, restir_update_meshes)
+    uint64_t scene_gen = 0;
+    uint64_t geom_gen = 0;
+    // What restir_update_meshes needs of the upload (refit.h RefitDev): the vertices and the triangles' indices into
+    // them, the tree's topology as static tables; per mesh, where its vertices lie and which of them a triangle uses
+    DevBuf vpos, vnrm, tri_idx, tri_order, topo, node_range, level_nodes, level_start, refit_raw;
+    struct MeshKeep {
+        uint32_t first_vertex = 0, num_vertices = 0;
+        std::vector<uint8_t> referenced;   // [num_vertices]: a triangle names the vertex
+        bool normals_bounded = true;       // SceneDev::normals_bounded over the mesh's referenced vertices
+    };
+    std::vector<MeshKeep> mesh_keep;
+    uint32_t bvh_levels = 0;
+    bool topo_q_ok = false;            // the upload had quantized nodes (a refit keeps them unless its grid is not finite)
+    // ... and restir_set_lights: the materials' and texels' part of shade_finite / miss_shade_zero
+    double shade_kmax = 0.0;
+    bool shade_k_finite = true, miss_mat_zero = true;
 
     // work buffers for one view
     uint32_t vw = 0, vh = 0, N = 0;
@@ -256,6 +274,7 @@ struct restir_ctx {
         uint32_t width = 0, height = 0;
         restir_tile tile{};
         uint32_t tex_on = 0;
+        uint32_t light_facts = 0;                  // what the tile flags take from the light list: any lights, all finite
         bool flags = false;                        // tmiss holds the view's flags
         uint32_t skip = 0;                         // the skip_res word the tracing frame ran with
         uint32_t map2d = 0, xcd_rows = 0, xcd_cols = 0, items = 0;   // the tile order the flags are indexed by
@@ -1135,6 +1154,108 @@ static RegularGrid find_regular_grid(const std::vector<float>& lt, uint32_t L) {
     return g;
 }
 
+static std::atomic<uint64_t> g_scene_gens{0};   // restir_ctx::scene_gen / geom_gen: never 0, never twice
+
+static restir_status check_lights(const restir_light* lights, uint32_t num_lights) {
+    for (uint32_t i = 0; i < num_lights; i++)
+        if (lights[i].type > RESTIR_LIGHT_PARALLELOGRAM)
+            return fail(RESTIR_ERR_INVALID, "light %u: bad type %u", i, lights[i].type);
+    return RESTIR_OK;
+}
+
+// SceneDev::normals_bounded over one mesh: the normals [num_vertices][3] of the vertices its triangles name
+static bool normals_bounded_of(const float* normals, const restir_ctx::MeshKeep& mk) {
+    for (uint32_t v = 0; v < mk.num_vertices; v++)
+        for (int a = 0; a < 3 && mk.referenced[v]; a++)
+            if (!(std::fabs(normals[3 * (size_t)v + a]) <= 0x1p125f)) return false;
+    return true;
+}
+
+// The light half of a scene upload (restir_set_scene*, restir_set_lights; lights checked by check_lights): the 7-row
+// table, its compact forms and everything SceneDev derives from the lights.  The materials' part of the shading flags is
+// the context's (shade_kmax, shade_k_finite, miss_mat_zero).  Synchronises the stream before it returns: the tables are
+// host vectors.
+static restir_status upload_lights(restir_ctx* c, const restir_light* lights, uint32_t num_lights) {
+    // lights: 7 float4 records
+    std::vector<float> lt(28 * std::max<uint32_t>(num_lights, 1), 0.0f);
+    uint32_t types = 0;
+    for (uint32_t i = 0; i < num_lights; i++) {
+        const restir_light& l = lights[i];
+        types |= 1u << l.type;
+        float* o = &lt[28 * i];
+        const float* src[7] = {l.p0, l.p1, l.p2, l.c0, l.c1, l.c2, l.c3};
+        for (int r = 0; r < 7; r++) { std::memcpy(&o[4 * r], src[r], 12); o[4 * r + 3] = 0.0f; }
+        o[3] = u2f(l.type);
+    }
+    ST_TRY(c->lights.upload(lt.data(), lt.size() * 4, c->stream));
+    // the compact light table of the RIS kernels' point and grid forms (kernels.hip kLtPoint / kLtGrid): rows 0 and 3
+    // of every record.  A light grid (the reference's regularLightGrid, scene.cpp:5-28): every light a parallelogram
+    // with light 0's edges and one colour at all four of its corners, bit for bit.
+    // Parallelograms with one colour at all four corners (kLtPgram: rows 0..3 of every record) are the
+    // reference's default nightclub set (scene.cpp:30-66); a grid also shares light 0's edges.
+    bool pgram = num_lights > 0 && types == (1u << RESTIR_LIGHT_PARALLELOGRAM);
+    for (uint32_t i = 0; pgram && i < num_lights; i++) {
+        const float* o = &lt[28 * i];
+        pgram = std::memcmp(o + 16, o + 12, 3 * sizeof(float)) == 0 && std::memcmp(o + 20, o + 12, 3 * sizeof(float)) == 0 &&
+                std::memcmp(o + 24, o + 12, 3 * sizeof(float)) == 0;
+    }
+    bool grid = pgram;
+    for (uint32_t i = 0; grid && i < num_lights; i++) grid = std::memcmp(&lt[28 * i + 4], &lt[4], 8 * sizeof(float)) == 0;
+    const RegularGrid reg = grid ? find_regular_grid(lt, num_lights) : RegularGrid{};
+    std::vector<float> lc4(16 * std::max<uint32_t>(pgram ? num_lights : 1u, 1u), 0.0f);
+    for (uint32_t i = 0; pgram && i < num_lights; i++) std::memcpy(&lc4[16 * i], &lt[28 * i], 64);
+    ST_TRY(c->light_c4.upload(lc4.data(), lc4.size() * 4, c->stream));
+    // two planes (SceneDev::light_c2): rows 0 of every light, then rows 3 -- a random light's 16-byte read from an LDS
+    // copy then lands on one of 16 bank groups instead of 8 (32-byte records)
+    std::vector<float> lc2(8 * std::max<uint32_t>(num_lights, 1), 0.0f);
+    for (uint32_t i = 0; i < num_lights; i++) {
+        std::memcpy(&lc2[4 * i], &lt[28 * i], 16);
+        std::memcpy(&lc2[4 * (num_lights + i)], &lt[28 * i + 12], 16);
+    }
+    ST_TRY(c->light_c2.upload(lc2.data(), lc2.size() * 4, c->stream));
+    std::vector<float> lcol(4 * std::max<uint32_t>(num_lights, 1), 0.0f);   // c0 of every light (kLtRegular)
+    for (uint32_t i = 0; i < num_lights; i++) std::memcpy(&lcol[4 * i], &lt[28 * i + 12], 12);
+    ST_TRY(c->light_col.upload(lcol.data(), lcol.size() * 4, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // host vectors go out of scope
+
+    SceneDev& s = c->sdev;
+    s.lights = c->lights.as<float4>();
+    s.num_lights = num_lights;
+    s.light_types = types;
+    s.light_c2 = c->light_c2.as<float4>();
+    s.lights_grid = grid ? 1u : 0u;
+    s.light_c4 = c->light_c4.as<float4>();
+    s.lights_pgram = pgram ? 1u : 0u;
+    s.lights_regular = reg.ok ? 1u : 0u;
+    s.grid_ny_log2 = reg.ny_log2;
+    s.grid_start = make_float4(reg.start[0], reg.start[1], reg.start[2], 0.0f);
+    s.grid_s01 = make_float4(reg.s01[0], reg.s01[1], reg.s01[2], 0.0f);
+    s.grid_s02 = make_float4(reg.s02[0], reg.s02[1], reg.s02[2], 0.0f);
+    s.light_col = c->light_col.as<float4>();
+    // w = p / (1/L) (light.cpp:80) equals p * L exactly when 1/L is a power of two
+    s.light_scale = (num_lights && (num_lights & (num_lights - 1)) == 0) ? (float)num_lights : 0.0f;
+    s.lights_finite = 1u;
+    for (uint32_t i = 0; i < 28 * num_lights; i++)
+        if (!std::isfinite(lt[i]) && (i % 4) != 3) s.lights_finite = 0u;
+    // every product colour x kd / colour x ks stays finite (with a margin for the mix() rounding of segment /
+    // parallelogram colours): shade() may then skip its per-component NaN tests for finite dotNL and pow
+    {
+        double cmax = 0.0;
+        bool finite = c->shade_k_finite;
+        for (uint32_t i = 0; i < num_lights; i++)
+            for (int r = 3; r < 7; r++)
+                for (int a = 0; a < 3; a++) {
+                    const float v = lt[28 * i + 4 * r + a];
+                    finite = finite && std::isfinite(v);
+                    cmax = std::max(cmax, (double)std::fabs(v));
+                }
+        s.shade_finite = (finite && cmax * c->shade_kmax <= 0x1p120) ? 1u : 0u;
+        s.miss_shade_zero = (s.lights_finite && cmax <= 0x1p126 && c->miss_mat_zero) ? 1u : 0u;
+    }
+    c->scene_gen = ++g_scene_gens;   // frame handles written so far name the table this one replaced
+    return RESTIR_OK;
+}
+
 restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes, uint32_t num_meshes,
                                         const restir_light* lights, uint32_t num_lights, const restir_texture* textures,
                                         uint32_t num_textures) {
@@ -1157,14 +1278,35 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
     std::vector<BvhTriangle> tris;
     std::vector<float> n0, n1, n2;   // float4 records
     std::vector<float> tuv;          // 2 float4 per triangle: (t0.xy, t1.xy), (t2.xy, 0, 0)
+    // restir_update_meshes' view of the same: all vertices back to back, per triangle its three indices into them + the mesh
+    std::vector<float> vpos, vnrm;
+    std::vector<uint32_t> tri_idx;
+    std::vector<restir_ctx::MeshKeep> mesh_keep(num_meshes);
     for (uint32_t m = 0; m < num_meshes; m++) {
         const restir_mesh& mesh = meshes[m];
         if (mesh.num_triangles && (!mesh.positions || !mesh.normals || !mesh.triangles))
             return fail(RESTIR_ERR_INVALID, "mesh %u: null arrays", m);
+        restir_ctx::MeshKeep& mk = mesh_keep[m];
+        mk.first_vertex = (uint32_t)(vpos.size() / 3);
+        mk.num_vertices = mesh.num_vertices;
+        mk.referenced.assign(mesh.num_vertices, 0);
+        if ((uint64_t)mk.first_vertex + mesh.num_vertices >= (1ull << 31))
+            return fail(RESTIR_ERR_INVALID, "too many vertices");
+        vpos.resize(vpos.size() + 3 * (size_t)mesh.num_vertices, 0.0f);
+        vnrm.resize(vnrm.size() + 3 * (size_t)mesh.num_vertices, 0.0f);
+        if (mesh.num_vertices && mesh.num_triangles) {   // (a mesh without triangles: its arrays are never read, as before)
+            std::memcpy(&vpos[3 * (size_t)mk.first_vertex], mesh.positions, 12 * (size_t)mesh.num_vertices);
+            std::memcpy(&vnrm[3 * (size_t)mk.first_vertex], mesh.normals, 12 * (size_t)mesh.num_vertices);
+        }
         for (uint32_t i = 0; i < mesh.num_triangles; i++) {
             const uint32_t* t = &mesh.triangles[3 * i];
             if (t[0] >= mesh.num_vertices || t[1] >= mesh.num_vertices || t[2] >= mesh.num_vertices)
                 return fail(RESTIR_ERR_INVALID, "mesh %u triangle %u: vertex index out of range", m, i);
+            for (int k = 0; k < 3; k++) {
+                mk.referenced[t[k]] = 1;
+                tri_idx.push_back(mk.first_vertex + t[k]);
+            }
+            tri_idx.push_back(m);
             BvhTriangle bt;
             std::memcpy(bt.v0, &mesh.positions[3 * t[0]], 12);
             std::memcpy(bt.v1, &mesh.positions[3 * t[1]], 12);
@@ -1227,18 +1369,7 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
         miss.transparency = 1.0f;
         put_material(num_meshes, miss);
     }
-    // lights: 7 float4 records
-    std::vector<float> lt(28 * std::max<uint32_t>(num_lights, 1), 0.0f);
-    uint32_t types = 0;
-    for (uint32_t i = 0; i < num_lights; i++) {
-        const restir_light& l = lights[i];
-        if (l.type > RESTIR_LIGHT_PARALLELOGRAM) return fail(RESTIR_ERR_INVALID, "light %u: bad type %u", i, l.type);
-        types |= 1u << l.type;
-        float* o = &lt[28 * i];
-        const float* src[7] = {l.p0, l.p1, l.p2, l.c0, l.c1, l.c2, l.c3};
-        for (int r = 0; r < 7; r++) { std::memcpy(&o[4 * r], src[r], 12); o[4 * r + 3] = 0.0f; }
-        o[3] = u2f(l.type);
-    }
+    ST_TRY(check_lights(lights, num_lights));
     if (n0.empty()) { n0.assign(4, 0.0f); n1.assign(4, 0.0f); n2.assign(4, 0.0f); }
     std::vector<float> nodes = bvh.nodes;
     if (nodes.empty()) nodes.assign(8, 0.0f);
@@ -1259,35 +1390,6 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
     ST_TRY(c->tri_n1.upload(n1.data(), n1.size() * 4, c->stream));
     ST_TRY(c->tri_n2.upload(n2.data(), n2.size() * 4, c->stream));
     ST_TRY(c->materials.upload(mats.data(), mats.size() * 4, c->stream));
-    ST_TRY(c->lights.upload(lt.data(), lt.size() * 4, c->stream));
-    // the compact light table of the RIS kernels' point and grid forms (kernels.hip kLtPoint / kLtGrid): rows 0 and 3
-    // of every record.  A light grid (the reference's regularLightGrid, scene.cpp:5-28): every light a parallelogram
-    // with light 0's edges and one colour at all four of its corners, bit for bit.
-    // Parallelograms with one colour at all four corners (kLtPgram: rows 0..3 of every record) are the
-    // reference's default nightclub set (scene.cpp:30-66); a grid also shares light 0's edges.
-    bool pgram = num_lights > 0 && types == (1u << RESTIR_LIGHT_PARALLELOGRAM);
-    for (uint32_t i = 0; pgram && i < num_lights; i++) {
-        const float* o = &lt[28 * i];
-        pgram = std::memcmp(o + 16, o + 12, 3 * sizeof(float)) == 0 && std::memcmp(o + 20, o + 12, 3 * sizeof(float)) == 0 &&
-                std::memcmp(o + 24, o + 12, 3 * sizeof(float)) == 0;
-    }
-    bool grid = pgram;
-    for (uint32_t i = 0; grid && i < num_lights; i++) grid = std::memcmp(&lt[28 * i + 4], &lt[4], 8 * sizeof(float)) == 0;
-    const RegularGrid reg = grid ? find_regular_grid(lt, num_lights) : RegularGrid{};
-    std::vector<float> lc4(16 * std::max<uint32_t>(pgram ? num_lights : 1u, 1u), 0.0f);
-    for (uint32_t i = 0; pgram && i < num_lights; i++) std::memcpy(&lc4[16 * i], &lt[28 * i], 64);
-    ST_TRY(c->light_c4.upload(lc4.data(), lc4.size() * 4, c->stream));
-    // two planes (SceneDev::light_c2): rows 0 of every light, then rows 3 -- a random light's 16-byte read from an LDS
-    // copy then lands on one of 16 bank groups instead of 8 (32-byte records)
-    std::vector<float> lc2(8 * std::max<uint32_t>(num_lights, 1), 0.0f);
-    for (uint32_t i = 0; i < num_lights; i++) {
-        std::memcpy(&lc2[4 * i], &lt[28 * i], 16);
-        std::memcpy(&lc2[4 * (num_lights + i)], &lt[28 * i + 12], 16);
-    }
-    ST_TRY(c->light_c2.upload(lc2.data(), lc2.size() * 4, c->stream));
-    std::vector<float> lcol(4 * std::max<uint32_t>(num_lights, 1), 0.0f);   // c0 of every light (kLtRegular)
-    for (uint32_t i = 0; i < num_lights; i++) std::memcpy(&lcol[4 * i], &lt[28 * i + 12], 12);
-    ST_TRY(c->light_col.upload(lcol.data(), lcol.size() * 4, c->stream));
     // textures: texels as float4, images back to back; (width, height, first texel, 0) per image
     std::vector<float> texels;
     std::vector<uint32_t> dims;
@@ -1313,7 +1415,55 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
     ST_TRY(c->tex_texels.upload(texels.data(), texels.size() * 4, c->stream));
     ST_TRY(c->tex_dims.upload(dims.data(), dims.size() * 4, c->stream));
     ST_TRY(c->tri_uv.upload(tuv.data(), tuv.size() * 4, c->stream));
+    // restir_update_meshes' tables (refit.h RefitDev): the topology a refit keeps.  Preorder: node i's subtree is
+    // [i, miss(i)), its triangles one contiguous range of BVH-order slots, its children i + 1 and miss(i + 1).
+    const uint32_t NN = bvh.num_nodes;
+    std::vector<uint32_t> topo(2 * std::max<size_t>(NN, 1), 0u), range(topo.size(), 0u), depth(std::max<size_t>(NN, 1), 0u);
+    for (uint32_t i = NN; i-- > 0;) {
+        const uint32_t miss = f2u(bvh.nodes[8 * (size_t)i + 3]), leaf = f2u(bvh.nodes[8 * (size_t)i + 7]);
+        topo[2 * i] = miss; topo[2 * i + 1] = leaf;
+        if (leaf) {
+            range[2 * i] = leaf & 0xFFFFFFu; range[2 * i + 1] = leaf >> 24;
+        } else {
+            const uint32_t right = f2u(bvh.nodes[8 * (size_t)(i + 1) + 3]);
+            range[2 * i] = range[2 * (i + 1)];
+            range[2 * i + 1] = range[2 * (i + 1) + 1] + range[2 * right + 1];
+        }
+    }
+    uint32_t levels = NN ? 1u : 0u;
+    for (uint32_t i = 0; i < NN; i++)
+        if (!topo[2 * i + 1]) {
+            depth[i + 1] = depth[topo[2 * (i + 1)]] = depth[i] + 1u;
+            levels = std::max(levels, depth[i] + 2u);
+        }
+    std::vector<uint32_t> level_start(levels + 1, 0u), level_nodes(std::max<size_t>(NN, 1), 0u);
+    for (uint32_t i = 0; i < NN; i++) level_start[levels - 1u - depth[i] + 1u]++;   // level 0 = the deepest
+    for (uint32_t l = 0; l < levels; l++) level_start[l + 1] += level_start[l];
+    {
+        std::vector<uint32_t> at(level_start.begin(), level_start.end() - 1);
+        for (uint32_t i = 0; i < NN; i++) level_nodes[at[levels - 1u - depth[i]]++] = i;
+    }
+    std::vector<uint32_t> order = bvh.tri_order;
+    if (order.empty()) order.assign(1, 0u);
+    if (tri_idx.empty()) tri_idx.assign(4, 0u);
+    if (vpos.empty()) { vpos.assign(3, 0.0f); vnrm.assign(3, 0.0f); }
+    ST_TRY(c->vpos.upload(vpos.data(), vpos.size() * 4, c->stream));
+    ST_TRY(c->vnrm.upload(vnrm.data(), vnrm.size() * 4, c->stream));
+    ST_TRY(c->tri_idx.upload(tri_idx.data(), tri_idx.size() * 4, c->stream));
+    ST_TRY(c->tri_order.upload(order.data(), order.size() * 4, c->stream));
+    ST_TRY(c->topo.upload(topo.data(), topo.size() * 4, c->stream));
+    ST_TRY(c->node_range.upload(range.data(), range.size() * 4, c->stream));
+    ST_TRY(c->level_nodes.upload(level_nodes.data(), level_nodes.size() * 4, c->stream));
+    ST_TRY(c->level_start.upload(level_start.data(), level_start.size() * 4, c->stream));
+    if (!refit_fits_lds(NN, (uint32_t)T)) ST_TRY(c->refit_raw.ensure((size_t)NN * 32));
     HIP_TRY(hipStreamSynchronize(c->stream));   // host vectors go out of scope
+    c->bvh_levels = levels;
+    c->topo_q_ok = q_ok;
+    for (uint32_t m = 0; m < num_meshes; m++) {
+        restir_ctx::MeshKeep& mk = mesh_keep[m];
+        mk.normals_bounded = normals_bounded_of(&vnrm[3 * (size_t)mk.first_vertex], mk);
+    }
+    c->mesh_keep = std::move(mesh_keep);
 
     SceneDev& s = c->sdev;
     s.nodes = c->nodes.as<float4>();
@@ -1337,56 +1487,144 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
     s.num_textures = num_textures;
     s.gbuf_uv = nullptr;   // per launch (scene_for)
     s.tex_on = 0u;
-    s.lights = c->lights.as<float4>();
-    s.num_lights = num_lights;
-    s.light_types = types;
-    s.light_c2 = c->light_c2.as<float4>();
-    s.lights_grid = grid ? 1u : 0u;
-    s.light_c4 = c->light_c4.as<float4>();
-    s.lights_pgram = pgram ? 1u : 0u;
-    s.lights_regular = reg.ok ? 1u : 0u;
-    s.grid_ny_log2 = reg.ny_log2;
-    s.grid_start = make_float4(reg.start[0], reg.start[1], reg.start[2], 0.0f);
-    s.grid_s01 = make_float4(reg.s01[0], reg.s01[1], reg.s01[2], 0.0f);
-    s.grid_s02 = make_float4(reg.s02[0], reg.s02[1], reg.s02[2], 0.0f);
-    s.light_col = c->light_col.as<float4>();
-    // w = p / (1/L) (light.cpp:80) equals p * L exactly when 1/L is a power of two
-    s.light_scale = (num_lights && (num_lights & (num_lights - 1)) == 0) ? (float)num_lights : 0.0f;
-    s.lights_finite = 1u;
-    for (uint32_t i = 0; i < 28 * num_lights; i++)
-        if (!std::isfinite(lt[i]) && (i % 4) != 3) s.lights_finite = 0u;
-    // every product colour x kd / colour x ks stays finite (with a margin for the mix() rounding of segment /
-    // parallelogram colours): shade() may then skip its per-component NaN tests for finite dotNL and pow
+    // the materials' and texels' part of shade_finite and miss_shade_zero (upload_lights has the lights' part)
     {
-        double cmax = 0.0, kmax = 0.0;
+        double kmax = 0.0;
         bool finite = true;
-        for (uint32_t i = 0; i < num_lights; i++)
-            for (int r = 3; r < 7; r++)
-                for (int a = 0; a < 3; a++) {
-                    const float v = lt[28 * i + 4 * r + a];
-                    finite = finite && std::isfinite(v);
-                    cmax = std::max(cmax, (double)std::fabs(v));
-                }
         for (uint32_t m = 0; m <= num_meshes; m++)
             for (int a : {0, 1, 2, 4, 5, 6}) {
                 const float v = mats[12 * m + a];
                 finite = finite && std::isfinite(v);
                 kmax = std::max(kmax, (double)std::fabs(v));
             }
-        finite = finite && tfinite;   // texels are diffuse colours too
-        kmax = std::max(kmax, tmax);
-        s.shade_finite = (finite && cmax * kmax <= 0x1p120) ? 1u : 0u;
-        bool miss_zero = s.lights_finite && cmax <= 0x1p126;
-        for (int a : {0, 1, 2, 4, 5, 6}) miss_zero = miss_zero && mats[12 * num_meshes + a] == 0.0f;
-        s.miss_shade_zero = miss_zero ? 1u : 0u;
+        c->shade_k_finite = finite && tfinite;   // texels are diffuse colours too
+        c->shade_kmax = std::max(kmax, tmax);
+        c->miss_mat_zero = true;
+        for (int a : {0, 1, 2, 4, 5, 6}) c->miss_mat_zero = c->miss_mat_zero && mats[12 * num_meshes + a] == 0.0f;
     }
+    ST_TRY(upload_lights(c, lights, num_lights));
     s.normals_bounded = 1u;
     for (const std::vector<float>* nv : {&n0, &n1, &n2})
         for (size_t i = 0; i < nv->size(); i++)
             if ((i % 4) != 3 && !(std::fabs((*nv)[i]) <= 0x1p125f)) s.normals_bounded = 0u;
-    static std::atomic<uint64_t> scene_gens{0};
-    c->scene_gen = ++scene_gens;
+    c->geom_gen = ++g_scene_gens;
     c->has_scene = true;
+    return RESTIR_OK;
+}
+
+static RefitDev refit_dev(const restir_ctx* c) {
+    const SceneDev& s = c->sdev;
+    RefitDev r{};
+    r.num_nodes = s.num_nodes; r.num_tris = s.num_tris; r.q_ok = c->topo_q_ok ? 1u : 0u;
+    r.vpos = c->vpos.as<float>(); r.vnrm = c->vnrm.as<float>();
+    r.tri_idx = c->tri_idx.as<uint4>(); r.tri_order = c->tri_order.as<uint32_t>();
+    r.topo = c->topo.as<uint2>(); r.range = c->node_range.as<uint2>();
+    r.level_nodes = c->level_nodes.as<uint32_t>(); r.level_start = c->level_start.as<uint32_t>();
+    r.levels = c->bvh_levels;
+    r.nodes = c->nodes.as<float4>(); r.nodes_q = c->nodes_q.as<uint4>();
+    r.tri_v0 = c->tri_v0.as<float4>(); r.tri_e1 = c->tri_e1.as<float4>(); r.tri_e2 = c->tri_e2.as<float4>();
+    r.tri_n0 = c->tri_n0.as<float4>(); r.tri_n1 = c->tri_n1.as<float4>(); r.tri_n2 = c->tri_n2.as<float4>();
+    r.raw = c->refit_raw.as<float4>();
+    return r;
+}
+
+// New vertex positions (and normals) for meshes of the uploaded scene: the vertices go to the device and refit.hip's
+// kernels recompute the triangle records, the boxes and the quantized nodes there, in stream order behind every frame
+// enqueued so far.  The host reads back the root's padded box (32 bytes, the one synchronisation) for SceneDev's
+// by-value quantization grid.
+restir_status restir_update_meshes(restir_ctx* c, const restir_mesh_update* updates, uint32_t count) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (count && !updates) return fail(RESTIR_ERR_INVALID, "updates is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_update_meshes before restir_set_scene");
+    if (count == 0) return RESTIR_OK;
+    // the whole input is checked before anything changes
+    std::vector<uint8_t> named(c->mesh_keep.size(), 0);
+    bool any_normals = false;
+    for (uint32_t u = 0; u < count; u++) {
+        const restir_mesh_update& up = updates[u];
+        if (up.mesh >= c->mesh_keep.size())
+            return fail(RESTIR_ERR_INVALID, "update %u: mesh %u of %zu", u, up.mesh, c->mesh_keep.size());
+        const restir_ctx::MeshKeep& mk = c->mesh_keep[up.mesh];
+        if (up.num_vertices != mk.num_vertices)
+            return fail(RESTIR_ERR_INVALID, "update %u: mesh %u was uploaded with %u vertices, not %u", u, up.mesh, mk.num_vertices,
+                        up.num_vertices);
+        if (named[up.mesh]) return fail(RESTIR_ERR_INVALID, "update %u: mesh %u named twice", u, up.mesh);
+        named[up.mesh] = 1;
+        if (up.num_vertices && !up.positions) return fail(RESTIR_ERR_INVALID, "update %u: positions is NULL", u);
+        // finite positions: min / max are then independent of the order the device evaluates them in
+        for (size_t i = 0; i < 3 * (size_t)up.num_vertices; i++)
+            if (!std::isfinite(up.positions[i]))
+                return fail(RESTIR_ERR_INVALID, "update %u: mesh %u vertex %zu has a non-finite position", u, up.mesh, i / 3);
+        any_normals = any_normals || (up.normals && up.num_vertices);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    c->gbuf.valid = false;   // the kept G-buffer is the old geometry's: the next frame traces
+    c->geom_gen = ++g_scene_gens;
+    for (uint32_t u = 0; u < count; u++) {
+        const restir_mesh_update& up = updates[u];
+        restir_ctx::MeshKeep& mk = c->mesh_keep[up.mesh];
+        if (!up.num_vertices) continue;
+        const size_t off = 12 * (size_t)mk.first_vertex, bytes = 12 * (size_t)up.num_vertices;
+        HIP_TRY(hipMemcpyAsync(c->vpos.as<char>() + off, up.positions, bytes, hipMemcpyHostToDevice, c->stream));
+        if (up.normals) {
+            HIP_TRY(hipMemcpyAsync(c->vnrm.as<char>() + off, up.normals, bytes, hipMemcpyHostToDevice, c->stream));
+            mk.normals_bounded = normals_bounded_of(up.normals, mk);
+        }
+    }
+    SceneDev& s = c->sdev;
+    const RefitDev r = refit_dev(c);
+    HIP_TRY(launch_refit_triangles(r, any_normals, c->stream));
+    HIP_TRY(launch_refit_boxes(r, c->stream));
+    float root[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (s.num_nodes) HIP_TRY(hipMemcpyAsync(root, c->nodes.p, sizeof(root), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's arrays may be freed on return; the root box is here
+    if (s.num_nodes) {
+        // quantize_nodes' grid over the new padded root; its q_ok beyond the topology's is a finite grid
+        FlatBvh rootb;
+        rootb.num_nodes = 1;
+        rootb.nodes.assign(root, root + 8);
+        rootb.nodes[7] = u2f(1u << 24);   // (any leaf word that fits)
+        const QuantizedNodes q = quantize_nodes(rootb);
+        s.nodes_q_ok = (c->topo_q_ok && q.ok) ? 1u : 0u;
+        if (s.nodes_q_ok) {
+            s.q_lo = make_float4(q.lo[0], q.lo[1], q.lo[2], 0.0f);
+            s.q_s = make_float4(q.s[0], q.s[1], q.s[2], 0.0f);
+        }
+    }
+    if (any_normals) {
+        s.normals_bounded = 1u;
+        for (const restir_ctx::MeshKeep& mk : c->mesh_keep) s.normals_bounded = s.normals_bounded && mk.normals_bounded ? 1u : 0u;
+    }
+    return RESTIR_OK;
+}
+
+// Another light list over the same geometry: the tree, the triangle records and the kept G-buffer stay.
+restir_status restir_set_lights(restir_ctx* c, const restir_light* lights, uint32_t num_lights) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (num_lights && !lights) return fail(RESTIR_ERR_INVALID, "lights is NULL");
+    ST_TRY(check_lights(lights, num_lights));
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_set_lights before restir_set_scene");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // previous frames (either slot) may still read the old tables
+    return upload_lights(c, lights, num_lights);
+}
+
+restir_status restir_debug_scene_download(restir_ctx* c, float* nodes, uint32_t* nodes_q, float* tri_v0, float* tri_e1,
+                                          float* tri_e2, float* tri_n0, float* tri_n1, float* tri_n2) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_debug_scene_download before restir_set_scene");
+    HIP_TRY(hipSetDevice(c->device));
+    const SceneDev& s = c->sdev;
+    const size_t nb = (size_t)s.num_nodes * 32, qb = s.nodes_q_ok ? (size_t)s.num_nodes * 16 : 0, tb = (size_t)s.num_tris * 16;
+    const struct { void* dst; const void* src; size_t bytes; } copies[] = {
+        {nodes, s.nodes, nb}, {nodes_q, s.nodes_q, qb}, {tri_v0, s.tri_v0, tb}, {tri_e1, s.tri_e1, tb},
+        {tri_e2, s.tri_e2, tb}, {tri_n0, s.tri_n0, tb}, {tri_n1, s.tri_n1, tb}, {tri_n2, s.tri_n2, tb}};
+    for (const auto& cp : copies)
+        if (cp.dst && cp.bytes) HIP_TRY(hipMemcpyAsync(cp.dst, cp.src, cp.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return RESTIR_OK;
 }
 
@@ -1560,7 +1798,9 @@ static restir_status render_mis_tile(restir_ctx* c, const restir_camera* cam, co
 static Ask frame_ris_ask(const restir_ctx* c, const SceneDev& s, const FrameBufs& fb, bool temporal) {
     Ask a;
     a.rp_out = fb.rp(0) != nullptr;
-    a.flags = c->tuning.miss_tiles && !temporal && s.normals_bounded && !fb.records;
+    // (no lights: no tile's RIS result is the known miss -- the kernel would flag every tile 1 -- and a context that has
+    // rendered a lit scene holds that scene's flags: the passes must not read any)
+    a.flags = c->tuning.miss_tiles && !temporal && s.normals_bounded && !fb.records && s.num_lights != 0u;
     return a;
 }
 
@@ -1579,13 +1819,16 @@ static restir_status ensure_tile_flags(restir_ctx* c, const Route& ris, const Re
 static restir_ctx::GbufView gbuf_view(const restir_ctx* c, const SceneDev& s, const CameraDev& cam, uint32_t width,
                                       uint32_t height, const restir_tile& t, const Route& ris, const uint8_t* tmiss) {
     restir_ctx::GbufView v;
-    v.scene_gen = c->scene_gen;
+    v.scene_gen = c->geom_gen;   // the planes hold geometry alone: another light list leaves them valid
     const float camf[9] = {cam.quat.x, cam.quat.y, cam.quat.z, cam.quat.w, cam.origin[0], cam.origin[1], cam.origin[2],
                            cam.half_w, cam.half_h};
     std::memcpy(v.cam, camf, sizeof(v.cam));
     v.width = width; v.height = height;
     v.tile = t;
     v.tex_on = s.tex_on;
+    // a tile is flagged background when its pixels' RIS result is the known miss: with lights, and finite ones
+    // (kernels.hip k_primary_ris); the G-buffer records themselves hold geometry alone
+    v.light_facts = (s.num_lights != 0u ? 1u : 0u) | (s.lights_finite ? 2u : 0u);
     v.flags = ris.flags && tmiss != nullptr;
     v.skip = ris.skip;
     v.map2d = ris.map2d; v.xcd_rows = ris.xcd_rows; v.xcd_cols = ris.xcd_cols; v.items = ris.grid;
@@ -1603,7 +1846,7 @@ static bool gbuf_reusable(const restir_ctx::GbufView& have, const restir_ctx::Gb
            have.width == want.width && have.height == want.height && a.global_width == b.global_width &&
            a.global_height == b.global_height && a.gx0 == b.gx0 && a.gy0 == b.gy0 && a.gwidth == b.gwidth &&
            a.gheight == b.gheight && a.x0 == b.x0 && a.y0 == b.y0 && a.width == b.width && a.height == b.height &&
-           have.tex_on == want.tex_on && have.map2d == want.map2d && have.xcd_rows == want.xcd_rows &&
+           have.tex_on == want.tex_on && have.light_facts == want.light_facts && have.map2d == want.map2d && have.xcd_rows == want.xcd_rows &&
            have.xcd_cols == want.xcd_cols && have.items == want.items && have.n_t == want.n_t && have.p_mat == want.p_mat &&
            have.uv == want.uv && (!want.flags || (have.flags && have.tmiss == want.tmiss)) &&
            (!(have.skip & 2u) || (want.skip & 2u));

@@ -77,6 +77,48 @@ class Renderer:
               "restir_set_scene_textured")
         self._scene_keep = (meshes, lights, keep, texs, tkeep)
 
+    def update_meshes(self, meshes: dict) -> None:
+        """restir_update_meshes: {mesh index: (positions [V][3], normals [V][3] or None)} -- new vertex positions (and
+        normals) for meshes of the scene set; the device refits the BVH, nothing is rebuilt or uploaded again."""
+        FP = C.POINTER(C.c_float)
+        ups = (_abi.MeshUpdate * max(1, len(meshes)))()
+        keep = []
+        for i, (m, (pos, nrm)) in enumerate(meshes.items()):
+            p = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+            keep.append(p)
+            ups[i].mesh, ups[i].num_vertices, ups[i].positions = int(m), len(p), p.ctypes.data_as(FP)
+            if nrm is not None:
+                n = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 3)
+                if len(n) != len(p):
+                    raise ValueError(f"mesh {m}: {len(n)} normals for {len(p)} positions")
+                keep.append(n)
+                ups[i].normals = n.ctypes.data_as(FP)
+        check(self.lib, self.lib.restir_update_meshes(self.ctx, ups, len(meshes)), "restir_update_meshes")
+
+    def set_lights(self, lights) -> None:
+        """restir_set_lights: another list of _abi.Light over the same geometry; the BVH and the kept G-buffer stay."""
+        arr = (_abi.Light * max(1, len(lights)))()
+        for i, l in enumerate(lights):
+            arr[i] = l
+        check(self.lib, self.lib.restir_set_lights(self.ctx, arr, len(lights)), "restir_set_lights")
+
+    def debug_scene(self) -> dict:
+        """restir_debug_scene_download: the device's scene arrays as they stand -- nodes [n][8] float32, nodes_q [n][4]
+        uint32 (None without quantized nodes), tri_v0 / tri_e1 / tri_e2 [T][4] in BVH order, tri_n0 / tri_n1 / tri_n2
+        [T][4] in the upload's order."""
+        info = self.scene_info()
+        n, t = info.num_nodes, info.num_tris
+        out = {"nodes": np.zeros((n, 8), np.float32), "nodes_q": np.zeros((n, 4), np.uint32) if info.nodes_q_ok else None}
+        for k in ("tri_v0", "tri_e1", "tri_e2", "tri_n0", "tri_n1", "tri_n2"):
+            out[k] = np.zeros((t, 4), np.float32)
+        FP, UP = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        ptr = lambda a, ty: a.ctypes.data_as(ty) if a is not None and a.size else None
+        check(self.lib, self.lib.restir_debug_scene_download(
+            self.ctx, ptr(out["nodes"], FP), ptr(out["nodes_q"], UP),
+            *[ptr(out[k], FP) for k in ("tri_v0", "tri_e1", "tri_e2", "tri_n0", "tri_n1", "tri_n2")]),
+            "restir_debug_scene_download")
+        return out
+
     def scene_info(self) -> _abi.SceneInfo:
         """restir_scene_info: what set_scene derived from the scene -- BVH size and LDS bytes, the light types present,
         the compact light-table forms it qualifies for, light_scale, nodes_q_ok (the shadow rays' quantized nodes
