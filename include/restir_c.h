@@ -353,6 +353,43 @@ restir_status restir_render_mis_tile(restir_ctx* ctx, const restir_camera* cam, 
 restir_status restir_render_mis_tiles(restir_ctx* ctx, const restir_camera* cam, const restir_features* features,
                                       const restir_tile_layout* layout, float* out_rgb);
 
+/* ---- motion-compensated temporal reuse: a predecessor grid reprojected to another camera --------------------
+ * restir_render combines pixel p with the predecessor's pixel p (temporalReuse, render_utils.cpp:142-177), which is
+ * right while the camera stands still.  restir_frame_reproject gathers a NEW predecessor grid for a camera that moved:
+ * *out (of prev's size and N) holds at every pixel the N sub-reservoirs of `prev` at the pixel where the current
+ * camera's surface point was seen from cam_prev, or empty reservoirs (all-zero words); hand it to
+ * restir_render(..., prev = *out, ...) as `prev` would be, and release it like any frame.  The call consumes no frame
+ * index and draws no random number, leaves `prev` untouched (it orders itself after prev's producer and records its
+ * read, as a render does), and never touches the kept G-buffer ("gbuf.reuse"): it traces both cameras into scratch
+ * planes of its own, so the next restir_render traces again.  Per pixel p = (x, y), y = 0 the bottom row:
+ *   1. (N_cur, t_cur, P, material) = the G-buffer record of cam_cur at p; a primary-ray miss -> empty (reason 0);
+ *   2. v = P - o_prev, c = conj(q_prev) * v (quat * vec3); !(c.z > 0) -> empty (1, behind the camera);
+ *   3. r = c.x / c.z, nx = (-r) / half_w, s = c.y / c.z, ny = s / half_h,
+ *      fx = floorf(((nx + 1) * 0.5f) * W + 0.5f), fy likewise with ny and H -- the nearest sample position, single
+ *      float32 operations in this order; !(0 <= fx < W && 0 <= fy < H) (NaN included) -> empty (2, off-screen);
+ *   4. (n_prev, t_prev, material) = the record of cam_prev at q = (fx, fy), traced over the geometry AS IT STANDS NOW
+ *      (after restir_update_meshes a moved mesh is validated against its new place); a miss -> empty (3);
+ *   5. d = glm::length(v); fabsf(1 - t_prev / d) > 0.1f -> empty (4, depth), else dot(n_prev, N_cur) < 0.90630778703f
+ *      -> empty (5, normal): render_utils.cpp:114-118 with the current depth replaced by d, whatever
+ *      unbiased_combination says;
+ *   6. otherwise prev's sub-reservoirs at q, bit for bit.
+ * When prev carries frame handles ("spatial.handles") they are gathered too -- an empty pixel gets the zero sample's
+ * handle (W = 0, M = 0, the light count as index) -- so the fused handle-reading temporal kernel still runs.
+ * out_map (nullable, host, W * H words): the flat index fy * W + fx of q, or 0xFFFFFFFF - reason for an empty pixel;
+ * with it the call synchronises, without it it only enqueues.  With timing enabled the two primary-ray launches count
+ * under RESTIR_K_PRIMARY; the gather itself is not timed.
+ * RESTIR_ERR_INVALID: a NULL argument, a predecessor on another device, a camera whose derived frame is not finite;
+ * RESTIR_ERR_STATE: before a scene is set; RESTIR_ERR_UNSUPPORTED: a predecessor that is a screen tile (its view is not
+ * the whole image) or in the per-pixel records layout ("layout.records").
+ *
+ * restir_reproject_pixel (pure host): steps 2-3 for one point P and the predecessor's derived camera -- the kernel's
+ * own text (csrc/reproject.h), bit for bit.  *x, *y = the source pixel, or both 0xFFFFFFFF - reason (1 or 2);
+ * *depth (nullable) = d of step 5.  RESTIR_ERR_INVALID for a NULL argument (depth aside) or W * H == 0. */
+restir_status restir_frame_reproject(restir_ctx* ctx, const restir_frame* prev, const restir_camera* cam_prev,
+                                     const restir_camera* cam_cur, restir_frame** out, uint32_t* out_map);
+restir_status restir_reproject_pixel(const restir_camera_frame* prev_cam, uint32_t W, uint32_t H, const float P[3],
+                                     uint32_t* x, uint32_t* y, float* depth);
+
 restir_status restir_frame_retain(restir_frame* frame);
 /* Drops a reference.  The last one hands the grid's device records back to the producing context for re-use,
  * ordered on the GPU after every kernel that wrote or read them (no host or device-wide synchronisation). */

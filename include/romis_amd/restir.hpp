@@ -283,6 +283,25 @@ inline std::shared_ptr<ReservoirGrid> renderReSTIR(Renderer& r, const std::share
     return std::make_shared<ReservoirGrid>(next);
 }
 
+// Motion-compensated temporal reuse (restir_frame_reproject): the predecessor grid `prev`, rendered from prevCamera,
+// gathered to where `camera` sees its surface points -- pass the result to renderReSTIR as `prev` when the camera
+// moved between the frames.  map (nullable): per pixel (rows y = 0 bottom) the source pixel's flat index or
+// 0xFFFFFFFF - reason, which makes the call synchronise.
+inline std::shared_ptr<ReservoirGrid> reprojectGrid(Renderer& r, const std::shared_ptr<ReservoirGrid>& prev,
+                                                    const Camera& prevCamera, const Camera& camera,
+                                                    std::vector<uint32_t>* map = nullptr) {
+    if (!prev) return nullptr;
+    if (map) {
+        uint32_t w = 0, h = 0;
+        check(restir_frame_info(prev->handle(), &w, &h, nullptr, nullptr, nullptr, nullptr, nullptr), "restir_frame_info");
+        map->assign(size_t(w) * h, 0u);
+    }
+    restir_frame* out = nullptr;
+    check(restir_frame_reproject(r.handle(), prev->handle(), &prevCamera, &camera, &out, map ? map->data() : nullptr),
+          "restir_frame_reproject");
+    return std::make_shared<ReservoirGrid>(out);
+}
+
 // renderRMIS / renderROMIS (render.cpp:64-265): maxIterationsMIS rounds of initial samples combined over each
 // pixel's neighbourhood into `screen` (features.ray_trace_mode selects the estimator).
 inline void renderMIS(Renderer& r, const Camera& camera, Screen& screen, const Features& features) {

@@ -216,6 +216,10 @@ SIGNATURES = {
                                          C.POINTER(Tile), C.POINTER(C.c_float)]),
     "restir_render_mis_tiles": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Features), C.POINTER(TileLayout),
                                           C.POINTER(C.c_float)]),
+    "restir_frame_reproject": (C.c_int, [_P, _P, C.POINTER(Camera), C.POINTER(Camera), C.POINTER(_P),
+                                         C.POINTER(C.c_uint32)]),
+    "restir_reproject_pixel": (C.c_int, [C.POINTER(CameraFrame), C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "restir_frame_retain": (C.c_int, [_P]),
     "restir_frame_release": (None, [_P]),
     "restir_frame_info": (C.c_int, [_P] + [C.POINTER(C.c_uint32)] * 7),

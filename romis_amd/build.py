@@ -37,11 +37,12 @@ SOURCES = [
     ("restir.cpp", ["-x", "hip"] + DEVICE),
     ("mis.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("refit.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
+    ("reproject.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("bvh.cpp", ["-x", "c++"]),
     ("screen.cpp", ["-x", "c++"]),
 ]
 HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
-           "route.h", "ris_members.h", "refit.h"]
+           "route.h", "ris_members.h", "refit.h", "reproject.h"]
 
 
 def source_hash() -> str:

@@ -29,6 +29,7 @@
 #include "device_math.h"
 #include "launch.h"
 #include "refit.h"
+#include "reproject.h"
 #include "restir_types.h"
 
 namespace romis {
@@ -180,6 +181,7 @@ struct restir_frame {
     // frame handles: the scene upload (restir_ctx::scene_gen) whose light table the sample handles at rec's tail
     // (W, M | light index << 24, after the reservoir planes) index; 0 = none written
     uint64_t hgen = 0;
+    uint32_t hzero = 0;   // that table's light count: the index a handle names the zero sample by (restir_frame_reproject)
     std::shared_ptr<FramePool> pool;   // where rec goes back on release (the producing context's)
     std::mutex mu;
     hipEvent_t ready = nullptr;        // recorded on the producer's stream after its last kernel touching rec
@@ -262,6 +264,9 @@ struct restir_ctx {
     uint32_t tmiss_w = 0, tmiss_h = 0;              // the last frame's computed region when it kept the flags (else 0)
     uint64_t last_px = 0;                           // the last frame's computed pixels
     DevBuf hnd[2];                                  // sample handles of rec[i] (N = 1 point lights, k_spatial1h)
+    // restir_frame_reproject's own scratch: the G-buffer planes of the current (0) and the predecessor's (1) camera and
+    // the map it downloads -- never the frame path's planes, so the kept G-buffer below stays as it is
+    DevBuf rpj_nt[2], rpj_pm[2], rpj_map;
     // The view whose G-buffer n_t, p_mat, uv (textured scenes) and tile flags tmiss hold (tuning "gbuf.reuse"): written
     // after a restir_render frame's fused primary + RIS launch over the SoA planes.  They are a function of these
     // fields and nothing else -- the frame index and the RNG key do not enter -- so a later frame whose fields are
@@ -1053,7 +1058,9 @@ void restir_destroy(restir_ctx* c) {
         std::lock_guard<std::mutex> lk(c->mu);
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
-        for (DevBuf* b : {&c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1]}) b->release();
+        for (DevBuf* b : {&c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
+                          &c->rpj_map})
+            b->release();
         for (DevBuf* b : {&c->nodes, &c->nodes_q, &c->tri_v0, &c->tri_e1, &c->tri_e2, &c->tri_n0, &c->tri_n1, &c->tri_n2,
                           &c->materials, &c->lights, &c->light_c2, &c->light_c4, &c->light_col, &c->tex_texels, &c->tex_dims, &c->tri_uv, &c->uv, &c->n_t, &c->p_mat, &c->ra[0], &c->ra[1], &c->rb[0], &c->rb[1],
                           &c->dbg[0], &c->dbg[1], &c->rgb, &c->halo_scratch, &c->rec[0], &c->rec[1], &c->rp[0], &c->rp[1]})
@@ -2088,6 +2095,7 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
         std::swap(fr->rec, c->rec[cur]);
         fr->records = fb.records;
         fr->hgen = frame_handles ? c->scene_gen : 0u;
+        fr->hzero = s.num_lights;
         *out_next = fr;
     }
     if (out_rgb) {
@@ -2146,6 +2154,119 @@ restir_status restir_render_mis_tiles(restir_ctx* c, const restir_camera* cam, c
                         (size_t)tv.width * 12);
     }
     c->frame_index = frame + 1u;
+    return RESTIR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// motion-compensated temporal reuse (reproject.h; DESIGN.md §6 "Reprojection")
+static bool camera_frame_finite(const restir_camera_frame& cf) {
+    bool ok = std::isfinite(cf.half_w) && std::isfinite(cf.half_h);
+    for (float v : cf.origin) ok = ok && std::isfinite(v);
+    for (float v : cf.quat) ok = ok && std::isfinite(v);
+    return ok;
+}
+
+static ReprojCam reproj_cam(const restir_camera_frame& cf, uint32_t W, uint32_t H) {
+    ReprojCam r{};
+    r.qx = cf.quat[0]; r.qy = cf.quat[1]; r.qz = cf.quat[2]; r.qw = cf.quat[3];
+    r.ox = cf.origin[0]; r.oy = cf.origin[1]; r.oz = cf.origin[2];
+    r.half_w = cf.half_w; r.half_h = cf.half_h;
+    r.W = W; r.H = H;
+    return r;
+}
+
+restir_status restir_reproject_pixel(const restir_camera_frame* prev_cam, uint32_t W, uint32_t H, const float P[3],
+                                     uint32_t* x, uint32_t* y, float* depth) {
+    if (!prev_cam || !P || !x || !y) return fail(RESTIR_ERR_INVALID, "restir_reproject_pixel: NULL argument");
+    if (W == 0 || H == 0) return fail(RESTIR_ERR_INVALID, "restir_reproject_pixel: empty image %ux%u", W, H);
+    uint32_t sx, sy;
+    float d;
+    const uint32_t why = reproject_source(reproj_cam(*prev_cam, W, H), P[0], P[1], P[2], sx, sy, d);
+    *x = why == kReprojOk ? sx : 0xFFFFFFFFu - why;
+    *y = why == kReprojOk ? sy : 0xFFFFFFFFu - why;
+    if (depth) *depth = d;
+    return RESTIR_OK;
+}
+
+restir_status restir_frame_reproject(restir_ctx* c, const restir_frame* prev, const restir_camera* cam_prev,
+                                     const restir_camera* cam_cur, restir_frame** out, uint32_t* out_map) {
+    // the argument checks come first: they need no device
+    if (out) *out = nullptr;
+    if (!out) return fail(RESTIR_ERR_INVALID, "restir_frame_reproject: out is NULL");
+    if (!cam_prev || !cam_cur) return fail(RESTIR_ERR_INVALID, "restir_frame_reproject: camera is NULL");
+    restir_camera_frame cf[2];
+    restir_camera_derive(cam_cur, &cf[0]);
+    restir_camera_derive(cam_prev, &cf[1]);
+    if (!camera_frame_finite(cf[0]) || !camera_frame_finite(cf[1]))
+        return fail(RESTIR_ERR_INVALID, "restir_frame_reproject: a camera's derived frame is not finite");
+    if (!prev) return fail(RESTIR_ERR_INVALID, "restir_frame_reproject: the predecessor frame is NULL");
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (prev->device != c->device)
+        return fail(RESTIR_ERR_INVALID, "temporal predecessor lives on device %d, this context on %d", prev->device, c->device);
+    if (prev->vx0 || prev->vy0 || prev->vw != prev->W || prev->vh != prev->H)
+        return fail(RESTIR_ERR_UNSUPPORTED, "restir_frame_reproject: the predecessor is a screen tile (its view is not the whole image)");
+    if (prev->records)
+        return fail(RESTIR_ERR_UNSUPPORTED, "restir_frame_reproject: the predecessor is in the per-pixel records layout");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_frame_reproject before restir_set_scene");
+    HIP_TRY(hipSetDevice(c->device));
+
+    const hipStream_t st = c->stream;
+    const uint32_t W = prev->W, H = prev->H, N = prev->N;
+    const size_t npx = (size_t)W * H;
+    for (int i = 0; i < 2; i++) {
+        ST_TRY(c->rpj_nt[i].ensure(npx * 16));
+        ST_TRY(c->rpj_pm[i].ensure(npx * 16));
+    }
+    if (out_map) ST_TRY(c->rpj_map.ensure(npx * 4));
+    // both G-buffers by the primary-ray launcher over the geometry as it stands now (the texCoord plane is not needed)
+    SceneDev s = c->sdev;
+    s.gbuf_uv = nullptr;
+    s.tex_on = 0u;
+    const Region view = make_region(W, H, 0, 0, W, H, 0, 0, W, H);
+    const CameraDev camd[2] = {camera_dev(cam_cur), camera_dev(cam_prev)};
+    for (int i = 0; i < 2; i++) {
+        LaunchBufs b;
+        b.cam = &camd[i]; b.origin = camd[i].origin;
+        b.n_t = c->rpj_nt[i].as<float4>(); b.p_mat = c->rpj_pm[i].as<float4>();
+        TIMED(c, RESTIR_K_PRIMARY, launch_primary(route_primary(s, view, c->tuning), s, view, b, st));
+    }
+    ST_TRY(use_prev(prev, c->device, st, c->pool.get()));   // the predecessor's records are complete (its producer's stream)
+    // the new grid's records, sized as ensure_records sizes a planes frame's (reservoir planes, then the handles' tail)
+    const size_t rec_bytes = npx * 2u * N * 16 + (N == 1 ? npx * 8 + 16 : N == 2 ? npx * 16 + 16 : 0);
+    DevBuf rec;
+    if (!c->pool->take(rec_bytes, st, rec)) ST_TRY(rec.ensure(rec_bytes));
+    const bool handles = prev->hgen != 0 && (N == 1 || N == 2);
+    ReprojDev r{};
+    r.prev_cam = reproj_cam(cf[1], W, H);
+    r.N = N;
+    r.miss_mat = s.num_materials - 1u;
+    r.cur_nt = c->rpj_nt[0].as<float4>(); r.cur_pm = c->rpj_pm[0].as<float4>();
+    r.prev_nt = c->rpj_nt[1].as<float4>(); r.prev_pm = c->rpj_pm[1].as<float4>();
+    r.ia = prev->rec.as<float4>(); r.ib = r.ia + npx * N;
+    r.oa = rec.as<float4>(); r.ob = r.oa + npx * N;
+    r.hin = handles ? reinterpret_cast<const float*>(r.ia + 2 * N * npx) : nullptr;
+    r.hout = handles ? reinterpret_cast<float*>(r.oa + 2 * N * npx) : nullptr;
+    r.zero_handle = prev->hzero << 24;
+    r.map = out_map ? c->rpj_map.as<uint32_t>() : nullptr;
+    const hipError_t e = launch_reproject(r, st);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        rec.release();
+        return fail(RESTIR_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+    }
+    used_prev(prev, st, c->pool.get());
+    restir_frame* fr = make_frame(c->pool, c->device, st);
+    fr->W = W; fr->H = H; fr->vx0 = 0; fr->vy0 = 0; fr->vw = W; fr->vh = H; fr->N = N;
+    fr->rec = rec;
+    fr->records = false;
+    fr->hgen = handles ? prev->hgen : 0u;
+    fr->hzero = prev->hzero;
+    *out = fr;
+    if (out_map) {
+        HIP_TRY(hipMemcpyAsync(out_map, c->rpj_map.p, npx * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
     return RESTIR_OK;
 }
 

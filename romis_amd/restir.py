@@ -156,6 +156,23 @@ class Renderer:
         grid = ReservoirGrid(self.lib, out) if want_grid and out.value else None
         return rgb, grid
 
+    def reproject(self, prev: ReservoirGrid, cam_prev, cam_cur, want_map: bool = False):
+        """restir_frame_reproject: a new predecessor grid for a camera that moved from cam_prev to cam_cur -- at each
+        pixel the reservoirs of `prev` at the pixel where the current surface point was seen from cam_prev, or empty
+        ones.  Pass it to render_restir as `prev`.  want_map: returns (grid, map [h][w] uint32, rows y = 0 bottom) with
+        the source pixel's flat index or 0xFFFFFFFF - reason (0 miss, 1 behind, 2 off-screen, 3 predecessor miss,
+        4 depth, 5 normal), and synchronises."""
+        out = C.c_void_p()
+        smap = None
+        if want_map:
+            i = prev.info()
+            smap = np.zeros((i["H"], i["W"]), np.uint32)
+        check(self.lib, self.lib.restir_frame_reproject(self.ctx, prev.handle, C.byref(cam_prev), C.byref(cam_cur), C.byref(out),
+                                                        smap.ctypes.data_as(C.POINTER(C.c_uint32)) if want_map else None),
+              "restir_frame_reproject")
+        grid = ReservoirGrid(self.lib, out)
+        return (grid, smap) if want_map else grid
+
     def synchronize(self) -> None:
         check(self.lib, self.lib.restir_synchronize(self.ctx), "restir_synchronize")
 
@@ -407,6 +424,18 @@ class Renderer:
 
 def rng_key(seed: int, frame: int, stage: int, pass_: int = 0) -> int:
     return _abi.load_library().restir_rng_key(seed, frame, stage, pass_)
+
+
+def reproject_pixel(prev_cam: _abi.CameraFrame, width: int, height: int, point):
+    """restir_reproject_pixel (pure host): (x, y, depth) -- the pixel of the width x height image where the camera
+    prev_cam (a derived CameraFrame) saw world point `point`, x = y = 0xFFFFFFFF - reason when behind (1) or off-screen
+    (2), and the point's distance from the camera."""
+    lib = _abi.load_library()
+    P = (C.c_float * 3)(*[float(v) for v in point])
+    x, y, d = C.c_uint32(), C.c_uint32(), C.c_float()
+    check(lib, lib.restir_reproject_pixel(C.byref(prev_cam), width, height, P, C.byref(x), C.byref(y), C.byref(d)),
+          "restir_reproject_pixel")
+    return x.value, y.value, d.value
 
 
 def rccl_unique_id() -> bytes:
