@@ -618,6 +618,19 @@ restir_status restir_background_pixels(restir_ctx* ctx, uint64_t* background, ui
  * their primary rays; restir_timings counts both kinds under RESTIR_K_PRIMARY_RIS. */
 restir_status restir_gbuf_reuses(restir_ctx* ctx, uint64_t* out_frames);
 
+/* restir_render frames of this context so far whose fused last pass traced its shadow rays over the view's candidate
+ * triangle lists (tuning "final.lists") instead of the BVH: from the second consecutive frame that reuses the kept
+ * G-buffer with the light list unchanged. */
+restir_status restir_shadow_list_frames(restir_ctx* ctx, uint64_t* out_frames);
+
+/* Test hook for those lists, as the last frame left them (RESTIR_ERR_STATE when there are none for the kept G-buffer):
+ * for every pixel of that frame's owned rectangle, width x height (RESTIR_ERR_INVALID when the frame's was another
+ * size; row-major from its first row, one byte each), the shadow ray from the
+ * pixel's hit point to point light `light` (num_lights: the zero sample at the origin) traced by the BVH walk (out_bvh)
+ * and over the pixel's tile's list (out_list), 1 visible / 0 occluded; 0xFF in both for a pixel of a background tile. */
+restir_status restir_debug_shadow_lists(restir_ctx* ctx, uint32_t light, uint32_t width, uint32_t height, uint8_t* out_bvh,
+                                        uint8_t* out_list);
+
 /* What restir_set_scene derived from the scene it uploaded -- the facts the route functions choose kernels by -- so that a
  * test can tell which form a scene took (a light grid the regular form, a BVH past the LDS budget).  Read-only: runs no
  * kernel, changes nothing.  RESTIR_ERR_STATE before the first scene.  (In C++ the function hides the struct's name:

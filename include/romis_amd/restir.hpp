@@ -234,6 +234,20 @@ public:
         check(restir_render_mis_tile(ctx_, &camera, &features, width, height, &tile, rgb.data()), "restir_render_mis_tile");
         return rgb;
     }
+    // Frames so far whose fused last pass traced its shadow rays over the view's triangle lists (restir_shadow_list_frames)
+    uint64_t shadowListFrames() const {
+        uint64_t n = 0;
+        check(restir_shadow_list_frames(ctx_, &n), "restir_shadow_list_frames");
+        return n;
+    }
+    // Test hook (restir_debug_shadow_lists): width x height bytes each, the last frame's owned rectangle (another size
+    // is refused)
+    void debugShadowLists(uint32_t light, std::vector<uint8_t>& byBvh, std::vector<uint8_t>& byList, uint32_t width,
+                          uint32_t height) const {
+        byBvh.assign(size_t(width) * height, 0);
+        byList.assign(size_t(width) * height, 0);
+        check(restir_debug_shadow_lists(ctx_, light, width, height, byBvh.data(), byList.data()), "restir_debug_shadow_lists");
+    }
     restir_ctx* handle() const { return ctx_; }
 
 private:

@@ -38,11 +38,12 @@ SOURCES = [
     ("mis.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("refit.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("reproject.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
+    ("shadow_lists.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("bvh.cpp", ["-x", "c++"]),
     ("screen.cpp", ["-x", "c++"]),
 ]
 HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
-           "route.h", "ris_members.h", "refit.h", "reproject.h"]
+           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h"]
 
 
 def source_hash() -> str:
@@ -95,6 +96,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_route_check(force)
     build_bvh_check(force)
     build_refit_check(force)
+    build_shadow_lists_check(force)
     if verbose:
         print(LIB)
     return LIB
@@ -139,6 +141,18 @@ def build_refit_check(force: bool = False) -> str:
         os.makedirs(os.path.dirname(tool), exist_ok=True)
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off", "-pthread", f"-I{CSRC}",
                                src, os.path.join(CSRC, "bvh.cpp"), "-o", tool])
+    return tool
+
+
+def build_shadow_lists_check(force: bool = False) -> str:
+    """tools/shadow_lists_check: tests/cpp/shadow_lists_check.cpp over csrc/shadow_lists.h with the host compiler -- no
+    record leaves out a triangle a ray of its family hits (tests/test_shadow_lists_host.py); no device code."""
+    tool = os.path.join(OUT, "tools", "shadow_lists_check")
+    src = os.path.join(ROOT, "tests", "cpp", "shadow_lists_check.cpp")
+    deps = [src, os.path.join(CSRC, "shadow_lists.h"), __file__]
+    if os.path.exists(src) and (force or _stale(tool, deps)):
+        os.makedirs(os.path.dirname(tool), exist_ok=True)
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off", f"-I{CSRC}", src, "-o", tool])
     return tool
 
 

@@ -1497,6 +1497,10 @@ __device__ __forceinline__ void fin_store_background(const Region& rg, const Fea
 __device__ __forceinline__ void fin_shade_block(const SceneDev& s, const Region& rg, const FeaturesDev& f, const FinalOut& fin,
                                                 const GlTabs& tb, bool live, bool own_bg, int tx0, int ty0, uint32_t wave, const Px& px,
                                                 bool pm_miss, v3 pos, v3 col, float W);
+__device__ __forceinline__ void fin_shade_block_lists(const SceneDev& s, const Region& rg, const FeaturesDev& f, const FinalOut& fin,
+                                                      const GlTabs& tb, bool live, bool own_bg, int tx0, int ty0, uint32_t wave,
+                                                      const Px& px, bool pm_miss, v3 pos, v3 col, float W, uint32_t li,
+                                                      const uint4* __restrict__ sl);
 
 // HG (the default 32 x 16 form since round 6): the handles are gathered from global memory (the own pixel's coalesced,
 // an accepted neighbour's one 4 + 4 B gather) instead of staged in LDS: the block's LDS is the n_t window and the light
@@ -1507,15 +1511,18 @@ __device__ __forceinline__ void fin_shade_block(const SceneDev& s, const Region&
 // block reaches the ray phase's barriers: a lane that would have left early (outside the rect, the miss material)
 // carries the reservoir it would have written instead.  After the combine the window and the light table are dead;
 // their bytes hold the BVH, the binned rays and the histogram (one barrier between the two uses).
-template <bool DBG, uint32_t TH = 1, bool HG = false, bool FIN = false>
+// LISTS (k_spatial1hg_t2_final_lists): FIN with the ray phase of fin_shade_block_lists -- each lane's ray over the
+// shadow list of (its tile, its light), sl -- which has no barrier, no histogram and no staged BVH.
+template <bool DBG, uint32_t TH = 1, bool HG = false, bool FIN = false, bool LISTS = false>
 __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key,
                                                v3 origin, const float4* __restrict__ n_t, const float4* __restrict__ p_mat,
                                                HandlesIn hi, float4* __restrict__ oa, float4* __restrict__ ob,
                                                float2* __restrict__ odbg, const float* __restrict__ rp_in,
                                                float* __restrict__ rp_out, float* __restrict__ how,
                                                uint32_t* __restrict__ hom, MissTiles mt, uint32_t odead,
-                                               FinalOut fin = FinalOut{nullptr, 0u}) {
+                                               FinalOut fin = FinalOut{nullptr, 0u}, const uint4* __restrict__ sl = nullptr) {
     static_assert(!FIN || (!DBG && TH == 2u && HG), "the fused form is the 32 x 16 gather pass without a debug plane");
+    static_assert(!LISTS || FIN, "the shadow lists serve the fused form's rays");
     float4* const l_nt = g_lds;
     float* const l_w = reinterpret_cast<float*>(g_lds + apron_max(TH));
     uint32_t* const l_m = reinterpret_cast<uint32_t*>(l_w + apron_max(TH));
@@ -1565,6 +1572,7 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
     Px rpx;
     v3 rpos = mk(0.0f, 0.0f, 0.0f), rcol = mk(0.0f, 0.0f, 0.0f);
     float rW = 0.0f;
+    uint32_t rli = L;   // LISTS: the held sample's light (L: the zero sample)
     uint32_t wave = 0u;
     if constexpr (FIN) wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     bool pm_miss = false;   // final_sorted_body's miss test, the part on p_mat (decided here: a flag, not pm.w, stays live)
@@ -1642,9 +1650,11 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
         if (rp_out) rp_out[pix] = p;
         if (how) { how[pix] = W; hom[pix] = cmb.macc | (cmb.li << 24); }
         if constexpr (FIN) { rpos = pos; rcol = col; rW = W; }
+        if constexpr (LISTS) rli = cmb.li;
     }
 shade:
-    if constexpr (FIN) fin_shade_block(s, rg, f, fin, tb, live, own_bg, tx0, ty0, wave, rpx, pm_miss, rpos, rcol, rW);
+    if constexpr (LISTS) fin_shade_block_lists(s, rg, f, fin, tb, live, own_bg, tx0, ty0, wave, rpx, pm_miss, rpos, rcol, rW, rli, sl);
+    else if constexpr (FIN) fin_shade_block(s, rg, f, fin, tb, live, own_bg, tx0, ty0, wave, rpx, pm_miss, rpos, rcol, rW);
 }
 
 #ifndef ROMIS_SPATIAL1H_WPE
@@ -2481,6 +2491,12 @@ __device__ __forceinline__ void fin_shade_block(const SceneDev& s, const Region&
     } else {
         W = 0.0f;
     }
+#ifdef ROMIS_FIN_CEILING
+    // measurement stand-in (never a default; wrong images): no ray phase at all, every needed ray counts as visible --
+    // the bound on what any cheaper ray phase can return (profiles/shadow_lists/ceiling.json)
+    if (!live) return;
+    v3 c = sc;
+#else
     __syncthreads();   // every lane is done with the window and the light table
     const uint32_t nb = 2u * s.num_nodes + 3u * s.num_tris;
     float4* const s_from = g_lds + nb;
@@ -2527,6 +2543,7 @@ __device__ __forceinline__ void fin_shade_block(const SceneDev& s, const Region&
     // finalShading's sum from 0 (final_body: -0 -> +0), then / N
     v3 c = sc;
     if (need && !s_vis[t]) c = mk(0.0f, 0.0f, 0.0f);
+#endif
     v3 color = vadd(mk(0.0f, 0.0f, 0.0f), vscale(c, W));
     color = tone_map_rgb(f, vdivs(color, 1.0f), tb);
     const uint32_t w = t >> 6, l = t & 63u;   // spatial1h_body's pixel of the 32 x 16 tile
@@ -2546,6 +2563,61 @@ k_spatial1hg_t2_final(SceneDev s, Region rg, FeaturesDev f, uint32_t key, float 
     spatial1h_body<false, 2, true, true>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, hi, oa, ob, nullptr, rp_in, nullptr, how,
                                          hom, mt, odead, fin);
 }
+
+// fin_shade_block with the rays over the view's shadow lists (shadow_lists.h; restir_render builds them once a view and
+// its lights stand still): the same shade, need test, miss path, x W, / 1, tone map and store, and between them each
+// needing lane traces visible()'s own ray over the record of (the block's tile, the lane's light li) -- no barrier, no
+// staged BVH, no binning.  A record that says "walk the BVH" sends that lane alone over the global BVH; a lane whose
+// start point the tile's box does not cover (a miss-material pixel that shades all the same) tests every triangle.
+// (Sending the whole block of a tile that holds such a record through fin_shade_block instead -- block-uniform by a
+// per-tile header -- measured slower than the parent at C2: 27 % of the tiles hold one, and the kernel with both ray
+// phases needs 36 B of scratch instead of 20)
+__device__ __forceinline__ void fin_shade_block_lists(const SceneDev& s, const Region& rg, const FeaturesDev& f, const FinalOut& fin,
+                                                      const GlTabs& tb, bool live, bool own_bg, int tx0, int ty0, uint32_t wave,
+                                                      const Px& px, bool pm_miss, v3 pos, v3 col, float W, uint32_t li,
+                                                      const uint4* __restrict__ sl) {
+    // the records of the block's tile in the pass's rect, row-major (lean_tile<2>'s numbering; block-uniform)
+    const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW;
+    const uint32_t tile = (((uint32_t)ty0 - rg.ry0) / (2u * kTileH)) * ntx + ((uint32_t)tx0 - rg.rx0) / kTileW;
+    const uint4* const rec = sl + (size_t)tile * sl_stride(s.num_lights);
+    const uint32_t t = (wave << 6) | __lane_id();
+    v3 sc = mk(0.0f, 0.0f, 0.0f);
+    bool need = false;
+    if (live && !own_bg) {
+        const bool miss = pm_miss && __builtin_isfinite(W) &&
+                          !__builtin_isnan((pos.x - px.P.x) + (pos.y - px.P.y) + (pos.z - px.P.z));
+        if (!miss) {
+            sc = shade(s, f, px, pos, col, tb);
+            need = sc.x != 0.0f || sc.y != 0.0f || sc.z != 0.0f;
+        } else {
+            W = 0.0f;
+        }
+    } else {
+        W = 0.0f;
+    }
+    Bvh bvh = global_bvh(s);
+#ifdef ROMIS_LISTS_LDS
+    // measurement variant (profiles/shadow_lists/ab.json "triangles_in_lds"): the triangles staged in the bytes the
+    // window and the light table held, at the cost of two barriers (the window's last reader, the copy); the nodes a
+    // walking lane reads stay in global memory
+    __syncthreads();
+    const Bvh staged = stage_bvh(s, g_lds, false);
+    bvh.v0 = staged.v0; bvh.e1 = staged.e1; bvh.e2 = staged.e2;
+#endif
+    if (!live) return;
+    v3 c = sc;
+    if (need && !visible_listed(bvh, s.num_tris, rec[li], px.mat == s.num_materials - 1u, px.P, pos))
+        c = mk(0.0f, 0.0f, 0.0f);
+    v3 color = vadd(mk(0.0f, 0.0f, 0.0f), vscale(c, W));
+    color = tone_map_rgb(f, vdivs(color, 1.0f), tb);
+    const uint32_t w = t >> 6, l = t & 63u;   // spatial1h_body's pixel of the 32 x 16 tile
+    const uint32_t x = (uint32_t)tx0 + (w & 3u) * 8u + (l & 7u), y = (uint32_t)ty0 + (w >> 2) * 8u + (l >> 3);
+    const uint32_t row = rg.rh - 1u - (y - rg.ry0);
+    float* o = fin.rgb + 3 * ((size_t)row * rg.rw + (x - rg.rx0));
+    o[0] = color.x; o[1] = color.y; o[2] = color.z;
+}
+
+// (k_spatial1hg_t2_final_lists itself is the last kernel of this file: the code of the kernels above stays where it was)
 
 #define ROMIS_FINAL_KERNEL(NT, LDS, NAME)                                                                            \
     extern "C" __global__ __launch_bounds__(256) void NAME(SceneDev s, Region rg, FeaturesDev f, float ox, float oy,     \
@@ -2631,6 +2703,15 @@ extern "C" __global__ __launch_bounds__(256) void k_read_stream(const float4* __
     }
     for (size_t i = waves * per + wave * 64 + lane; i < n4; i += waves * 64) acc += buf[i].x;   // the remainder
     if (acc == 12345.0f) sink[blockIdx.x % 256u] = acc;   // buffers are zero: never taken, but not provably so
+}
+
+// k_spatial1hg_t2_final with its rays over the shadow lists (fin_shade_block_lists)
+extern "C" __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(ROMIS_SPATIAL1HG_FINAL_WPE))) void
+k_spatial1hg_t2_final_lists(SceneDev s, Region rg, FeaturesDev f, uint32_t key, float ox, float oy, float oz, const float4* n_t,
+                            const float4* p_mat, HandlesIn hi, float4* oa, float4* ob, const float* rp_in, float* how,
+                            uint32_t* hom, MissTiles mt, uint32_t odead, FinalOut fin, const uint4* sl) {
+    spatial1h_body<false, 2, true, true, true>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, hi, oa, ob, nullptr, rp_in, nullptr, how,
+                                               hom, mt, odead, fin, sl);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2791,6 +2872,12 @@ hipError_t launch_spatial(const Route& r, const SceneDev& s, const Region& rg0, 
         break;
     case Kernel::kSpatial1hgFinal:
         assert(b.rgb);
+        if (r.lists) {
+            assert(b.shadow_lists);
+            ROMIS_LAUNCH(k_spatial1hg_t2_final_lists, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], b.n_t,
+                         b.p_mat, hi, b.oa, b.ob, rp_in, how, hom, mt, r.res_dead, FinalOut{b.rgb, r.miss}, b.shadow_lists);
+            break;
+        }
         ROMIS_LAUNCH(k_spatial1hg_t2_final, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], b.n_t, b.p_mat, hi,
                      b.oa, b.ob, rp_in, how, hom, mt, r.res_dead, FinalOut{b.rgb, r.miss});
         break;

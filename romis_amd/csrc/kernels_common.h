@@ -6,6 +6,7 @@
 #include "launch_shape.h"
 #include "restir_c.h"
 #include "restir_types.h"
+#include "shadow_lists.h"
 
 #include <float.h>
 
@@ -281,6 +282,28 @@ __device__ __forceinline__ bool visible(const Bvh& b, v3 P, v3 y) {
     v3 P2 = vadd(P, vscale(dir, 1e-3f));
     float tfar = vdistance(P2, y);
     return !occluded(b, P2, dir, tfar);
+}
+
+// visible() over a shadow-list record (shadow_lists.h): rec = the 16 bytes of (the start point's tile, the light at y),
+// b the global traversal arrays.  A count of 0 is visible; kSlWalk walks the BVH; else the same ray -- visible()'s P2,
+// dir and tfar -- against the listed triangles with occluded()'s tri_any, stopping at the first hit.  Any-hit over any
+// set that holds every triangle the ray hits is occluded()'s answer.  outside: the start point is not one the tile's
+// box was built over (a miss-material pixel), so every triangle is tested.  No LDS, no barrier.
+__device__ __forceinline__ bool visible_listed(const Bvh& b, uint32_t num_tris, uint4 rec, bool outside, v3 P, v3 y) {
+    const uint32_t cnt = rec.x & 0xFFu;
+    if (!outside && cnt == kSlWalk) return visible(b, P, y);
+    const v3 dir = vnormalize(vsub(y, P));
+    const v3 P2 = vadd(P, vscale(dir, 1e-3f));
+    const float tfar = vdistance(P2, y);
+    // the index bytes, shifted down one per step
+    uint32_t w0 = (rec.x >> 8) | (rec.y << 24), w1 = (rec.y >> 8) | (rec.z << 24), w2 = (rec.z >> 8) | (rec.w << 24), w3 = rec.w >> 8;
+    const uint32_t n = outside ? num_tris : cnt;
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t i = outside ? k : (w0 & 0xFFu);
+        if (tri_any(b.v0[i], b.e1[i], b.e2[i], P2, dir, tfar)) return false;
+        w0 = (w0 >> 8) | (w1 << 24); w1 = (w1 >> 8) | (w2 << 24); w2 = (w2 >> 8) | (w3 << 24); w3 >>= 8;
+    }
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------

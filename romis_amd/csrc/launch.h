@@ -30,6 +30,7 @@ struct LaunchBufs {
     Handles hin{nullptr, nullptr};     // the input's sample handles
     Handles hout{nullptr, nullptr};    // the output's
     float* rgb = nullptr;              // final shading's image (the owned rect)
+    const uint4* shadow_lists = nullptr;   // the view's shadow-list records (shadow_lists.h), for a route with `lists`
     TemporalIn tin{};                  // primary + RIS + temporal: the predecessor grid
 };
 

@@ -31,6 +31,7 @@
 #include "refit.h"
 #include "reproject.h"
 #include "restir_types.h"
+#include "shadow_lists.h"
 
 namespace romis {
 bool write_bmp_words(const char* path, uint32_t width, uint32_t height, const uint32_t* words);   // screen.cpp
@@ -286,6 +287,21 @@ struct restir_ctx {
         const void *n_t = nullptr, *p_mat = nullptr, *uv = nullptr, *tmiss = nullptr;   // the buffers themselves
     } gbuf;
     uint64_t gbuf_reuses = 0;                       // frames that took the k_gbuf_ris family (restir_gbuf_reuses)
+    uint64_t gbuf_epoch = 0;                        // counts the tracing frames that wrote `gbuf`: names one kept G-buffer
+    // The shadow lists of the kept G-buffer (shadow_lists.h, tuning "final.lists"): the records in `slists`, valid for
+    // what `key` names -- that G-buffer, the light table (scene_gen) and the geometry (geom_gen) -- and for the launch
+    // `dev` describes (the last pass's rect, the tile flags, the cap).  Built by the second consecutive frame that
+    // reuses the G-buffer with the lights unchanged (gbuf_streak counts them), so a client that moves its lights every
+    // frame never pays for them; whatever drops the G-buffer, the lights or the geometry leaves the key stale.
+    DevBuf slists;
+    struct ShadowListsKey {
+        bool valid = false;
+        uint64_t gbuf_epoch = 0, scene_gen = 0, geom_gen = 0;
+    } slists_key;
+    ShadowListsDev slists_dev{};
+    uint32_t gbuf_streak = 0;
+    uint64_t gbuf_streak_lights = 0;                // scene_gen of the frames the streak counts
+    uint64_t shadow_list_frames = 0;                // frames whose last pass traced over the lists (restir_shadow_list_frames)
     int cur = 0;
     uint32_t rgb_w = 0, rgb_h = 0;
 
@@ -1052,6 +1068,13 @@ restir_status restir_create(int device, restir_ctx** out) {
 
 static void release_rccl(restir_ctx* c);   // (halo section)
 
+// Free the shadow-list records (restir_ctx::slists): where nothing can read them again -- another scene, final.lists
+// off, the context's end.  (hipFree waits for the kernels that read them.)
+static void drop_shadow_lists(restir_ctx* c) {
+    c->slists_key.valid = false;
+    c->slists.release();
+}
+
 void restir_destroy(restir_ctx* c) {
     if (!c) return;
     {
@@ -1061,6 +1084,7 @@ void restir_destroy(restir_ctx* c) {
         for (DevBuf* b : {&c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
                           &c->rpj_map})
             b->release();
+        drop_shadow_lists(c);
         for (DevBuf* b : {&c->nodes, &c->nodes_q, &c->tri_v0, &c->tri_e1, &c->tri_e2, &c->tri_n0, &c->tri_n1, &c->tri_n2,
                           &c->materials, &c->lights, &c->light_c2, &c->light_c4, &c->light_col, &c->tex_texels, &c->tex_dims, &c->tri_uv, &c->uv, &c->n_t, &c->p_mat, &c->ra[0], &c->ra[1], &c->rb[0], &c->rb[1],
                           &c->dbg[0], &c->dbg[1], &c->rgb, &c->halo_scratch, &c->rec[0], &c->rec[1], &c->rp[0], &c->rp[1]})
@@ -1280,6 +1304,7 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
     std::lock_guard<std::mutex> lk(c->mu);
     c->gbuf.valid = false;   // another scene: the kept G-buffer is not its view
     HIP_TRY(hipSetDevice(c->device));
+    drop_shadow_lists(c);    // ... nor are the lists its triangles' (a scene they serve builds its own)
 
     // flatten triangles (mesh order = original index order, like the oracle)
     std::vector<BvhTriangle> tris;
@@ -1859,6 +1884,40 @@ static bool gbuf_reusable(const restir_ctx::GbufView& have, const restir_ctx::Gb
            (!(have.skip & 2u) || (want.skip & 2u));
 }
 
+// The shadow lists route `r` (the fused last pass over rect pr, Route::lists) reads: kept when they were built for this
+// G-buffer, light table, geometry and launch, else built now, on the frame's stream ahead of the pass.
+static restir_status ensure_shadow_lists(restir_ctx* c, const Route& r, const SceneDev& s, const Region& pr, const float4* p_mat,
+                                         const uint8_t* tmiss, hipStream_t st) {
+    ShadowListsDev d{};
+    d.s = s;
+    d.s.gbuf_uv = nullptr;   // (per launch, unread here: keeps the comparison below to what the lists depend on)
+    d.rg = r.region(pr);
+    d.p_mat = p_mat;
+    d.mt = MissTiles{r.flags ? tmiss : nullptr, r.flags_m, r.gbuf};
+    d.cap = std::min(std::max(c->tuning.final_lists_cap, 1u), kSlCap);
+    const size_t bytes = (size_t)shadow_list_tiles(d.rg) * sl_stride(s.num_lights) * 16u;
+    const restir_ctx::ShadowListsKey& k = c->slists_key;
+    const ShadowListsDev& h = c->slists_dev;
+    const bool same_launch = h.rg.vx0 == d.rg.vx0 && h.rg.vy0 == d.rg.vy0 && h.rg.vw == d.rg.vw && h.rg.vh == d.rg.vh &&
+                             h.rg.rx0 == d.rg.rx0 && h.rg.ry0 == d.rg.ry0 && h.rg.rw == d.rg.rw && h.rg.rh == d.rg.rh &&
+                             h.p_mat == d.p_mat && h.mt.flags == d.mt.flags && h.mt.m == d.mt.m && h.cap == d.cap &&
+                             h.s.num_lights == s.num_lights && h.s.num_tris == s.num_tris && h.s.light_c2 == s.light_c2 &&
+                             h.s.tri_v0 == s.tri_v0 && h.s.num_materials == s.num_materials;
+    if (k.valid && c->slists.p && k.gbuf_epoch == c->gbuf_epoch && k.scene_gen == c->scene_gen && k.geom_gen == c->geom_gen &&
+        same_launch)
+        return RESTIR_OK;
+    c->slists_key.valid = false;
+    ST_TRY(c->slists.ensure(bytes));
+    d.rec = c->slists.as<uint4>();
+    HIP_TRY(launch_shadow_lists(d, st));
+    c->slists_dev = d;
+    c->slists_key.valid = true;
+    c->slists_key.gbuf_epoch = c->gbuf_epoch;
+    c->slists_key.scene_gen = c->scene_gen;
+    c->slists_key.geom_gen = c->geom_gen;
+    return RESTIR_OK;
+}
+
 // renderReSTIR (render.cpp:28-62)
 restir_status restir_render(restir_ctx* c, const restir_camera* cam, const restir_features* features, uint32_t width,
                             uint32_t height, const restir_tile* tile, const restir_frame* prev, restir_frame** out_next,
@@ -2049,10 +2108,16 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
     }
     if (ris_ask.gbuf_cached) {
         c->gbuf_reuses++;
-    } else if (fused && !fb.records) {
-        c->gbuf = gv;
-        c->gbuf.valid = true;
+        c->gbuf_streak = c->gbuf_streak_lights == c->scene_gen ? c->gbuf_streak + 1u : 1u;
+    } else {
+        c->gbuf_streak = 0u;
+        if (fused && !fb.records) {
+            c->gbuf = gv;
+            c->gbuf.valid = true;
+            c->gbuf_epoch++;
+        }
     }
+    c->gbuf_streak_lights = c->scene_gen;
     c->last_px = (uint64_t)t.gwidth * t.gheight;   // restir_background_pixels
     c->tmiss_w = tmiss ? t.gwidth : 0u;
     c->tmiss_h = tmiss ? t.gheight : 0u;
@@ -2069,10 +2134,18 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
     for (uint32_t pass = 0; pass < passes; pass++) {
         const Region pr = pass_rect(pass);
         const int nxt = cur ^ 1;
-        last = route_spatial(s, pr, f, c->tuning, pass_ask(pass, last.rp_out));
+        Ask ask = pass_ask(pass, last.rp_out);
+        // the fused last pass's rays over the view's shadow lists, from the second still frame on (final.lists)
+        ask.shadow_lists = ask.fin && c->gbuf_streak >= c->tuning.final_lists_after;
+        last = route_spatial(s, pr, f, c->tuning, ask);
         b = fb.bufs(camd, restir_rng_key(c->seed, frame, RESTIR_STAGE_SPATIAL, pass), cur, nxt);
         b.vis = vis;
         b.flags = tmiss;
+        if (last.lists) {
+            ST_TRY(ensure_shadow_lists(c, last, s, pr, pm, tmiss, st));
+            b.shadow_lists = c->slists.as<uint4>();
+            c->shadow_list_frames++;
+        }
         if (pass + 1 == passes) b.hout = fb.fh(nxt);   // (frame_handles; the route names them)
         TIMED(c, RESTIR_K_SPATIAL, launch_spatial(last, s, pr, f, b, st));
         cur = nxt;
@@ -2653,6 +2726,45 @@ restir_status restir_gbuf_reuses(restir_ctx* c, uint64_t* out_frames) {
     std::lock_guard<std::mutex> lk(c->mu);
     *out_frames = c->gbuf_reuses;
     return RESTIR_OK;
+}
+
+restir_status restir_shadow_list_frames(restir_ctx* c, uint64_t* out_frames) {
+    if (!c || !out_frames) return fail(RESTIR_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out_frames = c->shadow_list_frames;
+    return RESTIR_OK;
+}
+
+// restir_debug_shadow_lists between its buffers' allocation and their release
+static restir_status debug_shadow_lists_run(restir_ctx* c, const ShadowListsDev& d, uint32_t light, size_t n, DevBuf& bb, DevBuf& bl,
+                                            uint8_t* out_bvh, uint8_t* out_list) {
+    ST_TRY(bb.ensure(n));
+    ST_TRY(bl.ensure(n));
+    hipError_t e = launch_debug_shadow_lists(d, light, bb.as<uint8_t>(), bl.as<uint8_t>(), c->stream);
+    if (e != hipSuccess) return fail(RESTIR_ERR_HIP, "debug shadow lists launch: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(out_bvh, bb.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_list, bl.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RESTIR_OK;
+}
+
+restir_status restir_debug_shadow_lists(restir_ctx* c, uint32_t light, uint32_t width, uint32_t height, uint8_t* out_bvh,
+                                        uint8_t* out_list) {
+    if (!c || !out_bvh || !out_list) return fail(RESTIR_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    const restir_ctx::ShadowListsKey& k = c->slists_key;
+    if (!c->has_scene || !c->gbuf.valid || !k.valid || k.gbuf_epoch != c->gbuf_epoch || k.scene_gen != c->scene_gen ||
+        k.geom_gen != c->geom_gen)
+        return fail(RESTIR_ERR_STATE, "restir_debug_shadow_lists: no shadow lists of the kept G-buffer (a frame builds them)");
+    const ShadowListsDev& d = c->slists_dev;
+    if (light > d.s.num_lights) return fail(RESTIR_ERR_INVALID, "light %u of %u (+ the zero sample)", light, d.s.num_lights);
+    if (width != d.rg.rw || height != d.rg.rh)
+        return fail(RESTIR_ERR_INVALID, "the planes are %u x %u, the lists' rectangle %u x %u", width, height, d.rg.rw, d.rg.rh);
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf bb, bl;
+    const restir_status st = debug_shadow_lists_run(c, d, light, (size_t)width * height, bb, bl, out_bvh, out_list);
+    bb.release(); bl.release();   // on every path
+    return st;
 }
 
 restir_status restir_scene_info(restir_ctx* c, struct restir_scene_info* out) {
@@ -3305,6 +3417,12 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     else if (!std::strcmp(key, "final.sort")) t.final_sort = v;
     else if (!std::strcmp(key, "final.qbvh")) t.final_qbvh = v;
     else if (!std::strcmp(key, "final.fuse")) t.final_fuse = v;
+    else if (!std::strcmp(key, "final.lists")) {
+        t.final_lists = v;
+        if (!v) { HIP_TRY(hipSetDevice(c->device)); drop_shadow_lists(c); }
+    }
+    else if (!std::strcmp(key, "final.lists_after")) { if (v < 1) return fail(RESTIR_ERR_INVALID, "final.lists_after: >= 1"); t.final_lists_after = v; }
+    else if (!std::strcmp(key, "final.lists_cap")) { if (v < 1 || v > kSlCap) return fail(RESTIR_ERR_INVALID, "final.lists_cap: 1 .. 15"); t.final_lists_cap = v; }
     else if (!std::strcmp(key, "primary.tl")) t.primary_tl = v;
     else if (!std::strcmp(key, "gbuf.reuse")) t.gbuf_reuse = v;
     else if (!std::strcmp(key, "mis.chunk")) t.mis_chunk = v;   // applies from the next ensure_mis

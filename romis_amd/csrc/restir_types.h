@@ -193,6 +193,13 @@ struct Tuning {
     uint32_t final_sort = 1;       // N = 1: bin each tile's shadow rays by target before tracing (-2.4 %, r2ah)
     uint32_t final_fuse = 1;       // restir_render: final shading inside the last N = 1 point-light handle pass
                                    // (k_spatial1hg_t2_final) where both kernels' conditions hold; 0: always two kernels
+    uint32_t final_lists = 1;      // restir_render: from the second frame that reuses the G-buffer with the lights unchanged, the
+                                   // fused last pass traces its shadow rays over per-tile, per-light candidate triangle
+                                   // lists (shadow_lists.h, k_spatial1hg_t2_final_lists); 0: always the BVH in LDS
+    uint32_t final_lists_after = 2; // ... from this many consecutive frames that reuse the G-buffer with the lights unchanged: a
+                                   // build costs about three C2 frames, so a view that moves sooner than some sixty frames
+                                   // after it stopped loses by it; raise this where views pause briefly
+    uint32_t final_lists_cap = 15; // indices a list record holds, 1 .. 15 (a longer list walks the BVH; tests lower it)
     uint32_t primary_tl = 1;       // fused primary + RIS, one tile per block: the primary rays test the tile's candidate
                                    // triangles (tile_triangles) instead of walking the BVH
     uint32_t gbuf_reuse = 1;       // restir_render: a frame whose view (scene upload, camera, image size, region) is the one

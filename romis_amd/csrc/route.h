@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "launch_shape.h"
+#include "shadow_lists.h"
 
 namespace romis {
 
@@ -61,6 +62,8 @@ struct Ask {
     // primary + RIS: the view's G-buffer and tile flags are in memory from an earlier frame (restir_render's GbufView):
     // the k_gbuf_ris family reads them and traces nothing
     bool gbuf_cached = false;
+    // spatial: the view's shadow lists (shadow_lists.h) are built: a fused last pass may trace its rays over them
+    bool shadow_lists = false;
 };
 
 struct Route {
@@ -93,6 +96,7 @@ struct Route {
     uint32_t mode = 0;         // primary + RIS: ris.late | primary.tl << 1
     uint32_t bvh_lds = 0;      // kSpatial: shadow rays over the BVH staged in LDS
     bool final_done = false;   // spatial: final shading ran in this kernel
+    bool lists = false;        // ... its rays over the shadow lists (k_spatial1hg_t2_final_lists)
     uint32_t miss = 1;         // final: the miss shortcut is allowed (final.miss)
 
     Region region(Region rg) const {
@@ -352,6 +356,8 @@ inline Route route_spatial(const SceneDev& s, const Region& rg, const FeaturesDe
             lean_shape(r, rg, tu, Kernel::kSpatial1hgFinal, 2u, XcdChunks::kOneRow, std::max(lds, lds_fin));
             r.final_done = true;
             r.miss = fin.miss;
+            // the rays over the view's shadow lists (final.lists) where the caller holds them: one-byte triangle indices
+            r.lists = ask.shadow_lists && tu.final_lists && s.num_tris <= kSlMaxTris;
             // nothing else reads the pass's reservoir planes (no returned grid): the fused kernel does not store them
             if (ask.fin_dead) r.res_dead = 1u;
         } else {

@@ -268,6 +268,24 @@ class Renderer:
         check(self.lib, self.lib.restir_gbuf_reuses(self.ctx, C.byref(n)), "restir_gbuf_reuses")
         return int(n.value)
 
+    def shadow_list_frames(self) -> int:
+        """render_restir frames so far whose fused last pass traced its shadow rays over the view's candidate triangle
+        lists (restir_shadow_list_frames; tuning "final.lists")."""
+        n = C.c_uint64()
+        check(self.lib, self.lib.restir_shadow_list_frames(self.ctx, C.byref(n)), "restir_shadow_list_frames")
+        return int(n.value)
+
+    def debug_shadow_lists(self, light: int, width: int, height: int):
+        """(by the BVH walk, over the list): [height][width] uint8 planes of the last frame's owned rectangle, the shadow
+        ray of every pixel to point light `light` (restir_debug_shadow_lists)."""
+        a = np.zeros((height, width), np.uint8)
+        b = np.zeros((height, width), np.uint8)
+        U8 = C.POINTER(C.c_uint8)
+        check(self.lib, self.lib.restir_debug_shadow_lists(self.ctx, light, width, height, a.ctypes.data_as(U8),
+                                                           b.ctypes.data_as(U8)),
+              "restir_debug_shadow_lists")
+        return a, b
+
     # ---- timing ---------------------------------------------------------------------------------------
     def enable_timing(self, on: bool = True) -> None:
         check(self.lib, self.lib.restir_enable_timing(self.ctx, 1 if on else 0), "restir_enable_timing")
