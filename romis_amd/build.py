@@ -32,9 +32,15 @@ DEVICE = [f"--offload-arch={ARCH}", "-fhip-fp32-correctly-rounded-divide-sqrt", 
 # (kbench, profiles/r2/noslp), fewer VGPRs and no RIS scratch spill.  Results are identical (no contraction).
 KERNEL_FLAGS = ["-fno-slp-vectorize"]
 
-SOURCES = [
-    ("kernels.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
-    ("restir.cpp", ["-x", "hip"] + DEVICE),
+# The units behind include/restir_c.h, with their flags.  source_hash() hashes them as the launcher: together with
+# route.h they decide which buffers a pass reads and writes.
+ABI_UNITS = [
+    ("restir.cpp", ["-x", "hip"] + DEVICE),      # HIP host code, no KERNEL_FLAGS
+    ("abi_error.cpp", ["-x", "c++"]),            # no HIP header
+    ("layout.cpp", ["-x", "c++"]),
+]
+
+SOURCES = [("kernels.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS)] + ABI_UNITS + [
     ("mis.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("refit.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("reproject.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
@@ -43,16 +49,16 @@ SOURCES = [
     ("screen.cpp", ["-x", "c++"]),
 ]
 HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
-           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h"]
+           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "abi_error.h", "layout.h", "halo_segs.h"]
 
 
 def source_hash() -> str:
-    """sha256 over the device sources, the launcher (restir.cpp and route.h decide which buffers a pass reads and writes)
-    and the flags: identifies the kernels a profile was measured on (bench.py reports a committed PMC traffic figure
+    """sha256 over the device sources, the launcher (the C ABI's units and route.h decide which buffers a pass reads and
+    writes) and the flags: identifies the kernels a profile was measured on (bench.py reports a committed PMC traffic figure
     only when it matches)."""
     import hashlib
     h = hashlib.sha256()
-    for f in [SOURCES[0][0], SOURCES[1][0]] + HEADERS:
+    for f in [SOURCES[0][0]] + [u for u, _ in ABI_UNITS] + HEADERS:
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(f.encode() + b"\0" + fh.read())
     h.update(" ".join([c for c in COMMON + DEVICE + KERNEL_FLAGS if not c.startswith("-I")]).encode())   # flags, not paths
@@ -83,7 +89,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OUT, exist_ok=True)
     # a library newer than every source stands even where its object files are gone (a tree copied without them)
     if force or _stale(LIB, [d for s in SOURCES for d in _deps(s[0])]):
-        with cf.ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+        with cf.ThreadPoolExecutor(max_workers=min(len(SOURCES), 16)) as ex:
             objs = list(ex.map(lambda s: _compile(s[0], s[1], force), SOURCES))
         if force or _stale(LIB, objs):
             cmd = [HIPCC, "-shared", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-o", LIB] + objs

@@ -3,7 +3,8 @@
 // Drop-in for renderReSTIR / renderRayTraced (src/rendering/render.cpp:28-62, :268-290): a context owns one
 // HIP device + stream, the uploaded scene (materials, lights, flattened BVH) and the per-frame device
 // buffers; every pass is one hand-written gfx950 kernel (kernels.hip) enqueued on the context's stream.
-#include "restir_c.h"
+#include "abi_error.h"
+#include "layout.h"
 
 #include <rccl/rccl.h>
 
@@ -13,7 +14,6 @@
 #include <atomic>
 #include <cfloat>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <ctime>
@@ -41,28 +41,10 @@ using namespace romis;
 // ---------------------------------------------------------------------------------------------------------
 // errors
 namespace {
-thread_local std::string g_err;
-
-restir_status fail(restir_status s, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return s;
-}
-
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) return fail(RESTIR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-#define ST_TRY(expr)                            \
-    do {                                        \
-        restir_status s_ = (expr);              \
-        if (s_ != RESTIR_OK) return s_;         \
     } while (0)
 
 struct DevBuf {
@@ -371,7 +353,6 @@ struct restir_ctx {
 // pure host helpers
 extern "C" {
 
-const char* restir_last_error(void) { return g_err.c_str(); }
 int restir_abi_version(void) { return RESTIR_ABI_VERSION; }
 
 void restir_features_default(restir_features* out) {
@@ -442,279 +423,7 @@ void restir_camera_derive(const restir_camera* cam, restir_camera_frame* out) {
 
 }  // extern "C"
 
-namespace {
-// a layout's cuts are well formed: every column and every row of a column at least one pixel, the ends at the image
-restir_status layout_check(const restir_tile_layout* L) {
-    if (!L) return fail(RESTIR_ERR_INVALID, "tile layout is NULL");
-    const uint32_t tx = L->tiles_x, ty = L->tiles_y;
-    if (L->global_width == 0 || L->global_height == 0 || tx == 0 || ty == 0 || tx > RESTIR_MAX_TILES_X ||
-        ty > RESTIR_MAX_TILES_Y)
-        return fail(RESTIR_ERR_INVALID, "tile layout: bad size (W=%u H=%u tiles=%ux%u, at most %ux%u)", L->global_width,
-                    L->global_height, tx, ty, RESTIR_MAX_TILES_X, RESTIR_MAX_TILES_Y);
-    if (L->x_cuts[0] != 0 || L->x_cuts[tx] != L->global_width)
-        return fail(RESTIR_ERR_INVALID, "tile layout: x cuts must run from 0 to the width");
-    for (uint32_t c = 0; c < tx; c++) {
-        if (L->x_cuts[c + 1] <= L->x_cuts[c]) return fail(RESTIR_ERR_INVALID, "tile layout: x cuts not increasing at %u", c);
-        if (L->y_cuts[c][0] != 0 || L->y_cuts[c][ty] != L->global_height)
-            return fail(RESTIR_ERR_INVALID, "tile layout: column %u's y cuts must run from 0 to the height", c);
-        for (uint32_t r = 0; r < ty; r++)
-            if (L->y_cuts[c][r + 1] <= L->y_cuts[c][r])
-                return fail(RESTIR_ERR_INVALID, "tile layout: column %u's y cuts not increasing at %u", c, r);
-    }
-    return RESTIR_OK;
-}
-// pixels of cost cell i along an axis of n pixels split into m cells: x belongs to cell floor(x m / n)
-inline uint32_t cell_of(uint32_t x, uint32_t m, uint32_t n) { return (uint32_t)((uint64_t)x * m / n); }
-inline uint32_t cell_begin(uint32_t i, uint32_t m, uint32_t n) { return (uint32_t)(((uint64_t)i * n + m - 1) / m); }
-// pixels of [a, b) in cell i
-inline uint32_t cell_overlap(uint32_t i, uint32_t m, uint32_t n, uint32_t a, uint32_t b) {
-    const uint32_t c0 = std::max(cell_begin(i, m, n), a), c1 = std::min(cell_begin(i + 1, m, n), b);
-    return c1 > c0 ? c1 - c0 : 0u;
-}
-// the cost the grid puts on the rectangle [xa, xb) x [ya, yb) (each cell's cost spread evenly over its pixels)
-double rect_cost(const float* cost, uint32_t cw, uint32_t ch, uint32_t W, uint32_t H, uint32_t xa, uint32_t xb,
-                 uint32_t ya, uint32_t yb) {
-    double sum = 0.0;
-    const uint32_t j0 = cell_of(ya, ch, H), j1 = cell_of(yb - 1, ch, H), i0 = cell_of(xa, cw, W), i1 = cell_of(xb - 1, cw, W);
-    for (uint32_t j = j0; j <= j1; j++) {
-        const double fy = (double)cell_overlap(j, ch, H, ya, yb) / (cell_begin(j + 1, ch, H) - cell_begin(j, ch, H));
-        for (uint32_t i = i0; i <= i1; i++) {
-            const double fx = (double)cell_overlap(i, cw, W, xa, xb) / (cell_begin(i + 1, cw, W) - cell_begin(i, cw, W));
-            sum += (double)cost[(size_t)j * cw + i] * fx * fy;
-        }
-    }
-    return sum;
-}
-// cuts c[1..parts-1] of [0, n) at the equal-share points of the per-pixel prefix cost P (P[x] = cost of [0, x)),
-// rounded to multiples of `align`, every part at least `align` wide (the last takes the remainder)
-void share_cuts(const std::vector<double>& P, uint32_t n, uint32_t parts, uint32_t align, uint32_t* c) {
-    c[0] = 0;
-    c[parts] = n;
-    const double total = P[n];
-    for (uint32_t k = 1; k < parts; k++) {
-        const double target = total * k / parts;
-        const uint32_t x = (uint32_t)(std::lower_bound(P.begin(), P.begin() + n + 1, target) - P.begin());
-        uint64_t q = ((uint64_t)x + align / 2) / align * align;
-        const uint64_t lo = (uint64_t)c[k - 1] + align, hi = (uint64_t)n - (uint64_t)(parts - k) * align;
-        q = std::min(std::max(q, lo), hi);
-        c[k] = (uint32_t)q;
-    }
-}
-void layout_rect(const restir_tile_layout& L, uint32_t rank, uint32_t& x0, uint32_t& y0, uint32_t& w, uint32_t& h) {
-    const uint32_t tx = rank % L.tiles_x, ty = rank / L.tiles_x;
-    x0 = L.x_cuts[tx]; w = L.x_cuts[tx + 1] - x0;
-    y0 = L.y_cuts[tx][ty]; h = L.y_cuts[tx][ty + 1] - y0;
-}
-}  // namespace
-
 extern "C" {
-
-restir_status restir_layout_even(uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t tiles_y, restir_tile_layout* out) {
-    if (!out || W == 0 || H == 0 || tiles_x == 0 || tiles_y == 0 || tiles_x > W || tiles_y > H ||
-        tiles_x > RESTIR_MAX_TILES_X || tiles_y > RESTIR_MAX_TILES_Y)
-        return fail(RESTIR_ERR_INVALID, "restir_tile_plan: bad arguments (W=%u H=%u tiles=%ux%u)", W, H, tiles_x, tiles_y);
-    restir_tile_layout L{};
-    L.global_width = W; L.global_height = H; L.tiles_x = tiles_x; L.tiles_y = tiles_y;
-    // even split, remainder to the first tiles (deterministic, every pixel owned exactly once)
-    auto start = [](uint32_t n, uint32_t parts, uint32_t i) { return i * (n / parts) + std::min(i, n % parts); };
-    for (uint32_t c = 0; c <= tiles_x; c++) L.x_cuts[c] = start(W, tiles_x, c);
-    for (uint32_t c = 0; c < tiles_x; c++)
-        for (uint32_t r = 0; r <= tiles_y; r++) L.y_cuts[c][r] = start(H, tiles_y, r);
-    *out = L;
-    return RESTIR_OK;
-}
-
-restir_status restir_layout_balanced(uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t tiles_y, const float* cost,
-                                     uint32_t cw, uint32_t ch, uint32_t align_x, uint32_t align_y, restir_tile_layout* out,
-                                     double* efficiency) {
-    if (!out || !cost || cw == 0 || ch == 0 || cw > W || ch > H)
-        return fail(RESTIR_ERR_INVALID, "restir_layout_balanced: bad cost grid (%ux%u over %ux%u)", cw, ch, W, H);
-    restir_tile_layout L{};
-    ST_TRY(restir_layout_even(W, H, tiles_x, tiles_y, &L));
-    align_x = std::max(align_x, 1u);
-    align_y = std::max(align_y, 1u);
-    if ((uint64_t)tiles_x * align_x > W || (uint64_t)tiles_y * align_y > H)
-        return fail(RESTIR_ERR_INVALID, "restir_layout_balanced: %ux%u tiles of at least %ux%u px do not fit %ux%u", tiles_x,
-                    tiles_y, align_x, align_y, W, H);
-    for (size_t i = 0; i < (size_t)cw * ch; i++)
-        if (!(cost[i] >= 0.0f) || !std::isfinite(cost[i]))
-            return fail(RESTIR_ERR_INVALID, "restir_layout_balanced: cost cell %zu is negative or not finite", i);
-    // columns: the per-pixel-column cost (each cell's column total spread over its pixel columns), prefix-summed
-    std::vector<double> colsum(cw, 0.0);
-    for (uint32_t j = 0; j < ch; j++)
-        for (uint32_t i = 0; i < cw; i++) colsum[i] += cost[(size_t)j * cw + i];
-    std::vector<double> P(W + 1, 0.0);
-    for (uint32_t x = 0; x < W; x++) {
-        const uint32_t i = cell_of(x, cw, W);
-        P[x + 1] = P[x] + colsum[i] / (cell_begin(i + 1, cw, W) - cell_begin(i, cw, W));
-    }
-    share_cuts(P, W, tiles_x, align_x, L.x_cuts);
-    // each column: its own rows' cost, prefix-summed over pixel rows
-    std::vector<double> Q(H + 1, 0.0), rowsum(ch);
-    for (uint32_t c = 0; c < tiles_x; c++) {
-        const uint32_t xa = L.x_cuts[c], xb = L.x_cuts[c + 1];
-        for (uint32_t j = 0; j < ch; j++) {
-            double s = 0.0;
-            for (uint32_t i = cell_of(xa, cw, W); i <= cell_of(xb - 1, cw, W); i++)
-                s += (double)cost[(size_t)j * cw + i] * cell_overlap(i, cw, W, xa, xb) /
-                     (cell_begin(i + 1, cw, W) - cell_begin(i, cw, W));
-            rowsum[j] = s;
-        }
-        for (uint32_t y = 0; y < H; y++) {
-            const uint32_t j = cell_of(y, ch, H);
-            Q[y + 1] = Q[y] + rowsum[j] / (cell_begin(j + 1, ch, H) - cell_begin(j, ch, H));
-        }
-        share_cuts(Q, H, tiles_y, align_y, L.y_cuts[c]);
-    }
-    ST_TRY(layout_check(&L));
-    if (efficiency) {
-        std::vector<double> sh(tiles_x * tiles_y);
-        ST_TRY(restir_layout_shares(&L, cost, cw, ch, sh.data()));
-        double mx = 0.0, mean = 0.0;
-        for (double v : sh) { mx = std::max(mx, v); mean += v / sh.size(); }
-        *efficiency = mx > 0.0 ? mean / mx : 1.0;
-    }
-    *out = L;
-    return RESTIR_OK;
-}
-
-restir_status restir_layout_shares(const restir_tile_layout* L, const float* cost, uint32_t cw, uint32_t ch, double* out) {
-    ST_TRY(layout_check(L));
-    if (!cost || !out || cw == 0 || ch == 0 || cw > L->global_width || ch > L->global_height)
-        return fail(RESTIR_ERR_INVALID, "restir_layout_shares: bad cost grid");
-    const uint32_t n = L->tiles_x * L->tiles_y;
-    double total = 0.0;
-    for (uint32_t q = 0; q < n; q++) {
-        uint32_t x0, y0, w, h;
-        layout_rect(*L, q, x0, y0, w, h);
-        out[q] = rect_cost(cost, cw, ch, L->global_width, L->global_height, x0, x0 + w, y0, y0 + h);
-        total += out[q];
-    }
-    for (uint32_t q = 0; q < n; q++) out[q] = total > 0.0 ? out[q] / total : 1.0 / n;
-    return RESTIR_OK;
-}
-
-restir_status restir_layout_tile(const restir_tile_layout* L, uint32_t rank, uint32_t ghost, restir_tile* out) {
-    ST_TRY(layout_check(L));
-    if (!out || rank >= L->tiles_x * L->tiles_y)
-        return fail(RESTIR_ERR_INVALID, "restir_tile_plan: bad arguments (rank %u of %ux%u tiles)", rank, L->tiles_x,
-                    L->tiles_y);
-    const uint32_t W = L->global_width, H = L->global_height;
-    restir_tile t{};
-    t.global_width = W;
-    t.global_height = H;
-    layout_rect(*L, rank, t.x0, t.y0, t.width, t.height);
-    const uint32_t gx0 = t.x0 > ghost ? t.x0 - ghost : 0u;
-    const uint32_t gy0 = t.y0 > ghost ? t.y0 - ghost : 0u;
-    const uint32_t gx1 = std::min<uint64_t>((uint64_t)t.x0 + t.width + ghost, W);
-    const uint32_t gy1 = std::min<uint64_t>((uint64_t)t.y0 + t.height + ghost, H);
-    t.gx0 = gx0; t.gy0 = gy0; t.gwidth = gx1 - gx0; t.gheight = gy1 - gy0;
-    *out = t;
-    return RESTIR_OK;
-}
-
-restir_status restir_tile_plan(uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t tiles_y, uint32_t rank, uint32_t ghost,
-                               restir_tile* out) {
-    restir_tile_layout L;
-    if (!out || rank >= tiles_x * tiles_y)
-        return fail(RESTIR_ERR_INVALID, "restir_tile_plan: bad arguments (W=%u H=%u tiles=%ux%u rank=%u)", W, H, tiles_x,
-                    tiles_y, rank);
-    ST_TRY(restir_layout_even(W, H, tiles_x, tiles_y, &L));
-    return restir_layout_tile(&L, rank, ghost, out);
-}
-
-restir_status restir_layout_halo_plan(const restir_tile_layout* L, uint32_t rank, uint32_t radius, uint32_t N,
-                                      restir_halo_segment* send, restir_halo_segment* recv, uint32_t* count) {
-    if (!count || !send || !recv || N == 0) return fail(RESTIR_ERR_INVALID, "restir_halo_plan: null argument / N = 0");
-    const uint32_t W = L ? L->global_width : 0u, H = L ? L->global_height : 0u;
-    restir_tile me{};
-    ST_TRY(restir_layout_tile(L, rank, 0, &me));
-    struct R { uint64_t x0, y0, x1, y1; };
-    auto grow = [&](const restir_tile& t) {
-        return R{t.x0 > radius ? t.x0 - radius : 0u, t.y0 > radius ? t.y0 - radius : 0u,
-                 std::min<uint64_t>((uint64_t)t.x0 + t.width + radius, W), std::min<uint64_t>((uint64_t)t.y0 + t.height + radius, H)};
-    };
-    auto owned = [](const restir_tile& t) { return R{t.x0, t.y0, (uint64_t)t.x0 + t.width, (uint64_t)t.y0 + t.height}; };
-    auto meet = [](R a, R b) {
-        R r{std::max(a.x0, b.x0), std::max(a.y0, b.y0), std::min(a.x1, b.x1), std::min(a.y1, b.y1)};
-        if (r.x1 <= r.x0 || r.y1 <= r.y0) r = R{0, 0, 0, 0};
-        return r;
-    };
-    const uint32_t cap = *count;
-    uint32_t n = 0;
-    uint64_t so = 0, ro = 0;
-    for (uint32_t q = 0; q < L->tiles_x * L->tiles_y; q++) {
-        if (q == rank) continue;
-        restir_tile tq{};
-        ST_TRY(restir_layout_tile(L, q, 0, &tq));
-        const R s_ = meet(owned(me), grow(tq)), r_ = meet(owned(tq), grow(me));
-        if (s_.x1 == 0 || r_.x1 == 0) continue;
-        if (n >= cap) return fail(RESTIR_ERR_INVALID, "restir_halo_plan: more than %u segments", cap);
-        auto fill = [&](restir_halo_segment& g, R r, uint64_t& off) {
-            g.rank = q;
-            g.x0 = (uint32_t)r.x0; g.y0 = (uint32_t)r.y0;
-            g.width = (uint32_t)(r.x1 - r.x0); g.height = (uint32_t)(r.y1 - r.y0);
-            g.offset = off;
-            g.bytes = (uint64_t)g.width * g.height * N * 32u;
-            off += g.bytes;
-        };
-        fill(send[n], s_, so);
-        fill(recv[n], r_, ro);
-        n++;
-    }
-    *count = n;
-    return RESTIR_OK;
-}
-
-restir_status restir_halo_plan(uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t tiles_y, uint32_t rank, uint32_t radius,
-                               uint32_t N, restir_halo_segment* send, restir_halo_segment* recv, uint32_t* count) {
-    restir_tile_layout L;
-    ST_TRY(restir_layout_even(W, H, tiles_x, tiles_y, &L));
-    return restir_layout_halo_plan(&L, rank, radius, N, send, recv, count);
-}
-
-}  // extern "C"
-
-namespace {
-// The operations restir_halo_pass posts, from a plan: send i then recv i per segment (restir_halo_ops)
-void halo_ops_from(const restir_halo_segment* send, const restir_halo_segment* recv, uint32_t n, restir_halo_op* ops) {
-    auto op = [](uint32_t kind, const restir_halo_segment& g) {
-        restir_halo_op o{};
-        o.kind = kind; o.peer = g.rank; o.offset = g.offset; o.bytes = g.bytes;
-        o.x0 = g.x0; o.y0 = g.y0; o.width = g.width; o.height = g.height;
-        return o;
-    };
-    for (uint32_t i = 0; i < n; i++) {
-        ops[2 * i] = op(RESTIR_HALO_OP_SEND, send[i]);
-        ops[2 * i + 1] = op(RESTIR_HALO_OP_RECV, recv[i]);
-    }
-}
-}  // namespace
-
-extern "C" {
-
-restir_status restir_halo_ops(uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t tiles_y, uint32_t rank, uint32_t radius,
-                              uint32_t N, restir_halo_op* ops, uint32_t* count) {
-    restir_tile_layout L;
-    ST_TRY(restir_layout_even(W, H, tiles_x, tiles_y, &L));
-    return restir_layout_halo_ops(&L, rank, radius, N, ops, count);
-}
-
-restir_status restir_layout_halo_ops(const restir_tile_layout* L, uint32_t rank, uint32_t radius, uint32_t N,
-                                     restir_halo_op* ops, uint32_t* count) {
-    if (!count || !ops) return fail(RESTIR_ERR_INVALID, "restir_halo_ops: null argument");
-    restir_halo_segment sg[RESTIR_MAX_HALO_SEGS], rg_[RESTIR_MAX_HALO_SEGS];
-    uint32_t n = RESTIR_MAX_HALO_SEGS;
-    ST_TRY(restir_layout_halo_plan(L, rank, radius, N, sg, rg_, &n));
-    if (*count < 2 * n) {
-        const uint32_t need = 2 * n;
-        *count = need;
-        return fail(RESTIR_ERR_INVALID, "restir_halo_ops: capacity for %u operations needed", need);
-    }
-    halo_ops_from(sg, rg_, n, ops);
-    *count = 2 * n;
-    return RESTIR_OK;
-}
 
 restir_status restir_device_count(int* out) {
     if (!out) return fail(RESTIR_ERR_INVALID, "restir_device_count: null");
@@ -1026,6 +735,23 @@ Region grow_rect(const Region& base, uint32_t g) {
     uint64_t y1 = std::min<uint64_t>((uint64_t)base.ry0 + base.rh + g, (uint64_t)base.vy0 + base.vh);
     r.rx0 = x0; r.ry0 = y0; r.rw = (uint32_t)(x1 - x0); r.rh = (uint32_t)(y1 - y0);
     return r;
+}
+
+// A temporal predecessor fits the frame about to render tile t of a width x height image: its grid is the tile's computed
+// region (`what`: the caller's word for it), and it was rendered with this context's buffer layout.  ghost_rule
+// (restir_render with spatial passes): nor may the tile have a ghost zone -- the predecessor's is not recomputed.
+restir_status check_prev(const restir_ctx* c, const restir_frame* prev, uint32_t N, const restir_tile& t, uint32_t width,
+                         uint32_t height, const char* what, bool ghost_rule) {
+    if (prev->N != N || prev->vw != t.gwidth || prev->vh != t.gheight || prev->vx0 != t.gx0 || prev->vy0 != t.gy0 ||
+        prev->W != width || prev->H != height)
+        return fail(RESTIR_ERR_INVALID, "temporal predecessor grid does not match this %s / N", what);
+    const bool has_ghost = t.gwidth != t.width || t.gheight != t.height;
+    if (has_ghost && ghost_rule)
+        return fail(RESTIR_ERR_UNSUPPORTED, "temporal reuse on a ghost-zoned tile needs the predecessor's ghost zone: "
+                                            "render such tiles with the halo-exchange stages (restir_halo_begin)");
+    if (prev->records != (c->tuning.records != 0))
+        return fail(RESTIR_ERR_INVALID, "temporal predecessor grid was rendered with the other buffer layout");
+    return RESTIR_OK;
 }
 
 }  // namespace
@@ -1918,6 +1644,297 @@ static restir_status ensure_shadow_lists(restir_ctx* c, const Route& r, const Sc
     return RESTIR_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// A restir_render frame's decisions, taken before it allocates or enqueues anything (plan_frame)
+struct FramePlan {
+    bool temporal = false;           // a predecessor is combined
+    bool fused = false;              // same region: one kernel (kernels.hip k_primary_ris)
+    bool temporal_fused = false;     // ... with temporal reuse inside it (k_primary_ris_n{1,2}_lds_pt_temporal)
+    bool temporal_handles = false;   // ... which rebuilds the predecessor from its frame handles
+    int hkind = -1;                  // the passes' sample-handle kind (spatial_handle_kind; -1: none)
+    bool handles = false;            // the passes read and write sample handles (restir_ctx::hnd)
+    bool frame_handles = false;      // the last pass writes the returned grid's handles for the next frame
+    bool vis = false;                // the last pass's own-pixel shadow rays go on to final shading (a plane of the view)
+    uint32_t skip_mode = 0;          // what of background tiles RIS need not store (Ask::skip)
+    Route ris;                       // primary + RIS before handles and skip_mode were known: names the tile flags
+    Ask ris_ask;                     // what the frame asks of primary + RIS (gbuf_cached: after the allocations)
+    // the fused RIS kernel writes background-tile flags (ensure_tile_flags) that the passes and final shading read
+    bool flags() const { return fused && !temporal_fused && ris.flags; }
+};
+
+// One restir_render frame: the request and what is derived from it, then what each step leaves for the next
+struct Frame {
+    restir_ctx* c;
+    const restir_features* features;
+    const restir_frame* prev;
+    bool want_next;                  // the caller takes the frame's grid
+    uint32_t width, height, N, passes, frame;   // frame: the index the RNG keys take
+    restir_tile t;                   // the tile rendered: the caller's, or the whole image
+    FeaturesDev f;
+    hipStream_t st;
+    FrameBufs fb;
+    CameraDev camd;
+    Region view, owned;
+    SceneDev s;
+    uint8_t *vis, *tmiss;            // alloc: the own-pixel ray plane and the tile flags, null where the plan has none
+    Route last;                      // the route that produced grid cur (rp_out: its pdf cache holds its samples' pdfs)
+    int cur;
+
+    Region pass_rect(uint32_t pass) const { return grow_rect(owned, (passes - 1u - pass) * f.R); }
+    Ask pass_ask(const FramePlan& p, uint32_t pass, bool rp_ok) const {
+        const bool is_last = pass + 1 == passes;
+        Ask a;
+        a.hin = p.handles ? p.hkind : -1;
+        // a pass before the last is read by the next one's handles alone: no reservoir planes
+        a.hout = p.handles ? (!is_last || p.frame_handles) : false;
+        a.hout_dead = p.handles && !is_last;
+        // every neighbour of this pass lies in the region the cache's producer covered (RIS / temporal: the whole view;
+        // pass p - 1: the owned rect grown by (P - p) R)
+        a.rp_in = a.rp_nb = rp_ok;
+        // the last pass's pdf cache has no reader (final shading re-shades; the next frame's temporal pass evaluates its
+        // own): not written
+        a.rp_out = !is_last && fb.rp(0) != nullptr;
+        a.vis = is_last && p.vis;
+        a.flags = p.flags();
+        // a background pixel holds M = f.M after RIS and after every biased pass; an unbiased pass sums its neighbours'
+        // M, which only pass 0 knows
+        a.flags_m = (!f.unbiased || pass == 0) ? f.M : 0u;
+        a.gbuf = (p.skip_mode & 2u) ? 1u : 0u;
+        // final shading inside the last pass (final.fuse), offered where launch_final would read the pass's grid
+        // without an own-pixel ray plane; the last pass's rect is the owned rect (grow_rect(owned, 0)), also on
+        // ghost-zoned tiles.  Without a returned grid nothing else reads that pass's reservoir planes (the stage and
+        // halo paths keep their own buffers and the separate kernels): they are not stored
+        a.fin = is_last && !p.vis;
+        a.fin_dead = !want_next;
+        return a;
+    }
+    restir_status alloc(const FramePlan& p);
+    restir_status ris_stage(const FramePlan& p);
+    restir_status spatial_passes(const FramePlan& p);
+    restir_status hand_off(const FramePlan& p, restir_frame** out_next, float* out_rgb);
+};
+
+// The tile a frame renders (the whole image for a null one), consistent with the image; its computed region must hold
+// the ghost zone g = passes * radius the spatial passes read (clipped at the image border)
+restir_status frame_tile(const restir_tile* tile, uint32_t width, uint32_t height, uint64_t g, restir_tile& t) {
+    t = restir_tile{};
+    if (tile) {
+        t = *tile;
+        if (t.global_width != width || t.global_height != height)
+            return fail(RESTIR_ERR_INVALID, "tile global size %ux%u != %ux%u", t.global_width, t.global_height, width, height);
+        if (t.width == 0 || t.height == 0 || t.x0 + t.width > width || t.y0 + t.height > height || t.gx0 > t.x0 ||
+            t.gy0 > t.y0 || t.gx0 + t.gwidth < t.x0 + t.width || t.gy0 + t.gheight < t.y0 + t.height ||
+            t.gx0 + t.gwidth > width || t.gy0 + t.gheight > height)
+            return fail(RESTIR_ERR_INVALID, "inconsistent tile");
+    } else {
+        if (width == 0 || height == 0) return fail(RESTIR_ERR_INVALID, "empty image %ux%u", width, height);
+        t.global_width = width; t.global_height = height;
+        t.x0 = 0; t.y0 = 0; t.width = width; t.height = height;
+        t.gx0 = 0; t.gy0 = 0; t.gwidth = width; t.gheight = height;
+    }
+    uint32_t gx0 = t.x0 > g ? (uint32_t)(t.x0 - g) : 0u, gy0 = t.y0 > g ? (uint32_t)(t.y0 - g) : 0u;
+    uint64_t gx1 = std::min<uint64_t>((uint64_t)t.x0 + t.width + g, width);
+    uint64_t gy1 = std::min<uint64_t>((uint64_t)t.y0 + t.height + g, height);
+    if (t.gx0 > gx0 || t.gy0 > gy0 || (uint64_t)t.gx0 + t.gwidth < gx1 || (uint64_t)t.gy0 + t.gheight < gy1)
+        return fail(RESTIR_ERR_INVALID, "tile ghost zone narrower than passes * radius = %llu", (unsigned long long)g);
+    return RESTIR_OK;
+}
+
+// Pure host code over the frame's inputs: no HIP call, no allocation, nothing of the context written
+FramePlan plan_frame(const Frame& fr) {
+    const restir_ctx* c = fr.c;
+    const SceneDev& s = fr.s;
+    const FeaturesDev& f = fr.f;
+    const restir_tile& t = fr.t;
+    const uint32_t N = fr.N, passes = fr.passes;
+    FramePlan p;
+    p.temporal = fr.features->temporal_reuse && fr.prev != nullptr;
+    p.ris_ask = frame_ris_ask(c, s, fr.fb, p.temporal);
+    p.ris = route_primary_ris(s, fr.view, f, c->tuning, p.ris_ask);
+    p.fused = c->tuning.fuse_primary_ris && p.ris.ok;
+    // temporal reuse inside the fused kernel: the predecessor's reservoirs are combined while the RIS reservoirs are
+    // still in registers (no store / reload, no G-buffer re-read, one launch less)
+    p.temporal_fused = p.temporal && p.fused && route_primary_ris_temporal(s, fr.view, f, c->tuning, p.ris_ask).ok;
+    // sample handles (k_spatial1h): N = 1 biased passes over a point-light scene, written by the fused RIS kernel and by
+    // every pass but the last; 4 + 4 B per pixel and 16 B of slack (the planes are read a word at a time)
+    // (point lights: two 4-byte planes; a regular light grid: one float4 plane, k_spatial1g)
+    // With temporal reuse the passes read handles when the fused temporal kernel can rebuild the predecessor from its
+    // frame handles (point lights, the same scene upload): every M then bounded by RIS's plus the clamp's
+    const bool no_ghost = t.gwidth == t.width && t.gheight == t.height;
+    p.temporal_handles = p.temporal_fused && no_ghost && fr.prev->hgen != 0 && fr.prev->hgen == c->scene_gen;
+    // the M every sub-reservoir can hold entering the passes after temporal reuse: the current M plus each of the N
+    // predecessor sub-reservoirs clamped to clampM M + 1 (kernels.hip ris_pixel TEMP)
+    const uint64_t m_temporal = (uint64_t)f.M + (uint64_t)N * ((uint64_t)f.clamp_m * f.M + 1u);
+    p.hkind = (!p.fused || (p.temporal && !p.temporal_handles))
+                  ? -1
+                  : spatial_handle_kind(s, fr.view, f, c->tuning, passes, p.temporal ? m_temporal : 0u);
+    p.handles = p.hkind >= 0 && (!p.temporal || p.hkind == 0 || p.hkind == 2);
+    // the last pass also writes the returned grid's handles (point lights, no ghost ring) for the next frame, bounded as
+    // if that frame's temporal reuse had run (its M bound)
+    p.frame_handles = p.handles && (p.hkind == 0 || p.hkind == 2) && fr.want_next && no_ghost &&
+                      spatial_handle_kind(s, fr.view, f, c->tuning, passes, m_temporal) == p.hkind;
+    // the last pass's own-pixel shadow rays (unbiased + visibility reuse, N = 1) go on to final shading
+    p.vis = passes && fr.features->unbiased_combination && fr.features->spatial_reuse_visibility_check && N == 1;
+    if (p.flags() && passes > 0 && no_ghost) {
+        // the first spatial pass substitutes a background tile's known reservoirs (Route::bg_known); the later passes and
+        // final shading read the passes' outputs, and with no ghost ring the last pass overwrites the whole returned
+        // grid: RIS need not store those reservoirs
+        const bool skip_res = route_spatial(s, fr.pass_rect(0), f, c->tuning, fr.pass_ask(p, 0, p.ris.rp_out)).bg_known;
+        // a single unbiased pass (k_spatial1u) also substitutes a background pixel's G-buffer records (own and the Z
+        // loop's neighbours); final shading writes background tiles from the flags without reading them (its tiles are
+        // the RIS tiles here): nor are those stored.  Biased passes (every pass reads the flags) fix their window up
+        // instead (MissTiles::gbuf); knob miss.gbuf.
+        const uint32_t mg = c->tuning.miss_gbuf;
+        Ask with_flags;
+        with_flags.flags = true;
+        const bool gbuf_ok = mg && route_final(s, fr.owned, f, c->tuning, with_flags).flags &&
+                             (f.unbiased ? passes == 1u : (mg == 1u || t.gwidth >= 2048u));
+        p.skip_mode = skip_res ? (1u | (gbuf_ok ? 2u : 0u)) : 0u;
+    }
+    // the handle passes read RIS's samples through the handles alone, and a pass's output is read by the next pass's
+    // handles alone: their reservoir planes are dead (the last pass writes the returned grid's owned rect; a tile's
+    // ghost ring holds intermediate values, include/restir_c.h)
+    p.ris_ask.hout = p.ris_ask.hout_dead = p.handles;
+    p.ris_ask.skip = p.skip_mode;
+    return p;
+}
+
+// What the plan needs allocated: the handle planes, the own-pixel ray plane, the tile flags
+restir_status Frame::alloc(const FramePlan& p) {
+    if (p.handles)
+        for (int i = 0; i < 2; i++) ST_TRY(c->hnd[i].ensure((size_t)t.gwidth * t.gheight * (p.hkind ? 16u : 8u) + 16u));
+    if (p.vis) {
+        ST_TRY(fb.vis().ensure((size_t)t.gwidth * t.gheight));
+        vis = fb.vis().as<uint8_t>();
+    }
+    if (p.fused && !p.temporal_fused) ST_TRY(ensure_tile_flags(c, p.ris, view, tmiss));
+    return RESTIR_OK;
+}
+
+// Primary rays + RIS (+ temporal reuse) over the view into grid 0, in one of three launch shapes, and the kept
+// G-buffer's bookkeeping
+restir_status Frame::ris_stage(const FramePlan& p) {
+    Ask ris_ask = p.ris_ask;
+    Route& ris = last;
+    LaunchBufs b = fb.bufs(camd, restir_rng_key(c->seed, frame, RESTIR_STAGE_RIS, 0), 0, cur);
+    b.flags = tmiss;
+    auto route_fused = [&](const Ask& a) {
+        return p.temporal_fused ? route_primary_ris_temporal(s, view, f, c->tuning, a)
+                                : route_primary_ris(s, view, f, c->tuning, a);
+    };
+    // the view this frame's fused kernel would leave in the G-buffer planes; when they hold it already (the static
+    // camera of the reference's viewer loop), the k_gbuf_ris family runs over them instead (tuning "gbuf.reuse")
+    restir_ctx::GbufView gv;
+    if (p.fused) {
+        ris = route_fused(ris_ask);
+        gv = gbuf_view(c, s, camd, width, height, t, ris, tmiss);
+        ris_ask.gbuf_cached = c->tuning.gbuf_reuse && !fb.records && gbuf_reusable(c->gbuf, gv);
+        if (ris_ask.gbuf_cached) ris = route_fused(ris_ask);
+    } else {
+        ris = route_ris(s, view, f, c->tuning, ris_ask);
+    }
+    // kept by a frame that reuses it; a frame that traces replaces it once its launch is issued (any error return in
+    // between leaves none)
+    if (!ris_ask.gbuf_cached) c->gbuf.valid = false;
+    if (p.temporal_fused) {
+        ST_TRY(use_prev(prev, c->device, st, c->pool.get()));   // the predecessor's records are complete (its producer's stream)
+        b.tin = TemporalIn{fb.pa(prev), fb.pb(prev), restir_rng_key(c->seed, frame, RESTIR_STAGE_TEMPORAL, 0),
+                           p.handles ? fb.fhw(prev) : nullptr, p.handles ? fb.fhm(prev) : nullptr};
+        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ris, s, view, f, b, st));
+        used_prev(prev, st, c->pool.get());
+    } else if (p.fused) {
+        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ris, s, view, f, b, st));
+    } else {
+        TIMED(c, RESTIR_K_PRIMARY, launch_primary(route_primary(s, view, c->tuning), s, view, b, st));
+        TIMED(c, RESTIR_K_RIS, launch_ris(ris, s, view, f, b, st));
+    }
+    if (ris_ask.gbuf_cached) {
+        c->gbuf_reuses++;
+        c->gbuf_streak = c->gbuf_streak_lights == c->scene_gen ? c->gbuf_streak + 1u : 1u;
+    } else {
+        c->gbuf_streak = 0u;
+        if (p.fused && !fb.records) {
+            c->gbuf = gv;
+            c->gbuf.valid = true;
+            c->gbuf_epoch++;
+        }
+    }
+    c->gbuf_streak_lights = c->scene_gen;
+    c->last_px = (uint64_t)t.gwidth * t.gheight;   // restir_background_pixels
+    c->tmiss_w = tmiss ? t.gwidth : 0u;
+    c->tmiss_h = tmiss ? t.gheight : 0u;
+    if (p.temporal && !p.temporal_fused) {
+        ST_TRY(use_prev(prev, c->device, st, c->pool.get()));   // the predecessor's records are complete (its producer's stream)
+        TIMED(c, RESTIR_K_TEMPORAL,
+              launch_temporal(s, view, f, restir_rng_key(c->seed, frame, RESTIR_STAGE_TEMPORAL, 0), camd.origin, fb.nt(cur),
+                              fb.pm(), fb.ra(cur), fb.rb(cur), fb.pa(prev), fb.pb(prev), fb.ra(cur), fb.rb(cur), nullptr,
+                              fb.rp(cur), fb.rp(cur), st));
+        used_prev(prev, st, c->pool.get());
+    }
+    return RESTIR_OK;
+}
+
+// For each pass: route, launch, from grid cur into its partner; then final shading unless the last pass ran it
+restir_status Frame::spatial_passes(const FramePlan& p) {
+    LaunchBufs b;
+    for (uint32_t pass = 0; pass < passes; pass++) {
+        const Region pr = pass_rect(pass);
+        const int nxt = cur ^ 1;
+        Ask ask = pass_ask(p, pass, last.rp_out);
+        // the fused last pass's rays over the view's shadow lists, from the second still frame on (final.lists)
+        ask.shadow_lists = ask.fin && c->gbuf_streak >= c->tuning.final_lists_after;
+        last = route_spatial(s, pr, f, c->tuning, ask);
+        b = fb.bufs(camd, restir_rng_key(c->seed, frame, RESTIR_STAGE_SPATIAL, pass), cur, nxt);
+        b.vis = vis;
+        b.flags = tmiss;
+        if (last.lists) {
+            ST_TRY(ensure_shadow_lists(c, last, s, pr, fb.pm(), tmiss, st));
+            b.shadow_lists = c->slists.as<uint4>();
+            c->shadow_list_frames++;
+        }
+        if (pass + 1 == passes) b.hout = fb.fh(nxt);   // (frame_handles; the route names them)
+        TIMED(c, RESTIR_K_SPATIAL, launch_spatial(last, s, pr, f, b, st));
+        cur = nxt;
+    }
+    if (!last.final_done) {
+        Ask fin_ask;
+        fin_ask.vis = last.vis;
+        fin_ask.flags = tmiss != nullptr;
+        b = fb.bufs(camd, 0u, cur, cur);
+        b.vis = vis;
+        b.flags = tmiss;
+        TIMED(c, RESTIR_K_FINAL, launch_final(route_final(s, owned, f, c->tuning, fin_ask), s, owned, f, b, st));
+    }
+    c->cur = cur;
+    return RESTIR_OK;
+}
+
+// The frame's grid (cur) to the caller as a frame handle, its image to the caller's memory
+restir_status Frame::hand_off(const FramePlan& p, restir_frame** out_next, float* out_rgb) {
+    if (out_next) {
+        restir_frame* fr = make_frame(c->pool, c->device, st);   // after the final kernel, the records' last reader
+        fr->W = width; fr->H = height; fr->vx0 = t.gx0; fr->vy0 = t.gy0; fr->vw = t.gwidth; fr->vh = t.gheight; fr->N = N;
+        // hand the final grid's records to the frame (no copy); the context re-allocates lazily
+        std::swap(fr->rec, c->rec[cur]);
+        fr->records = fb.records;
+        fr->hgen = p.frame_handles ? c->scene_gen : 0u;
+        fr->hzero = s.num_lights;
+        *out_next = fr;
+    }
+    if (out_rgb) {
+        HIP_TRY(hipMemcpyAsync(out_rgb, fb.rgb().p, (size_t)t.width * t.height * 12, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return RESTIR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 // renderReSTIR (render.cpp:28-62)
 restir_status restir_render(restir_ctx* c, const restir_camera* cam, const restir_features* features, uint32_t width,
                             uint32_t height, const restir_tile* tile, const restir_frame* prev, restir_frame** out_next,
@@ -1937,245 +1954,34 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
         return render_mis(c, cam, features, width, height, out_rgb);
     }
 
-    restir_tile t{};
-    if (tile) {
-        t = *tile;
-        if (t.global_width != width || t.global_height != height)
-            return fail(RESTIR_ERR_INVALID, "tile global size %ux%u != %ux%u", t.global_width, t.global_height, width, height);
-        if (t.width == 0 || t.height == 0 || t.x0 + t.width > width || t.y0 + t.height > height || t.gx0 > t.x0 ||
-            t.gy0 > t.y0 || t.gx0 + t.gwidth < t.x0 + t.width || t.gy0 + t.gheight < t.y0 + t.height ||
-            t.gx0 + t.gwidth > width || t.gy0 + t.gheight > height)
-            return fail(RESTIR_ERR_INVALID, "inconsistent tile");
-    } else {
-        if (width == 0 || height == 0) return fail(RESTIR_ERR_INVALID, "empty image %ux%u", width, height);
-        t.global_width = width; t.global_height = height;
-        t.x0 = 0; t.y0 = 0; t.width = width; t.height = height;
-        t.gx0 = 0; t.gy0 = 0; t.gwidth = width; t.gheight = height;
-    }
-    const FeaturesDev f = to_dev(features);
-    const uint32_t N = f.N;
-    const uint32_t passes = features->spatial_reuse ? features->spatial_resampling_passes : 0u;
-    // the computed region must hold the ghost zone the spatial passes read (clipped at the image border)
-    {
-        const uint64_t g = (uint64_t)passes * f.R;
-        uint32_t gx0 = t.x0 > g ? (uint32_t)(t.x0 - g) : 0u, gy0 = t.y0 > g ? (uint32_t)(t.y0 - g) : 0u;
-        uint64_t gx1 = std::min<uint64_t>((uint64_t)t.x0 + t.width + g, width);
-        uint64_t gy1 = std::min<uint64_t>((uint64_t)t.y0 + t.height + g, height);
-        if (t.gx0 > gx0 || t.gy0 > gy0 || (uint64_t)t.gx0 + t.gwidth < gx1 || (uint64_t)t.gy0 + t.gheight < gy1)
-            return fail(RESTIR_ERR_INVALID, "tile ghost zone narrower than passes * radius = %llu", (unsigned long long)g);
-    }
-    const bool temporal = features->temporal_reuse && prev != nullptr;
-    if (temporal) {
-        if (prev->N != N || prev->vw != t.gwidth || prev->vh != t.gheight || prev->vx0 != t.gx0 || prev->vy0 != t.gy0 ||
-            prev->W != width || prev->H != height)
-            return fail(RESTIR_ERR_INVALID, "temporal predecessor grid does not match this frame's region / N");
-        const bool has_ghost = t.gwidth != t.width || t.gheight != t.height;
-        if (has_ghost && passes > 0)
-            return fail(RESTIR_ERR_UNSUPPORTED, "temporal reuse on a ghost-zoned tile needs the predecessor's ghost zone: "
-                                                "render such tiles with the halo-exchange stages (restir_halo_begin)");
-        if (prev->records != (c->tuning.records != 0))
-            return fail(RESTIR_ERR_INVALID, "temporal predecessor grid was rendered with the other buffer layout");
-    }
+    Frame fr{};
+    fr.c = c; fr.features = features; fr.width = width; fr.height = height; fr.prev = prev; fr.want_next = out_next != nullptr;
+    fr.f = to_dev(features);
+    fr.N = fr.f.N;
+    fr.passes = features->spatial_reuse ? features->spatial_resampling_passes : 0u;
+    fr.st = c->stream;
+    restir_tile& t = fr.t;
+    ST_TRY(frame_tile(tile, width, height, (uint64_t)fr.passes * fr.f.R, t));
+    if (features->temporal_reuse && prev != nullptr)
+        ST_TRY(check_prev(c, prev, fr.N, t, width, height, "frame's region", fr.passes > 0));
 
-    const hipStream_t st = c->stream;
-    FrameBufs fb;
-    ST_TRY(ensure_records(c, t.gwidth, t.gheight, N, fb));
+    ST_TRY(ensure_records(c, t.gwidth, t.gheight, fr.N, fr.fb));
     c->stage_ok = false;   // ensure_records re-sized the shared view state: the stage API must be reconfigured
-    ST_TRY(fb.rgb().ensure((size_t)t.width * t.height * 12));
+    ST_TRY(fr.fb.rgb().ensure((size_t)t.width * t.height * 12));
     c->rgb_w = t.width; c->rgb_h = t.height;
 
-    const CameraDev camd = camera_dev(cam);
-    const Region view = fb.region(make_region(width, height, t.gx0, t.gy0, t.gwidth, t.gheight, t.gx0, t.gy0, t.gwidth, t.gheight));
-    const Region owned = fb.region(make_region(width, height, t.gx0, t.gy0, t.gwidth, t.gheight, t.x0, t.y0, t.width, t.height));
-    const uint32_t frame = c->frame_index++;
-    SceneDev s;
-    ST_TRY(scene_for(c, f, (size_t)t.gwidth * t.gheight, s, &fb.uv()));
-    float4* pm = fb.pm();
-    int cur = 0;
+    fr.camd = camera_dev(cam);
+    fr.view = fr.fb.region(make_region(width, height, t.gx0, t.gy0, t.gwidth, t.gheight, t.gx0, t.gy0, t.gwidth, t.gheight));
+    fr.owned = fr.fb.region(make_region(width, height, t.gx0, t.gy0, t.gwidth, t.gheight, t.x0, t.y0, t.width, t.height));
+    fr.frame = c->frame_index++;
+    ST_TRY(scene_for(c, fr.f, (size_t)t.gwidth * t.gheight, fr.s, &fr.fb.uv()));
 
-    Ask ris_ask = frame_ris_ask(c, s, fb, temporal);
-    Route ris = route_primary_ris(s, view, f, c->tuning, ris_ask);
-    const bool fused = c->tuning.fuse_primary_ris && ris.ok;   // same region: one kernel (kernels.hip k_primary_ris)
-    // temporal reuse inside the fused kernel (k_primary_ris_n{1,2}_lds_pt_temporal): the predecessor's reservoirs are
-    // combined while the RIS reservoirs are still in registers (no store / reload, no G-buffer re-read, one launch less)
-    const bool temporal_fused = temporal && fused && route_primary_ris_temporal(s, view, f, c->tuning, ris_ask).ok;
-    // sample handles (k_spatial1h): N = 1 biased passes over a point-light scene, written by the fused RIS kernel and by
-    // every pass but the last; 4 + 4 B per pixel and 16 B of slack (the planes are read a word at a time)
-    // (point lights: two 4-byte planes; a regular light grid: one float4 plane, k_spatial1g)
-    // With temporal reuse the passes read handles when the fused temporal kernel can rebuild the predecessor from its
-    // frame handles (point lights, the same scene upload): every M then bounded by RIS's plus the clamp's
-    const bool no_ghost = t.gwidth == t.width && t.gheight == t.height;
-    const bool temporal_handles = temporal_fused && no_ghost && prev->hgen != 0 && prev->hgen == c->scene_gen;
-    // the M every sub-reservoir can hold entering the passes after temporal reuse: the current M plus each of the N
-    // predecessor sub-reservoirs clamped to clampM M + 1 (kernels.hip ris_pixel TEMP)
-    const uint64_t m_temporal = (uint64_t)f.M + (uint64_t)N * ((uint64_t)f.clamp_m * f.M + 1u);
-    const int hkind = (!fused || (temporal && !temporal_handles))
-                          ? -1
-                          : spatial_handle_kind(s, view, f, c->tuning, passes, temporal ? m_temporal : 0u);
-    const bool handles = hkind >= 0 && (!temporal || hkind == 0 || hkind == 2);
-    // the last pass also writes the returned grid's handles (point lights, no ghost ring) for the next frame, bounded as
-    // if that frame's temporal reuse had run (its M bound)
-    const bool frame_handles = handles && (hkind == 0 || hkind == 2) && out_next && no_ghost &&
-                               spatial_handle_kind(s, view, f, c->tuning, passes, m_temporal) == hkind;
-    if (handles)
-        for (int i = 0; i < 2; i++) ST_TRY(c->hnd[i].ensure((size_t)t.gwidth * t.gheight * (hkind ? 16u : 8u) + 16u));
-    // the last pass's own-pixel shadow rays (unbiased + visibility reuse, N = 1) go on to final shading
-    uint8_t* vis = nullptr;
-    if (passes && features->unbiased_combination && features->spatial_reuse_visibility_check && N == 1) {
-        ST_TRY(fb.vis().ensure((size_t)t.gwidth * t.gheight));
-        vis = fb.vis().as<uint8_t>();
-    }
-    uint8_t* tmiss = nullptr;
-    if (fused && !temporal_fused) ST_TRY(ensure_tile_flags(c, ris, view, tmiss));
-    uint32_t skip_mode = 0u;
-    auto pass_ask = [&](uint32_t pass, bool rp_ok) {
-        const bool last = pass + 1 == passes;
-        Ask a;
-        a.hin = handles ? hkind : -1;
-        // a pass before the last is read by the next one's handles alone: no reservoir planes
-        a.hout = handles ? (!last || frame_handles) : false;
-        a.hout_dead = handles && !last;
-        // every neighbour of this pass lies in the region the cache's producer covered (RIS / temporal: the whole view;
-        // pass p - 1: the owned rect grown by (P - p) R)
-        a.rp_in = a.rp_nb = rp_ok;
-        // the last pass's pdf cache has no reader (final shading re-shades; the next frame's temporal pass evaluates its
-        // own): not written
-        a.rp_out = !last && fb.rp(0) != nullptr;
-        a.vis = last && vis;
-        a.flags = tmiss != nullptr;
-        // a background pixel holds M = f.M after RIS and after every biased pass; an unbiased pass sums its neighbours'
-        // M, which only pass 0 knows
-        a.flags_m = (!f.unbiased || pass == 0) ? f.M : 0u;
-        a.gbuf = (skip_mode & 2u) ? 1u : 0u;
-        // final shading inside the last pass (final.fuse), offered where launch_final would read the pass's grid
-        // without an own-pixel ray plane; the last pass's rect is the owned rect (grow_rect(owned, 0)), also on
-        // ghost-zoned tiles.  Without a returned grid nothing else reads that pass's reservoir planes (the stage and
-        // halo paths keep their own buffers and the separate kernels): they are not stored
-        a.fin = last && !vis;
-        a.fin_dead = out_next == nullptr;
-        return a;
-    };
-    auto pass_rect = [&](uint32_t pass) { return grow_rect(owned, (passes - 1u - pass) * f.R); };
-    if (tmiss && passes > 0 && no_ghost) {
-        // the first spatial pass substitutes a background tile's known reservoirs (Route::bg_known); the later passes and
-        // final shading read the passes' outputs, and with no ghost ring the last pass overwrites the whole returned
-        // grid: RIS need not store those reservoirs
-        const bool skip_res = route_spatial(s, pass_rect(0), f, c->tuning, pass_ask(0, ris.rp_out)).bg_known;
-        // a single unbiased pass (k_spatial1u) also substitutes a background pixel's G-buffer records (own and the Z
-        // loop's neighbours); final shading writes background tiles from the flags without reading them (its tiles are
-        // the RIS tiles here): nor are those stored.  Biased passes (every pass reads the flags) fix their window up
-        // instead (MissTiles::gbuf); knob miss.gbuf.
-        const uint32_t mg = c->tuning.miss_gbuf;
-        Ask with_flags;
-        with_flags.flags = true;
-        const bool gbuf_ok = mg && route_final(s, owned, f, c->tuning, with_flags).flags &&
-                             (f.unbiased ? passes == 1u : (mg == 1u || t.gwidth >= 2048u));
-        skip_mode = skip_res ? (1u | (gbuf_ok ? 2u : 0u)) : 0u;
-    }
-    // the handle passes read RIS's samples through the handles alone, and a pass's output is read by the next pass's
-    // handles alone: their reservoir planes are dead (the last pass writes the returned grid's owned rect; a tile's
-    // ghost ring holds intermediate values, include/restir_c.h)
-    ris_ask.hout = ris_ask.hout_dead = handles;
-    ris_ask.skip = skip_mode;
-    LaunchBufs b = fb.bufs(camd, restir_rng_key(c->seed, frame, RESTIR_STAGE_RIS, 0), 0, cur);
-    b.flags = tmiss;
-    // the view this frame's fused kernel would leave in the G-buffer planes; when they hold it already (the static
-    // camera of the reference's viewer loop), the k_gbuf_ris family runs over them instead (tuning "gbuf.reuse")
-    restir_ctx::GbufView gv;
-    if (fused) {
-        ris = temporal_fused ? route_primary_ris_temporal(s, view, f, c->tuning, ris_ask)
-                             : route_primary_ris(s, view, f, c->tuning, ris_ask);
-        gv = gbuf_view(c, s, camd, width, height, t, ris, tmiss);
-        ris_ask.gbuf_cached = c->tuning.gbuf_reuse && !fb.records && gbuf_reusable(c->gbuf, gv);
-    }
-    // kept by a frame that reuses it; a frame that traces replaces it once its launch is issued (any error return in
-    // between leaves none)
-    if (!ris_ask.gbuf_cached) c->gbuf.valid = false;
-    if (temporal_fused) {
-        ris = route_primary_ris_temporal(s, view, f, c->tuning, ris_ask);
-        ST_TRY(use_prev(prev, c->device, st, c->pool.get()));   // the predecessor's records are complete (its producer's stream)
-        b.tin = TemporalIn{fb.pa(prev), fb.pb(prev), restir_rng_key(c->seed, frame, RESTIR_STAGE_TEMPORAL, 0),
-                           handles ? fb.fhw(prev) : nullptr, handles ? fb.fhm(prev) : nullptr};
-        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ris, s, view, f, b, st));
-        used_prev(prev, st, c->pool.get());
-    } else if (fused) {
-        ris = route_primary_ris(s, view, f, c->tuning, ris_ask);
-        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ris, s, view, f, b, st));
-    } else {
-        ris = route_ris(s, view, f, c->tuning, ris_ask);
-        TIMED(c, RESTIR_K_PRIMARY, launch_primary(route_primary(s, view, c->tuning), s, view, b, st));
-        TIMED(c, RESTIR_K_RIS, launch_ris(ris, s, view, f, b, st));
-    }
-    if (ris_ask.gbuf_cached) {
-        c->gbuf_reuses++;
-        c->gbuf_streak = c->gbuf_streak_lights == c->scene_gen ? c->gbuf_streak + 1u : 1u;
-    } else {
-        c->gbuf_streak = 0u;
-        if (fused && !fb.records) {
-            c->gbuf = gv;
-            c->gbuf.valid = true;
-            c->gbuf_epoch++;
-        }
-    }
-    c->gbuf_streak_lights = c->scene_gen;
-    c->last_px = (uint64_t)t.gwidth * t.gheight;   // restir_background_pixels
-    c->tmiss_w = tmiss ? t.gwidth : 0u;
-    c->tmiss_h = tmiss ? t.gheight : 0u;
-    if (temporal && !temporal_fused) {
-        ST_TRY(use_prev(prev, c->device, st, c->pool.get()));   // the predecessor's records are complete (its producer's stream)
-        TIMED(c, RESTIR_K_TEMPORAL,
-              launch_temporal(s, view, f, restir_rng_key(c->seed, frame, RESTIR_STAGE_TEMPORAL, 0), camd.origin, fb.nt(cur), pm,
-                              fb.ra(cur), fb.rb(cur), fb.pa(prev), fb.pb(prev), fb.ra(cur), fb.rb(cur), nullptr,
-                              fb.rp(cur), fb.rp(cur), st));
-        used_prev(prev, st, c->pool.get());
-    }
-    // for each pass: route, launch.  rp_ok: the current grid's target-pdf cache holds its samples' pdfs
-    Route last = ris;
-    for (uint32_t pass = 0; pass < passes; pass++) {
-        const Region pr = pass_rect(pass);
-        const int nxt = cur ^ 1;
-        Ask ask = pass_ask(pass, last.rp_out);
-        // the fused last pass's rays over the view's shadow lists, from the second still frame on (final.lists)
-        ask.shadow_lists = ask.fin && c->gbuf_streak >= c->tuning.final_lists_after;
-        last = route_spatial(s, pr, f, c->tuning, ask);
-        b = fb.bufs(camd, restir_rng_key(c->seed, frame, RESTIR_STAGE_SPATIAL, pass), cur, nxt);
-        b.vis = vis;
-        b.flags = tmiss;
-        if (last.lists) {
-            ST_TRY(ensure_shadow_lists(c, last, s, pr, pm, tmiss, st));
-            b.shadow_lists = c->slists.as<uint4>();
-            c->shadow_list_frames++;
-        }
-        if (pass + 1 == passes) b.hout = fb.fh(nxt);   // (frame_handles; the route names them)
-        TIMED(c, RESTIR_K_SPATIAL, launch_spatial(last, s, pr, f, b, st));
-        cur = nxt;
-    }
-    if (!last.final_done) {
-        Ask fin_ask;
-        fin_ask.vis = last.vis;
-        fin_ask.flags = tmiss != nullptr;
-        b = fb.bufs(camd, 0u, cur, cur);
-        b.vis = vis;
-        b.flags = tmiss;
-        TIMED(c, RESTIR_K_FINAL, launch_final(route_final(s, owned, f, c->tuning, fin_ask), s, owned, f, b, st));
-    }
-    c->cur = cur;
-
-    if (out_next) {
-        restir_frame* fr = make_frame(c->pool, c->device, st);   // after the final kernel, the records' last reader
-        fr->W = width; fr->H = height; fr->vx0 = t.gx0; fr->vy0 = t.gy0; fr->vw = t.gwidth; fr->vh = t.gheight; fr->N = N;
-        // hand the final grid's records to the frame (no copy); the context re-allocates lazily
-        std::swap(fr->rec, c->rec[cur]);
-        fr->records = fb.records;
-        fr->hgen = frame_handles ? c->scene_gen : 0u;
-        fr->hzero = s.num_lights;
-        *out_next = fr;
-    }
-    if (out_rgb) {
-        HIP_TRY(hipMemcpyAsync(out_rgb, fb.rgb().p, (size_t)t.width * t.height * 12, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return RESTIR_OK;
+    // the decisions, the allocations they imply, then the launches in stream order
+    const FramePlan p = plan_frame(fr);
+    ST_TRY(fr.alloc(p));
+    ST_TRY(fr.ris_stage(p));
+    ST_TRY(fr.spatial_passes(p));
+    return fr.hand_off(p, out_next, out_rgb);
 }
 
 // One tile (validated) by the whole-image path when it is the whole image, else by the tile path; either consumes one
@@ -2874,11 +2680,7 @@ restir_status restir_halo_begin_layout(restir_ctx* c, const restir_camera* cam, 
     }
     const bool temporal = features->temporal_reuse && prev != nullptr;
     if (temporal) {
-        if (prev->N != f.N || prev->vw != t.gwidth || prev->vh != t.gheight || prev->vx0 != t.gx0 ||
-            prev->vy0 != t.gy0 || prev->W != width || prev->H != height)
-            return fail(RESTIR_ERR_INVALID, "temporal predecessor grid does not match this tile's view / N");
-        if (prev->records != (c->tuning.records != 0))
-            return fail(RESTIR_ERR_INVALID, "temporal predecessor grid was rendered with the other buffer layout");
+        ST_TRY(check_prev(c, prev, f.N, t, width, height, "tile's view", false));
         ST_TRY(use_prev(prev, c->device, c->stream, c->pool.get()));
     }
     auto& h = c->halo;

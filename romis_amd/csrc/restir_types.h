@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "halo_segs.h"
+
 #define RESTIR_MAX_N_DEV 32u
 
 // material pow modes (std::pow(cosTheta, shininess), shading.cpp:26)
@@ -209,7 +211,6 @@ struct Tuning {
 };
 
 // Halo segments of one exchange (restir_halo_plan), pixel prefix offsets into the packed buffer.
-#define RESTIR_MAX_HALO_SEGS 8u
 struct HaloSegs {
     uint32_t n;
     uint32_t x0[RESTIR_MAX_HALO_SEGS], y0[RESTIR_MAX_HALO_SEGS], w[RESTIR_MAX_HALO_SEGS], h[RESTIR_MAX_HALO_SEGS];
