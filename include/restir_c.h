@@ -409,6 +409,44 @@ restir_status restir_synchronize(restir_ctx* ctx);
 /* Last rendered image (owned pixels), host float RGB, row 0 = top. */
 restir_status restir_download_rgb(restir_ctx* ctx, float* out_rgb, size_t count);
 
+/* ---- presenting a frame: snapshots of the last image through a pinned, pipelined read-back ------------------
+ * The last rendered image (what restir_download_rgb serves: float3 per owned pixel, row 0 = top) converted on the
+ * device and copied into pinned host memory without stalling the frames behind it.  Formats:
+ *   RESTIR_IMAGE_RGB32F           the floats themselves, 12 bytes per pixel, bit for bit
+ *   RESTIR_IMAGE_RGBA8            restir_rgb_to_rgba8's bytes (Screen::writeBitmapToFile's conversion), 4 per pixel
+ *   RESTIR_IMAGE_BGRA8_BOTTOM_UP  the same bytes as stbi_write_bmp's pixel body: B, G, R, A, the last image row first
+ *                                 (a BMP file = the header + this buffer)
+ * restir_image_begin takes one of the context's RESTIR_MAX_IMAGES_IN_FLIGHT slots -- a device staging buffer and a
+ * pinned host buffer, created on first need, grown for a larger image, kept for re-use, freed by restir_destroy --,
+ * enqueues the conversion (RGB32F: a device-to-device copy) on the context's stream behind the frame that produced
+ * the image, then the device-to-host copy on the context's copy stream (created by the first restir_image_begin)
+ * behind the conversion, and returns without synchronising anything.  The snapshot lives in staging: the next
+ * restir_render may overwrite the image at once, and only the copy -- not the frames enqueued after it -- is waited
+ * for.  restir_image_ready never blocks; restir_image_wait blocks until this snapshot's copy has landed and returns
+ * the pinned bytes (restir_image_info's `bytes` of them), valid until restir_image_release, which waits for the copy
+ * if it has not landed and frees the slot for re-use (NULL: no-op).
+ * RESTIR_ERR_STATE: nothing rendered yet, or RESTIR_MAX_IMAGES_IN_FLIGHT snapshots unreleased; RESTIR_ERR_INVALID: a
+ * NULL argument or an unknown format.  restir_destroy waits for the outstanding copies and frees the slots: handles
+ * still unreleased are invalid afterwards and must not be used, not even released.  A handle belongs to its context
+ * and is used from one thread at a time, like the context.  Between restir_halo_begin and restir_halo_end the image
+ * has its size but not yet its pixels: a snapshot taken there holds undefined content (as restir_download_rgb would).
+ * restir_download_rgba8: begin(RGBA8), wait, memcpy, release -- `pixels` = the capacity of out_rgba in pixels
+ * (RESTIR_ERR_INVALID when below the image's).  restir_write_image_bmp: the last image as the file restir_write_bmp
+ * writes from its floats, from a BGRA8_BOTTOM_UP snapshot (RESTIR_ERR_INVALID when the file cannot be written).
+ * The conversion launch has no RESTIR_K_* slot: restir_timings does not see it. */
+typedef enum restir_image_format { RESTIR_IMAGE_RGB32F = 0, RESTIR_IMAGE_RGBA8 = 1,
+                                   RESTIR_IMAGE_BGRA8_BOTTOM_UP = 2 } restir_image_format;
+typedef struct restir_image restir_image;
+#define RESTIR_MAX_IMAGES_IN_FLIGHT 4u
+restir_status restir_image_begin(restir_ctx* ctx, uint32_t format, restir_image** out);
+restir_status restir_image_info(const restir_image* image, uint32_t* width, uint32_t* height, uint32_t* format,
+                                size_t* bytes);   /* any out pointer may be NULL */
+restir_status restir_image_ready(restir_image* image, int* ready);
+restir_status restir_image_wait(restir_image* image, const void** data);
+void          restir_image_release(restir_image* image);
+restir_status restir_download_rgba8(restir_ctx* ctx, uint8_t* out_rgba, size_t pixels);
+restir_status restir_write_image_bmp(restir_ctx* ctx, const char* path);
+
 /* ---- stage-level access for parity tests and profiling ---------------------------------------------- *
  * Buffers are the device SoA layout (DESIGN.md "Data layout"), one entry per pixel of the computed region
  * (row-major, y = 0 bottom), and for reservoirs [N][pixels]:
@@ -599,6 +637,9 @@ restir_status restir_rgb_to_rgba8(const float* rgb, size_t pixels, uint8_t* rgba
 restir_status restir_encode_bmp(const float* rgb, uint32_t width, uint32_t height, uint8_t* out, size_t capacity,
                                 size_t* length);
 restir_status restir_write_bmp(const char* path, const float* rgb, uint32_t width, uint32_t height);
+/* The bytes restir_encode_bmp puts before the pixels of a width x height image (the file and V4 headers): a
+ * RESTIR_IMAGE_BGRA8_BOTTOM_UP snapshot appended to them is the BMP file.  out == NULL queries *length. */
+restir_status restir_bmp_header(uint32_t width, uint32_t height, uint8_t* out, size_t capacity, size_t* length);
 restir_status restir_features_json(const restir_features* features, const restir_features_record_extra* extra,
                                    char* out, size_t capacity, size_t* length);
 

@@ -179,6 +179,54 @@ private:
     restir_frame* frame_;
 };
 
+// A snapshot of a Renderer's last image on its way to pinned host memory (restir_image_begin): the next frame may be
+// enqueued at once.  Released by the destructor; must not outlive its Renderer (restir_destroy frees the slots).
+class PresentedImage {
+public:
+    explicit PresentedImage(restir_image* image) : image_(image) {
+        check(restir_image_info(image_, &width_, &height_, &format_, &bytes_), "restir_image_info");
+    }
+    ~PresentedImage() { restir_image_release(image_); }
+    PresentedImage(PresentedImage&& o) noexcept
+        : image_(o.image_), width_(o.width_), height_(o.height_), format_(o.format_), bytes_(o.bytes_) { o.image_ = nullptr; }
+    PresentedImage(const PresentedImage&) = delete;
+    PresentedImage& operator=(const PresentedImage&) = delete;
+    PresentedImage& operator=(PresentedImage&&) = delete;
+    uint32_t width() const { return width_; }
+    uint32_t height() const { return height_; }
+    restir_image_format format() const { return restir_image_format(format_); }
+    size_t bytes() const { return bytes_; }
+    bool ready() const {   // never blocks
+        int r = 0;
+        check(restir_image_ready(image_, &r), "restir_image_ready");
+        return r != 0;
+    }
+    // blocks on this snapshot's copy only; bytes() bytes of pinned memory, valid while this object lives
+    const void* wait() const {
+        const void* p = nullptr;
+        check(restir_image_wait(image_, &p), "restir_image_wait");
+        return p;
+    }
+    // a BGRA8_BOTTOM_UP snapshot as the BMP file Screen::writeBitmapToFile writes: the header + the bytes
+    void writeBitmapToFile(const std::filesystem::path& filePath) const {
+        if (format_ != RESTIR_IMAGE_BGRA8_BOTTOM_UP) throw RestirError("writeBitmapToFile: the snapshot is not BGRA8_BOTTOM_UP");
+        const void* body = wait();
+        size_t n = 0;
+        check(restir_bmp_header(width_, height_, nullptr, 0, &n), "restir_bmp_header");
+        std::vector<uint8_t> header(n);
+        check(restir_bmp_header(width_, height_, header.data(), n, &n), "restir_bmp_header");
+        std::ofstream out(filePath, std::ios::binary);
+        out.write(reinterpret_cast<const char*>(header.data()), std::streamsize(n));
+        out.write(static_cast<const char*>(body), std::streamsize(bytes_));
+        if (!out) throw RestirError("writeBitmapToFile: cannot write " + filePath.string());
+    }
+
+private:
+    restir_image* image_;
+    uint32_t width_ = 0, height_ = 0, format_ = 0;
+    size_t bytes_ = 0;
+};
+
 // Owns a HIP device context: the EmbreeInterface + OpenMP loops of the reference become this object.
 class Renderer {
 public:
@@ -247,6 +295,23 @@ public:
         byBvh.assign(size_t(width) * height, 0);
         byList.assign(size_t(width) * height, 0);
         check(restir_debug_shadow_lists(ctx_, light, width, height, byBvh.data(), byList.data()), "restir_debug_shadow_lists");
+    }
+    // A snapshot of the last image (restir_image_begin): converted on the device, copied to pinned memory behind the
+    // frame that produced it; returns without synchronising, so the next frame may be rendered at once
+    PresentedImage present(restir_image_format format = RESTIR_IMAGE_RGBA8) {
+        restir_image* im = nullptr;
+        check(restir_image_begin(ctx_, uint32_t(format), &im), "restir_image_begin");
+        return PresentedImage(im);
+    }
+    // The last image as restir_rgb_to_rgba8's bytes, converted on the device: a snapshot, waited for and copied
+    std::vector<uint8_t> downloadRgba8() {
+        PresentedImage im = present(RESTIR_IMAGE_RGBA8);
+        const uint8_t* p = static_cast<const uint8_t*>(im.wait());
+        return std::vector<uint8_t>(p, p + im.bytes());
+    }
+    // Screen::writeBitmapToFile (screen.cpp:45-56) of the last image, without the floats leaving the device
+    void writeBitmapToFile(const std::filesystem::path& filePath) {
+        check(restir_write_image_bmp(ctx_, filePath.string().c_str()), "restir_write_image_bmp");
     }
     restir_ctx* handle() const { return ctx_; }
 

@@ -39,6 +39,11 @@ BUF_GBUF_UV = 11
 K_PRIMARY, K_RIS, K_TEMPORAL, K_SPATIAL, K_FINAL, K_PRIMARY_RIS, K_MIS, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7
 KERNEL_NAMES = ["primary", "ris", "temporal", "spatial", "final", "primary_ris", "mis"]
 
+# restir_image_format and the slots a context has (restir_image_begin)
+IMAGE_RGB32F, IMAGE_RGBA8, IMAGE_BGRA8_BOTTOM_UP = 0, 1, 2
+IMAGE_FORMATS = {"rgb32f": IMAGE_RGB32F, "rgba8": IMAGE_RGBA8, "bgra8_bottom_up": IMAGE_BGRA8_BOTTOM_UP}
+RESTIR_MAX_IMAGES_IN_FLIGHT = 4
+
 STATUS_NAMES = {0: "OK", 1: "INVALID", 2: "HIP", 3: "NO_DEVICE", 4: "STATE", 5: "UNSUPPORTED", 6: "COMM"}
 
 F3 = C.c_float * 3
@@ -227,6 +232,14 @@ SIGNATURES = {
                                         C.POINTER(C.c_uint32)]),
     "restir_synchronize": (C.c_int, [_P]),
     "restir_download_rgb": (C.c_int, [_P, C.POINTER(C.c_float), C.c_size_t]),
+    "restir_image_begin": (C.c_int, [_P, C.c_uint32, C.POINTER(_P)]),
+    "restir_image_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_size_t)]),
+    "restir_image_ready": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "restir_image_wait": (C.c_int, [_P, C.POINTER(_P)]),
+    "restir_image_release": (None, [_P]),
+    "restir_download_rgba8": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_size_t]),
+    "restir_write_image_bmp": (C.c_int, [_P, C.c_char_p]),
     "restir_stage_configure": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "restir_stage_upload": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     "restir_stage_download": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
@@ -264,6 +277,7 @@ SIGNATURES = {
     "restir_rgb_to_rgba8": (C.c_int, [_P, C.c_size_t, _P]),
     "restir_encode_bmp": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "restir_write_bmp": (C.c_int, [C.c_char_p, _P, C.c_uint32, C.c_uint32]),
+    "restir_bmp_header": (C.c_int, [C.c_uint32, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "restir_features_json": (C.c_int, [C.POINTER(Features), C.POINTER(FeaturesRecordExtra), C.c_char_p, C.c_size_t,
                                        C.POINTER(C.c_size_t)]),
     "restir_halo_end": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_float)]),

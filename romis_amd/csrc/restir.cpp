@@ -29,6 +29,7 @@
 #include "device_math.h"
 #include "launch.h"
 #include "refit.h"
+#include "present.h"
 #include "reproject.h"
 #include "restir_types.h"
 #include "shadow_lists.h"
@@ -206,10 +207,29 @@ void used_prev(const restir_frame* prev, hipStream_t s, const FramePool* own) {
 }
 }  // namespace
 
+// One snapshot slot of a context (restir_image_begin): the staging buffer the conversion writes and the copy reads, the
+// pinned host buffer the copy lands in, and the two events -- `converted` on the context's stream, `landed` on its copy
+// stream.  Buffers and events are created on first need and live until restir_destroy.
+struct restir_image {
+    restir_ctx* ctx = nullptr;
+    bool in_use = false;
+    uint32_t width = 0, height = 0, format = 0;
+    size_t bytes = 0;                  // of this snapshot (<= stage.bytes, host_bytes)
+    DevBuf stage;
+    void* host = nullptr;              // hipHostMalloc
+    size_t host_bytes = 0;
+    hipEvent_t converted = nullptr, landed = nullptr;
+};
+
 struct restir_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::mutex mu;
+
+    // presenting (restir_image_begin): the slots, and the stream their device-to-host copies run on -- created by the
+    // first snapshot, so a program that takes none opens no second queue
+    restir_image images[RESTIR_MAX_IMAGES_IN_FLIGHT];
+    hipStream_t copy_stream = nullptr;
 
     // scene
     DevBuf nodes, tri_v0, tri_e1, tri_e2, tri_n0, tri_n1, tri_n2, materials, lights, light_c2, light_c4, light_col, tex_texels,
@@ -793,6 +813,7 @@ restir_status restir_create(int device, restir_ctx** out) {
 }
 
 static void release_rccl(restir_ctx* c);   // (halo section)
+static void release_images(restir_ctx* c);   // (presenting section)
 
 // Free the shadow-list records (restir_ctx::slists): where nothing can read them again -- another scene, final.lists
 // off, the context's end.  (hipFree waits for the kernels that read them.)
@@ -819,6 +840,7 @@ void restir_destroy(restir_ctx* c) {
         for (hipEvent_t ev : c->free_events) (void)hipEventDestroy(ev);
         c->pool->close();   // frames still alive free their records themselves on release
         release_rccl(c);
+        release_images(c);
         (void)hipStreamDestroy(c->stream);
     }
     delete c;
@@ -2226,6 +2248,178 @@ restir_status restir_download_rgb(restir_ctx* c, float* out_rgb, size_t count) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyAsync(out_rgb, c->rgb.p, need * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return RESTIR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// presenting a frame (include/restir_c.h "presenting a frame")
+static void release_images(restir_ctx* c) {
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);   // outstanding copies land before their buffers go
+    for (restir_image& im : c->images) {
+        im.stage.release();
+        if (im.host) (void)hipHostFree(im.host);
+        if (im.converted) (void)hipEventDestroy(im.converted);
+        if (im.landed) (void)hipEventDestroy(im.landed);
+        im = restir_image();
+    }
+    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    c->copy_stream = nullptr;
+}
+
+// the conversion (or copy) into the slot's staging buffer on the context's stream, the copy to its pinned buffer on the
+// copy stream behind it
+static restir_status image_enqueue(restir_ctx* c, restir_image* im, uint32_t format, size_t px, size_t bytes) {
+    if (format == RESTIR_IMAGE_RGB32F) {
+        HIP_TRY(hipMemcpyAsync(im->stage.p, c->rgb.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        PresentDev p{};
+        p.rgb = c->rgb.as<float>();
+        p.out = im->stage.as<uint32_t>();
+        p.bgr_flip = format == RESTIR_IMAGE_BGRA8_BOTTOM_UP;
+        p.row_px = p.bgr_flip ? c->rgb_w : px;
+        p.rows = p.bgr_flip ? c->rgb_h : 1u;
+        HIP_TRY(launch_present(p, c->stream));
+    }
+    HIP_TRY(hipEventRecord(im->converted, c->stream));
+    HIP_TRY(hipStreamWaitEvent(c->copy_stream, im->converted, 0));   // the one cross-stream dependency
+    HIP_TRY(hipMemcpyAsync(im->host, im->stage.p, bytes, hipMemcpyDeviceToHost, c->copy_stream));
+    HIP_TRY(hipEventRecord(im->landed, c->copy_stream));
+    return RESTIR_OK;
+}
+
+// the caller holds c->mu and has set the device
+static restir_status image_begin_locked(restir_ctx* c, uint32_t format, restir_image** out) {
+    if (format > (uint32_t)RESTIR_IMAGE_BGRA8_BOTTOM_UP) return fail(RESTIR_ERR_INVALID, "unknown image format %u", format);
+    const size_t px = (size_t)c->rgb_w * c->rgb_h;
+    if (px == 0) return fail(RESTIR_ERR_STATE, "nothing rendered yet");
+    restir_image* im = nullptr;
+    for (restir_image& s : c->images)
+        if (!s.in_use) { im = &s; break; }
+    if (!im)
+        return fail(RESTIR_ERR_STATE, "%u snapshots are unreleased (RESTIR_MAX_IMAGES_IN_FLIGHT): restir_image_release one first",
+                    RESTIR_MAX_IMAGES_IN_FLIGHT);
+    const size_t bytes = px * (format == RESTIR_IMAGE_RGB32F ? 12u : 4u);
+    if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    if (!im->converted) HIP_TRY(hipEventCreateWithFlags(&im->converted, hipEventDisableTiming));
+    if (!im->landed) HIP_TRY(hipEventCreateWithFlags(&im->landed, hipEventDisableTiming));
+    // a free slot's last copy has landed (restir_image_release waited for it): its buffers may be replaced
+    ST_TRY(im->stage.ensure(bytes));
+    if (im->host_bytes < bytes) {
+        if (im->host) (void)hipHostFree(im->host);
+        im->host = nullptr;
+        im->host_bytes = 0;
+        hipError_t e = hipHostMalloc(&im->host, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { im->host = nullptr; return fail(RESTIR_ERR_HIP, "hipHostMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
+        im->host_bytes = bytes;
+    }
+    const restir_status st = image_enqueue(c, im, format, px, bytes);
+    if (st != RESTIR_OK) {
+        // part of the work may be enqueued: the slot stays free, so nothing may still write its buffers when it is taken
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipStreamSynchronize(c->copy_stream);
+        return st;
+    }
+    im->ctx = c;
+    im->in_use = true;
+    im->width = c->rgb_w;
+    im->height = c->rgb_h;
+    im->format = format;
+    im->bytes = bytes;
+    *out = im;
+    return RESTIR_OK;
+}
+
+static void image_release_locked(restir_image* im) {
+    if (!im->in_use) return;
+    (void)hipEventSynchronize(im->landed);   // the slot's buffers are re-used only after its copy
+    im->in_use = false;
+}
+
+restir_status restir_image_begin(restir_ctx* c, uint32_t format, restir_image** out) {
+    if (!c || !out) return fail(RESTIR_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    return image_begin_locked(c, format, out);
+}
+
+restir_status restir_image_info(const restir_image* im, uint32_t* width, uint32_t* height, uint32_t* format, size_t* bytes) {
+    if (!im || !im->ctx) return fail(RESTIR_ERR_INVALID, "image is NULL");
+    std::lock_guard<std::mutex> lk(im->ctx->mu);
+    if (!im->in_use) return fail(RESTIR_ERR_INVALID, "the image has been released");
+    if (width) *width = im->width;
+    if (height) *height = im->height;
+    if (format) *format = im->format;
+    if (bytes) *bytes = im->bytes;
+    return RESTIR_OK;
+}
+
+restir_status restir_image_ready(restir_image* im, int* ready) {
+    if (!im || !ready || !im->ctx) return fail(RESTIR_ERR_INVALID, "null argument");
+    *ready = 0;
+    std::lock_guard<std::mutex> lk(im->ctx->mu);
+    if (!im->in_use) return fail(RESTIR_ERR_INVALID, "the image has been released");
+    HIP_TRY(hipSetDevice(im->ctx->device));
+    const hipError_t e = hipEventQuery(im->landed);
+    if (e == hipSuccess) { *ready = 1; return RESTIR_OK; }
+    if (e == hipErrorNotReady) { (void)hipGetLastError(); return RESTIR_OK; }
+    return fail(RESTIR_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(e));
+}
+
+restir_status restir_image_wait(restir_image* im, const void** data) {
+    if (!im || !data || !im->ctx) return fail(RESTIR_ERR_INVALID, "null argument");
+    *data = nullptr;
+    hipEvent_t landed;
+    const void* host;
+    {
+        std::lock_guard<std::mutex> lk(im->ctx->mu);
+        if (!im->in_use) return fail(RESTIR_ERR_INVALID, "the image has been released");
+        HIP_TRY(hipSetDevice(im->ctx->device));
+        landed = im->landed;
+        host = im->host;
+    }
+    // outside the mutex: another thread may enqueue the next frame while this one waits for its copy, and only for it
+    HIP_TRY(hipEventSynchronize(landed));
+    *data = host;
+    return RESTIR_OK;
+}
+
+void restir_image_release(restir_image* im) {
+    if (!im || !im->ctx) return;
+    std::lock_guard<std::mutex> lk(im->ctx->mu);
+    (void)hipSetDevice(im->ctx->device);
+    image_release_locked(im);
+}
+
+restir_status restir_download_rgba8(restir_ctx* c, uint8_t* out_rgba, size_t pixels) {
+    if (!c || !out_rgba) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t need = (size_t)c->rgb_w * c->rgb_h;
+    if (need == 0) return fail(RESTIR_ERR_STATE, "nothing rendered yet");
+    if (pixels < need) return fail(RESTIR_ERR_INVALID, "buffer holds %zu pixels, need %zu", pixels, need);
+    HIP_TRY(hipSetDevice(c->device));
+    restir_image* im = nullptr;
+    ST_TRY(image_begin_locked(c, RESTIR_IMAGE_RGBA8, &im));
+    const hipError_t e = hipEventSynchronize(im->landed);
+    if (e == hipSuccess) std::memcpy(out_rgba, im->host, im->bytes);
+    image_release_locked(im);
+    if (e != hipSuccess) return fail(RESTIR_ERR_HIP, "hipEventSynchronize: %s", hipGetErrorString(e));
+    return RESTIR_OK;
+}
+
+restir_status restir_write_image_bmp(restir_ctx* c, const char* path) {
+    if (!c || !path) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((size_t)c->rgb_w * c->rgb_h == 0) return fail(RESTIR_ERR_STATE, "nothing rendered yet");
+    HIP_TRY(hipSetDevice(c->device));
+    restir_image* im = nullptr;
+    ST_TRY(image_begin_locked(c, RESTIR_IMAGE_BGRA8_BOTTOM_UP, &im));
+    const hipError_t e = hipEventSynchronize(im->landed);
+    // stbi_write_bmp's header (screen.cpp bmp_header, shared with restir_encode_bmp) around the snapshot's bytes
+    const bool ok = e == hipSuccess && write_bmp_words(path, im->width, im->height, static_cast<const uint32_t*>(im->host));
+    image_release_locked(im);
+    if (e != hipSuccess) return fail(RESTIR_ERR_HIP, "hipEventSynchronize: %s", hipGetErrorString(e));
+    if (!ok) return fail(RESTIR_ERR_INVALID, "cannot write %s", path);
     return RESTIR_OK;
 }
 

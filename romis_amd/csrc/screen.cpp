@@ -226,6 +226,18 @@ restir_status restir_encode_bmp(const float* rgb, uint32_t width, uint32_t heigh
     return RESTIR_OK;
 }
 
+restir_status restir_bmp_header(uint32_t width, uint32_t height, uint8_t* out, size_t capacity, size_t* length) {
+    const size_t bytes = 14 + 108;
+    if (length) *length = bytes;
+    if (!out) return RESTIR_OK;   // size query
+    if (capacity < bytes || bytes + (size_t)width * height * 4 > 0xFFFFFFFFull) return RESTIR_ERR_INVALID;
+    std::vector<uint8_t> o;
+    o.reserve(bytes);
+    bmp_header(o, width, height);
+    std::memcpy(out, o.data(), bytes);
+    return RESTIR_OK;
+}
+
 restir_status restir_write_bmp(const char* path, const float* rgb, uint32_t width, uint32_t height) {
     if (!path) return RESTIR_ERR_INVALID;
     size_t n = 0;

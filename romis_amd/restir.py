@@ -51,6 +51,55 @@ class ReservoirGrid:
         return pos.reshape(shp + (3,)), col.reshape(shp + (3,)), w.reshape(shp), m.reshape(shp)
 
 
+class PresentedImage:
+    """A snapshot of a Renderer's last image on its way to pinned host memory (restir_image_begin): the next frame may
+    be enqueued at once.  ready() never blocks; wait() blocks on this snapshot's copy only and returns a numpy view of
+    the pinned bytes -- (H, W, 4) uint8 for "rgba8" / "bgra8_bottom_up", (H, W, 3) float32 for "rgb32f" -- valid until
+    release().  A context manager (release on exit); keeps its Renderer alive.  Closing the Renderer invalidates it."""
+
+    def __init__(self, renderer: "Renderer", handle):
+        self._renderer = renderer
+        self._lib = renderer.lib
+        self.handle = handle
+        w, h, fmt, n = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_size_t()
+        check(self._lib, self._lib.restir_image_info(handle, C.byref(w), C.byref(h), C.byref(fmt), C.byref(n)),
+              "restir_image_info")
+        self.width, self.height, self.format, self.nbytes = w.value, h.value, fmt.value, n.value
+
+    def _live(self):
+        if not self.handle or not self._renderer.ctx:
+            raise RestirError("the presented image has been released (or its Renderer closed)")
+        return self.handle
+
+    def ready(self) -> bool:
+        r = C.c_int()
+        check(self._lib, self._lib.restir_image_ready(self._live(), C.byref(r)), "restir_image_ready")
+        return bool(r.value)
+
+    def wait(self) -> np.ndarray:
+        p = C.c_void_p()
+        check(self._lib, self._lib.restir_image_wait(self._live(), C.byref(p)), "restir_image_wait")
+        buf = (C.c_uint8 * self.nbytes).from_address(p.value)
+        if self.format == _abi.IMAGE_RGB32F:
+            return np.frombuffer(buf, np.float32).reshape(self.height, self.width, 3)
+        return np.frombuffer(buf, np.uint8).reshape(self.height, self.width, 4)
+
+    def release(self) -> None:
+        if getattr(self, "handle", None):
+            if self._renderer.ctx:   # a closed Renderer freed the slots itself
+                self._lib.restir_image_release(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+
+    def __del__(self):
+        self.release()
+
+
 class Renderer:
     def __init__(self, device: int = 0):
         self.lib = _abi.load_library()
@@ -181,6 +230,31 @@ class Renderer:
         check(self.lib, self.lib.restir_download_rgb(self.ctx, rgb.ctypes.data_as(C.POINTER(C.c_float)), rgb.size),
               "restir_download_rgb")
         return rgb
+
+    # ---- presenting a frame (include/restir_c.h "presenting a frame") ---------------------------------
+    def present(self, format: str | int = "rgba8") -> PresentedImage:
+        """restir_image_begin: a snapshot of the last image as "rgba8", "bgra8_bottom_up" or "rgb32f", converted on the
+        device and copied to pinned memory behind the frame that produced it; returns without synchronising."""
+        fmt = _abi.IMAGE_FORMATS[format] if isinstance(format, str) else int(format)
+        h = C.c_void_p()
+        check(self.lib, self.lib.restir_image_begin(self.ctx, fmt, C.byref(h)), "restir_image_begin")
+        return PresentedImage(self, h)
+
+    def download_rgba8(self, width: int | None = None, height: int | None = None) -> np.ndarray:
+        """The last image as (H, W, 4) uint8 -- restir_rgb_to_rgba8's bytes, converted on the device.  With the image's
+        size (as download_rgb takes it) this is restir_download_rgba8; without, a snapshot that tells its own size,
+        waited for and copied."""
+        if width is None or height is None:
+            with self.present("rgba8") as im:
+                return im.wait().copy()
+        out = np.zeros((height, width, 4), np.uint8)
+        check(self.lib, self.lib.restir_download_rgba8(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint8)), width * height),
+              "restir_download_rgba8")
+        return out
+
+    def write_bmp(self, path) -> None:
+        """restir_write_image_bmp: the last image as the BMP file Screen::writeBitmapToFile writes."""
+        check(self.lib, self.lib.restir_write_image_bmp(self.ctx, os.fsencode(path)), "restir_write_image_bmp")
 
     # ---- halo-mode frames (include/restir_c.h "halo-mode frames") -------------------------------------
     def halo_begin(self, prev, camera, width, height, features, tiles, rank, layout=None):
