@@ -659,10 +659,23 @@ restir_status restir_background_pixels(restir_ctx* ctx, uint64_t* background, ui
  * their primary rays; restir_timings counts both kinds under RESTIR_K_PRIMARY_RIS. */
 restir_status restir_gbuf_reuses(restir_ctx* ctx, uint64_t* out_frames);
 
-/* restir_render frames of this context so far whose fused last pass traced its shadow rays over the view's candidate
- * triangle lists (tuning "final.lists") instead of the BVH: from the second consecutive frame that reuses the kept
- * G-buffer with the light list unchanged. */
+/* restir_render frames of this context so far whose fused last pass took the view's candidate triangle lists (tuning
+ * "final.lists") instead of the BVH: from the second consecutive frame that reuses the kept G-buffer with the light list
+ * unchanged.  A frame that read its rays' answers from the visibility bits built over those lists (below) counts too. */
 restir_status restir_shadow_list_frames(restir_ctx* ctx, uint64_t* out_frames);
+
+/* ... of which those whose last pass read every shadow ray's answer from the view's visibility bits (tuning "final.vis",
+ * "final.vis_after"): one bit per (pixel, point light), the lists' rays traced once for a view that stands still.  The
+ * bits live exactly as long as the lists they were built over.  restir_shadow_vis_builds: how often they were built. */
+restir_status restir_shadow_vis_frames(restir_ctx* ctx, uint64_t* out_frames);
+restir_status restir_shadow_vis_builds(restir_ctx* ctx, uint64_t* out_builds);
+
+/* Test hook for those bits, as the last frame left them (RESTIR_ERR_STATE when there are none for the kept G-buffer):
+ * for every pixel of that frame's owned rectangle, width x height (RESTIR_ERR_INVALID when the frame's was another size;
+ * row-major from its first row, one byte each), the stored answer for point light `light` (< num_lights, else
+ * RESTIR_ERR_INVALID: the zero sample has no bits), 1 visible / 0 occluded; 0xFF where none is held -- a pixel of a
+ * background tile or one that shows no surface. */
+restir_status restir_debug_shadow_vis(restir_ctx* ctx, uint32_t light, uint32_t width, uint32_t height, uint8_t* out_bits);
 
 /* Test hook for those lists, as the last frame left them (RESTIR_ERR_STATE when there are none for the kept G-buffer):
  * for every pixel of that frame's owned rectangle, width x height (RESTIR_ERR_INVALID when the frame's was another

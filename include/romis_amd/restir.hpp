@@ -296,6 +296,23 @@ public:
         byList.assign(size_t(width) * height, 0);
         check(restir_debug_shadow_lists(ctx_, light, width, height, byBvh.data(), byList.data()), "restir_debug_shadow_lists");
     }
+    // Frames so far whose last pass read its shadow rays' answers from the view's visibility bits, and the builds of
+    // those bits (restir_shadow_vis_frames, restir_shadow_vis_builds)
+    uint64_t shadowVisFrames() const {
+        uint64_t n = 0;
+        check(restir_shadow_vis_frames(ctx_, &n), "restir_shadow_vis_frames");
+        return n;
+    }
+    uint64_t shadowVisBuilds() const {
+        uint64_t n = 0;
+        check(restir_shadow_vis_builds(ctx_, &n), "restir_shadow_vis_builds");
+        return n;
+    }
+    // Test hook (restir_debug_shadow_vis): width x height bytes, the last frame's owned rectangle (another size is refused)
+    void debugShadowVis(uint32_t light, std::vector<uint8_t>& bits, uint32_t width, uint32_t height) const {
+        bits.assign(size_t(width) * height, 0);
+        check(restir_debug_shadow_vis(ctx_, light, width, height, bits.data()), "restir_debug_shadow_vis");
+    }
     // A snapshot of the last image (restir_image_begin): converted on the device, copied to pinned memory behind the
     // frame that produced it; returns without synchronising, so the next frame may be rendered at once
     PresentedImage present(restir_image_format format = RESTIR_IMAGE_RGBA8) {

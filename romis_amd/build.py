@@ -45,12 +45,13 @@ SOURCES = [("kernels.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS)] + ABI_UNITS +
     ("refit.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("reproject.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("shadow_lists.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
+    ("shadow_vis.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("present.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("bvh.cpp", ["-x", "c++"]),
     ("screen.cpp", ["-x", "c++"]),
 ]
 HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
-           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "abi_error.h", "layout.h", "halo_segs.h", "present.h"]
+           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "shadow_vis.h", "abi_error.h", "layout.h", "halo_segs.h", "present.h"]
 
 
 def source_hash() -> str:
@@ -104,6 +105,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_bvh_check(force)
     build_refit_check(force)
     build_shadow_lists_check(force)
+    build_shadow_vis_layout(force)
     if verbose:
         print(LIB)
     return LIB
@@ -160,6 +162,18 @@ def build_shadow_lists_check(force: bool = False) -> str:
     if os.path.exists(src) and (force or _stale(tool, deps)):
         os.makedirs(os.path.dirname(tool), exist_ok=True)
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off", f"-I{CSRC}", src, "-o", tool])
+    return tool
+
+
+def build_shadow_vis_layout(force: bool = False) -> str:
+    """tools/shadow_vis_layout: tests/cpp/shadow_vis_layout.cpp over csrc/shadow_vis.h with the host compiler -- the
+    plane's indices as the header computes them (tests/test_shadow_vis_layout.py); no device code."""
+    tool = os.path.join(OUT, "tools", "shadow_vis_layout")
+    src = os.path.join(ROOT, "tests", "cpp", "shadow_vis_layout.cpp")
+    deps = [src, os.path.join(CSRC, "shadow_vis.h"), __file__]
+    if os.path.exists(src) and (force or _stale(tool, deps)):
+        os.makedirs(os.path.dirname(tool), exist_ok=True)
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", tool])
     return tool
 
 

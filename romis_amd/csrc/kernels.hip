@@ -15,6 +15,7 @@
 // ray kernels stage once per (persistent) workgroup into LDS; the light table is staged into LDS for RIS.
 #include "kernels_common.h"
 #include "ris_members.h"
+#include "shadow_vis.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // genPrimaryRayHits for pixel (x, y) at view index p: writes and returns the G-buffer records (n_t, p_mat)
@@ -1501,6 +1502,10 @@ __device__ __forceinline__ void fin_shade_block_lists(const SceneDev& s, const R
                                                       const GlTabs& tb, bool live, bool own_bg, int tx0, int ty0, uint32_t wave,
                                                       const Px& px, bool pm_miss, v3 pos, v3 col, float W, uint32_t li,
                                                       const uint4* __restrict__ sl);
+__device__ __forceinline__ void fin_shade_block_vis(const SceneDev& s, const Region& rg, const FeaturesDev& f, const FinalOut& fin,
+                                                    const GlTabs& tb, bool live, bool own_bg, int tx0, int ty0, uint32_t wave,
+                                                    const Px& px, bool pm_miss, v3 pos, v3 col, float W, uint32_t li,
+                                                    const uint4* __restrict__ sl, const uint32_t* __restrict__ sv);
 
 // HG (the default 32 x 16 form since round 6): the handles are gathered from global memory (the own pixel's coalesced,
 // an accepted neighbour's one 4 + 4 B gather) instead of staged in LDS: the block's LDS is the n_t window and the light
@@ -1513,16 +1518,19 @@ __device__ __forceinline__ void fin_shade_block_lists(const SceneDev& s, const R
 // their bytes hold the BVH, the binned rays and the histogram (one barrier between the two uses).
 // LISTS (k_spatial1hg_t2_final_lists): FIN with the ray phase of fin_shade_block_lists -- each lane's ray over the
 // shadow list of (its tile, its light), sl -- which has no barrier, no histogram and no staged BVH.
-template <bool DBG, uint32_t TH = 1, bool HG = false, bool FIN = false, bool LISTS = false>
+// VIS (k_spatial1hg_t2_final_vis): LISTS whose rays read their answer from the view's visibility bits, sv (shadow_vis.h).
+template <bool DBG, uint32_t TH = 1, bool HG = false, bool FIN = false, bool LISTS = false, bool VIS = false>
 __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key,
                                                v3 origin, const float4* __restrict__ n_t, const float4* __restrict__ p_mat,
                                                HandlesIn hi, float4* __restrict__ oa, float4* __restrict__ ob,
                                                float2* __restrict__ odbg, const float* __restrict__ rp_in,
                                                float* __restrict__ rp_out, float* __restrict__ how,
                                                uint32_t* __restrict__ hom, MissTiles mt, uint32_t odead,
-                                               FinalOut fin = FinalOut{nullptr, 0u}, const uint4* __restrict__ sl = nullptr) {
+                                               FinalOut fin = FinalOut{nullptr, 0u}, const uint4* __restrict__ sl = nullptr,
+                                               const uint32_t* sv = nullptr) {
     static_assert(!FIN || (!DBG && TH == 2u && HG), "the fused form is the 32 x 16 gather pass without a debug plane");
     static_assert(!LISTS || FIN, "the shadow lists serve the fused form's rays");
+    static_assert(!VIS || LISTS, "the visibility bits hold the lists' answers");
     float4* const l_nt = g_lds;
     float* const l_w = reinterpret_cast<float*>(g_lds + apron_max(TH));
     uint32_t* const l_m = reinterpret_cast<uint32_t*>(l_w + apron_max(TH));
@@ -1653,7 +1661,8 @@ __device__ __forceinline__ void spatial1h_body(const SceneDev& s, const Region& 
         if constexpr (LISTS) rli = cmb.li;
     }
 shade:
-    if constexpr (LISTS) fin_shade_block_lists(s, rg, f, fin, tb, live, own_bg, tx0, ty0, wave, rpx, pm_miss, rpos, rcol, rW, rli, sl);
+    if constexpr (VIS) fin_shade_block_vis(s, rg, f, fin, tb, live, own_bg, tx0, ty0, wave, rpx, pm_miss, rpos, rcol, rW, rli, sl, sv);
+    else if constexpr (LISTS) fin_shade_block_lists(s, rg, f, fin, tb, live, own_bg, tx0, ty0, wave, rpx, pm_miss, rpos, rcol, rW, rli, sl);
     else if constexpr (FIN) fin_shade_block(s, rg, f, fin, tb, live, own_bg, tx0, ty0, wave, rpx, pm_miss, rpos, rcol, rW);
 }
 
@@ -2606,6 +2615,11 @@ __device__ __forceinline__ void fin_shade_block_lists(const SceneDev& s, const R
 #endif
     if (!live) return;
     v3 c = sc;
+#ifdef ROMIS_LISTS_CEILING
+    // measurement stand-in (never a default; wrong images): every needed ray counts as visible, no record is read --
+    // the bound on what any cheaper answer to the lists' rays can return (profiles/shadow_vis/ceiling.json)
+    need = false;
+#endif
     if (need && !visible_listed(bvh, s.num_tris, rec[li], px.mat == s.num_materials - 1u, px.P, pos))
         c = mk(0.0f, 0.0f, 0.0f);
     v3 color = vadd(mk(0.0f, 0.0f, 0.0f), vscale(c, W));
@@ -2617,7 +2631,56 @@ __device__ __forceinline__ void fin_shade_block_lists(const SceneDev& s, const R
     o[0] = color.x; o[1] = color.y; o[2] = color.z;
 }
 
-// (k_spatial1hg_t2_final_lists itself is the last kernel of this file: the code of the kernels above stays where it was)
+// fin_shade_block_lists with the rays' answers read from the view's visibility bits (shadow_vis.h; restir_render builds
+// them over the lists once the view has stood still a little longer): the same shade, need test, miss path, x W, / 1,
+// tone map and store.  A needing lane whose light is one of the table's and whose pixel does not hold the miss material
+// reads the answer k_shadow_vis stored for the very call fin_shade_block_lists makes -- record 512 tile + t, the word
+// and bit of li: one 4-byte load, a wave's 64 records one contiguous run.  Any other needing lane (the zero sample behind
+// a NaN shade, a miss-material pixel that shades all the same) makes that call itself: dead code for ordinary scenes,
+// kept so that every case stays exact.
+__device__ __forceinline__ void fin_shade_block_vis(const SceneDev& s, const Region& rg, const FeaturesDev& f, const FinalOut& fin,
+                                                    const GlTabs& tb, bool live, bool own_bg, int tx0, int ty0, uint32_t wave,
+                                                    const Px& px, bool pm_miss, v3 pos, v3 col, float W, uint32_t li,
+                                                    const uint4* __restrict__ sl, const uint32_t* __restrict__ sv) {
+    const uint32_t ntx = (rg.rw + kTileW - 1) / kTileW;
+    const uint32_t tile = (((uint32_t)ty0 - rg.ry0) / (2u * kTileH)) * ntx + ((uint32_t)tx0 - rg.rx0) / kTileW;
+    const uint32_t t = (wave << 6) | __lane_id();
+    v3 sc = mk(0.0f, 0.0f, 0.0f);
+    bool need = false;
+    if (live && !own_bg) {
+        const bool miss = pm_miss && __builtin_isfinite(W) &&
+                          !__builtin_isnan((pos.x - px.P.x) + (pos.y - px.P.y) + (pos.z - px.P.z));
+        if (!miss) {
+            sc = shade(s, f, px, pos, col, tb);
+            need = sc.x != 0.0f || sc.y != 0.0f || sc.z != 0.0f;
+        } else {
+            W = 0.0f;
+        }
+    } else {
+        W = 0.0f;
+    }
+    if (!live) return;
+    v3 c = sc;
+    if (need) {
+        bool vis;
+        if (li < s.num_lights && px.mat != s.num_materials - 1u)
+            vis = (sv[sv_index(sv_slot_of_thread(tile, t), sv_words(s.num_lights), sv_word_of(li))] & sv_bit(li)) != 0u;
+        else
+            vis = visible_listed(global_bvh(s), s.num_tris, sl[(size_t)tile * sl_stride(s.num_lights) + li],
+                                 px.mat == s.num_materials - 1u, px.P, pos);
+        if (!vis) c = mk(0.0f, 0.0f, 0.0f);
+    }
+    v3 color = vadd(mk(0.0f, 0.0f, 0.0f), vscale(c, W));
+    color = tone_map_rgb(f, vdivs(color, 1.0f), tb);
+    const uint32_t w = t >> 6, l = t & 63u;   // spatial1h_body's pixel of the 32 x 16 tile
+    const uint32_t x = (uint32_t)tx0 + (w & 3u) * 8u + (l & 7u), y = (uint32_t)ty0 + (w >> 2) * 8u + (l >> 3);
+    const uint32_t row = rg.rh - 1u - (y - rg.ry0);
+    float* o = fin.rgb + 3 * ((size_t)row * rg.rw + (x - rg.rx0));
+    o[0] = color.x; o[1] = color.y; o[2] = color.z;
+}
+
+// (k_spatial1hg_t2_final_lists and _vis themselves are the last kernels of this file: the code of the kernels above stays
+// where it was)
 
 #define ROMIS_FINAL_KERNEL(NT, LDS, NAME)                                                                            \
     extern "C" __global__ __launch_bounds__(256) void NAME(SceneDev s, Region rg, FeaturesDev f, float ox, float oy,     \
@@ -2712,6 +2775,15 @@ k_spatial1hg_t2_final_lists(SceneDev s, Region rg, FeaturesDev f, uint32_t key, 
                             uint32_t* hom, MissTiles mt, uint32_t odead, FinalOut fin, const uint4* sl) {
     spatial1h_body<false, 2, true, true, true>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, hi, oa, ob, nullptr, rp_in, nullptr, how,
                                                hom, mt, odead, fin, sl);
+}
+
+// k_spatial1hg_t2_final_lists with the rays' answers read from the view's visibility bits (fin_shade_block_vis)
+extern "C" __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(ROMIS_SPATIAL1HG_FINAL_WPE))) void
+k_spatial1hg_t2_final_vis(SceneDev s, Region rg, FeaturesDev f, uint32_t key, float ox, float oy, float oz, const float4* n_t,
+                          const float4* p_mat, HandlesIn hi, float4* oa, float4* ob, const float* rp_in, float* how,
+                          uint32_t* hom, MissTiles mt, uint32_t odead, FinalOut fin, const uint4* sl, const uint32_t* sv) {
+    spatial1h_body<false, 2, true, true, true, true>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, hi, oa, ob, nullptr, rp_in, nullptr,
+                                                     how, hom, mt, odead, fin, sl, sv);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2872,6 +2944,12 @@ hipError_t launch_spatial(const Route& r, const SceneDev& s, const Region& rg0, 
         break;
     case Kernel::kSpatial1hgFinal:
         assert(b.rgb);
+        if (r.bits) {
+            assert(r.lists && b.shadow_lists && b.shadow_vis);
+            ROMIS_LAUNCH(k_spatial1hg_t2_final_vis, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], b.n_t, b.p_mat,
+                         hi, b.oa, b.ob, rp_in, how, hom, mt, r.res_dead, FinalOut{b.rgb, r.miss}, b.shadow_lists, b.shadow_vis);
+            break;
+        }
         if (r.lists) {
             assert(b.shadow_lists);
             ROMIS_LAUNCH(k_spatial1hg_t2_final_lists, grid, block, r.lds, stream, s, rg, f, b.key, o[0], o[1], o[2], b.n_t,

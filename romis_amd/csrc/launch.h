@@ -31,6 +31,7 @@ struct LaunchBufs {
     Handles hout{nullptr, nullptr};    // the output's
     float* rgb = nullptr;              // final shading's image (the owned rect)
     const uint4* shadow_lists = nullptr;   // the view's shadow-list records (shadow_lists.h), for a route with `lists`
+    const uint32_t* shadow_vis = nullptr;  // the view's visibility bits (shadow_vis.h), for a route with `bits`
     TemporalIn tin{};                  // primary + RIS + temporal: the predecessor grid
 };
 

@@ -33,6 +33,7 @@
 #include "reproject.h"
 #include "restir_types.h"
 #include "shadow_lists.h"
+#include "shadow_vis.h"
 
 namespace romis {
 bool write_bmp_words(const char* path, uint32_t width, uint32_t height, const uint32_t* words);   // screen.cpp
@@ -303,7 +304,17 @@ struct restir_ctx {
     ShadowListsDev slists_dev{};
     uint32_t gbuf_streak = 0;
     uint64_t gbuf_streak_lights = 0;                // scene_gen of the frames the streak counts
-    uint64_t shadow_list_frames = 0;                // frames whose last pass traced over the lists (restir_shadow_list_frames)
+    uint64_t shadow_list_frames = 0;                // frames whose last pass took the lists route, its rays traced over the lists
+                                                    // or answered from the bits below (restir_shadow_list_frames)
+    uint64_t slists_builds = 0;                     // k_shadow_lists launches: names one build of the lists
+    // The visibility bits of the lists' rays (shadow_vis.h, tuning "final.vis"): valid for the one build of the lists
+    // they asked (`svis_lists_build`), hence for exactly what leaves those lists valid -- the same key, rect and flags.
+    DevBuf svis;
+    bool svis_valid = false;
+    uint64_t svis_lists_build = 0;
+    ShadowVisDev svis_dev{};
+    uint64_t shadow_vis_frames = 0;                 // frames whose last pass read the bits (restir_shadow_vis_frames)
+    uint64_t shadow_vis_builds = 0;                 // k_shadow_vis launches (restir_shadow_vis_builds)
     int cur = 0;
     uint32_t rgb_w = 0, rgb_h = 0;
 
@@ -816,10 +827,16 @@ static void release_rccl(restir_ctx* c);   // (halo section)
 static void release_images(restir_ctx* c);   // (presenting section)
 
 // Free the shadow-list records (restir_ctx::slists): where nothing can read them again -- another scene, final.lists
-// off, the context's end.  (hipFree waits for the kernels that read them.)
+// off, the context's end.  (hipFree waits for the kernels that read them.)  The visibility bits hold those records'
+// answers and go with them.
+static void drop_shadow_vis(restir_ctx* c) {
+    c->svis_valid = false;
+    c->svis.release();
+}
 static void drop_shadow_lists(restir_ctx* c) {
     c->slists_key.valid = false;
     c->slists.release();
+    drop_shadow_vis(c);
 }
 
 void restir_destroy(restir_ctx* c) {
@@ -1658,11 +1675,29 @@ static restir_status ensure_shadow_lists(restir_ctx* c, const Route& r, const Sc
     ST_TRY(c->slists.ensure(bytes));
     d.rec = c->slists.as<uint4>();
     HIP_TRY(launch_shadow_lists(d, st));
+    c->slists_builds++;
     c->slists_dev = d;
     c->slists_key.valid = true;
     c->slists_key.gbuf_epoch = c->gbuf_epoch;
     c->slists_key.scene_gen = c->scene_gen;
     c->slists_key.geom_gen = c->geom_gen;
+    return RESTIR_OK;
+}
+
+// The visibility bits route `r` (Route::bits) reads, after ensure_shadow_lists of the same frame: kept when they hold
+// the answers of the lists as they stand -- the same build, so the same key, rect and flags -- else built now from
+// those lists, on the frame's stream behind their build and ahead of the pass.
+static restir_status ensure_shadow_vis(restir_ctx* c, hipStream_t st) {
+    const ShadowListsDev& l = c->slists_dev;
+    if (c->svis_valid && c->svis.p && c->svis_lists_build == c->slists_builds && c->svis_dev.lists.rec == l.rec) return RESTIR_OK;
+    c->svis_valid = false;
+    ST_TRY(c->svis.ensure(sv_size(l.rg.rw, l.rg.rh, l.s.num_lights) * sizeof(uint32_t)));
+    ShadowVisDev d{l, c->svis.as<uint32_t>()};
+    HIP_TRY(launch_shadow_vis(d, st));
+    c->shadow_vis_builds++;
+    c->svis_dev = d;
+    c->svis_lists_build = c->slists_builds;
+    c->svis_valid = true;
     return RESTIR_OK;
 }
 
@@ -1908,6 +1943,8 @@ restir_status Frame::spatial_passes(const FramePlan& p) {
         Ask ask = pass_ask(p, pass, last.rp_out);
         // the fused last pass's rays over the view's shadow lists, from the second still frame on (final.lists)
         ask.shadow_lists = ask.fin && c->gbuf_streak >= c->tuning.final_lists_after;
+        // ... their answers from the view's visibility bits, from the final.vis_after-th on (final.vis)
+        ask.shadow_vis = ask.shadow_lists && c->gbuf_streak >= c->tuning.final_vis_after;
         last = route_spatial(s, pr, f, c->tuning, ask);
         b = fb.bufs(camd, restir_rng_key(c->seed, frame, RESTIR_STAGE_SPATIAL, pass), cur, nxt);
         b.vis = vis;
@@ -1916,6 +1953,11 @@ restir_status Frame::spatial_passes(const FramePlan& p) {
             ST_TRY(ensure_shadow_lists(c, last, s, pr, fb.pm(), tmiss, st));
             b.shadow_lists = c->slists.as<uint4>();
             c->shadow_list_frames++;
+            if (last.bits) {
+                ST_TRY(ensure_shadow_vis(c, st));
+                b.shadow_vis = c->svis.as<uint32_t>();
+                c->shadow_vis_frames++;
+            }
         }
         if (pass + 1 == passes) b.hout = fb.fh(nxt);   // (frame_handles; the route names them)
         TIMED(c, RESTIR_K_SPATIAL, launch_spatial(last, s, pr, f, b, st));
@@ -2735,6 +2777,49 @@ restir_status restir_shadow_list_frames(restir_ctx* c, uint64_t* out_frames) {
     return RESTIR_OK;
 }
 
+restir_status restir_shadow_vis_frames(restir_ctx* c, uint64_t* out_frames) {
+    if (!c || !out_frames) return fail(RESTIR_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out_frames = c->shadow_vis_frames;
+    return RESTIR_OK;
+}
+
+restir_status restir_shadow_vis_builds(restir_ctx* c, uint64_t* out_builds) {
+    if (!c || !out_builds) return fail(RESTIR_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out_builds = c->shadow_vis_builds;
+    return RESTIR_OK;
+}
+
+// restir_debug_shadow_vis between its buffer's allocation and its release
+static restir_status debug_shadow_vis_run(restir_ctx* c, const ShadowVisDev& d, uint32_t light, size_t n, DevBuf& bo, uint8_t* out) {
+    ST_TRY(bo.ensure(n));
+    hipError_t e = launch_debug_shadow_vis(d, light, bo.as<uint8_t>(), c->stream);
+    if (e != hipSuccess) return fail(RESTIR_ERR_HIP, "debug shadow vis launch: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(out, bo.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RESTIR_OK;
+}
+
+restir_status restir_debug_shadow_vis(restir_ctx* c, uint32_t light, uint32_t width, uint32_t height, uint8_t* out_bits) {
+    if (!c || !out_bits) return fail(RESTIR_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    const restir_ctx::ShadowListsKey& k = c->slists_key;
+    if (!c->has_scene || !c->gbuf.valid || !k.valid || k.gbuf_epoch != c->gbuf_epoch || k.scene_gen != c->scene_gen ||
+        k.geom_gen != c->geom_gen || !c->svis_valid || !c->svis.p || c->svis_lists_build != c->slists_builds)
+        return fail(RESTIR_ERR_STATE, "restir_debug_shadow_vis: no visibility bits of the kept G-buffer (a frame builds them)");
+    const ShadowVisDev& d = c->svis_dev;
+    if (light >= d.lists.s.num_lights) return fail(RESTIR_ERR_INVALID, "light %u of %u", light, d.lists.s.num_lights);
+    if (width != d.lists.rg.rw || height != d.lists.rg.rh)
+        return fail(RESTIR_ERR_INVALID, "the plane is %u x %u, the bits' rectangle %u x %u", width, height, d.lists.rg.rw,
+                    d.lists.rg.rh);
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf bo;
+    const restir_status st = debug_shadow_vis_run(c, d, light, (size_t)width * height, bo, out_bits);
+    bo.release();   // on every path
+    return st;
+}
+
 // restir_debug_shadow_lists between its buffers' allocation and their release
 static restir_status debug_shadow_lists_run(restir_ctx* c, const ShadowListsDev& d, uint32_t light, size_t n, DevBuf& bb, DevBuf& bl,
                                             uint8_t* out_bvh, uint8_t* out_list) {
@@ -3378,7 +3463,14 @@ restir_status restir_timings(restir_ctx* c, double* ms, uint64_t* launches) {
 restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     if (!c || !key) return fail(RESTIR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    c->gbuf.valid = false;   // a knob may change what a frame leaves in the G-buffer planes: the next one traces
+    // A knob may change what a frame leaves in the G-buffer planes: the next one traces.  Not these five: the timing
+    // knobs choose which launches carry an event pair and how it is created, the two *_after knobs on which reusing frame
+    // a cache is built -- none of them reaches a kernel's arguments or launch shape, so no stored byte of the G-buffer,
+    // the tile flags, the shadow lists or the visibility bits can differ (DESIGN.md §6 "Knobs that keep the caches")
+    static const char* const kKeepsCaches[] = {"timing.mask", "timing.every", "timing.fence", "final.lists_after", "final.vis_after"};
+    bool keeps = false;
+    for (const char* k : kKeepsCaches) keeps = keeps || !std::strcmp(key, k);
+    if (!keeps) c->gbuf.valid = false;
     Tuning& t = c->tuning;
     const uint32_t v = (uint32_t)value;
     if (!std::strcmp(key, "primary.lds")) t.primary_lds = v;
@@ -3419,6 +3511,14 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     }
     else if (!std::strcmp(key, "final.lists_after")) { if (v < 1) return fail(RESTIR_ERR_INVALID, "final.lists_after: >= 1"); t.final_lists_after = v; }
     else if (!std::strcmp(key, "final.lists_cap")) { if (v < 1 || v > kSlCap) return fail(RESTIR_ERR_INVALID, "final.lists_cap: 1 .. 15"); t.final_lists_cap = v; }
+    else if (!std::strcmp(key, "final.vis")) {
+        t.final_vis = v;
+        if (!v) { HIP_TRY(hipSetDevice(c->device)); drop_shadow_vis(c); }
+    }
+    else if (!std::strcmp(key, "final.vis_after")) {
+        if (v < t.final_lists_after) return fail(RESTIR_ERR_INVALID, "final.vis_after: >= final.lists_after (%u)", t.final_lists_after);
+        t.final_vis_after = v;
+    }
     else if (!std::strcmp(key, "primary.tl")) t.primary_tl = v;
     else if (!std::strcmp(key, "gbuf.reuse")) t.gbuf_reuse = v;
     else if (!std::strcmp(key, "mis.chunk")) t.mis_chunk = v;   // applies from the next ensure_mis

@@ -202,6 +202,10 @@ struct Tuning {
                                    // build costs about three C2 frames, so a view that moves sooner than some sixty frames
                                    // after it stopped loses by it; raise this where views pause briefly
     uint32_t final_lists_cap = 15; // indices a list record holds, 1 .. 15 (a longer list walks the BVH; tests lower it)
+    uint32_t final_vis = 1;        // restir_render: once the lists stand, k_shadow_vis stores every (pixel, light) answer of
+                                   // their rays as one bit (shadow_vis.h) and the fused last pass reads its answers
+                                   // (k_spatial1hg_t2_final_vis); 0: the lists' rays are traced every frame
+    uint32_t final_vis_after = 4;  // ... built by the frame whose streak of reusing frames reaches this (>= final.lists_after)
     uint32_t primary_tl = 1;       // fused primary + RIS, one tile per block: the primary rays test the tile's candidate
                                    // triangles (tile_triangles) instead of walking the BVH
     uint32_t gbuf_reuse = 1;       // restir_render: a frame whose view (scene upload, camera, image size, region) is the one

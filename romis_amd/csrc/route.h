@@ -9,6 +9,7 @@
 
 #include "launch_shape.h"
 #include "shadow_lists.h"
+#include "shadow_vis.h"
 
 namespace romis {
 
@@ -64,6 +65,8 @@ struct Ask {
     bool gbuf_cached = false;
     // spatial: the view's shadow lists (shadow_lists.h) are built: a fused last pass may trace its rays over them
     bool shadow_lists = false;
+    // ... and its visibility bits (shadow_vis.h) may be built too: such a pass reads its rays' answers
+    bool shadow_vis = false;
 };
 
 struct Route {
@@ -97,6 +100,7 @@ struct Route {
     uint32_t bvh_lds = 0;      // kSpatial: shadow rays over the BVH staged in LDS
     bool final_done = false;   // spatial: final shading ran in this kernel
     bool lists = false;        // ... its rays over the shadow lists (k_spatial1hg_t2_final_lists)
+    bool bits = false;         // ... their answers read from the visibility bits (k_spatial1hg_t2_final_vis; `vis` is the ray plane)
     uint32_t miss = 1;         // final: the miss shortcut is allowed (final.miss)
 
     Region region(Region rg) const {
@@ -358,6 +362,8 @@ inline Route route_spatial(const SceneDev& s, const Region& rg, const FeaturesDe
             r.miss = fin.miss;
             // the rays over the view's shadow lists (final.lists) where the caller holds them: one-byte triangle indices
             r.lists = ask.shadow_lists && tu.final_lists && s.num_tris <= kSlMaxTris;
+            // ... answered from the view's visibility bits (final.vis): at most kSvMaxWords words per pixel
+            r.bits = r.lists && ask.shadow_vis && tu.final_vis && s.num_lights > 0u && sv_words(s.num_lights) <= kSvMaxWords;
             // nothing else reads the pass's reservoir planes (no returned grid): the fused kernel does not store them
             if (ask.fin_dead) r.res_dead = 1u;
         } else {

@@ -360,6 +360,27 @@ class Renderer:
               "restir_debug_shadow_lists")
         return a, b
 
+    def shadow_vis_frames(self) -> int:
+        """render_restir frames so far whose fused last pass read its shadow rays' answers from the view's visibility
+        bits (restir_shadow_vis_frames; tuning "final.vis")."""
+        n = C.c_uint64()
+        check(self.lib, self.lib.restir_shadow_vis_frames(self.ctx, C.byref(n)), "restir_shadow_vis_frames")
+        return int(n.value)
+
+    def shadow_vis_builds(self) -> int:
+        """Builds of the visibility bits so far (restir_shadow_vis_builds)."""
+        n = C.c_uint64()
+        check(self.lib, self.lib.restir_shadow_vis_builds(self.ctx, C.byref(n)), "restir_shadow_vis_builds")
+        return int(n.value)
+
+    def debug_shadow_vis(self, light: int, width: int, height: int):
+        """[height][width] uint8 plane of the last frame's owned rectangle: the stored answer of every pixel's shadow ray to
+        point light `light`, 1 / 0, 0xFF where no bit is held (restir_debug_shadow_vis)."""
+        a = np.zeros((height, width), np.uint8)
+        check(self.lib, self.lib.restir_debug_shadow_vis(self.ctx, light, width, height, a.ctypes.data_as(C.POINTER(C.c_uint8))),
+              "restir_debug_shadow_vis")
+        return a
+
     # ---- timing ---------------------------------------------------------------------------------------
     def enable_timing(self, on: bool = True) -> None:
         check(self.lib, self.lib.restir_enable_timing(self.ctx, 1 if on else 0), "restir_enable_timing")
