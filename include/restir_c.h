@@ -677,6 +677,22 @@ restir_status restir_shadow_vis_builds(restir_ctx* ctx, uint64_t* out_builds);
  * background tile or one that shows no surface. */
 restir_status restir_debug_shadow_vis(restir_ctx* ctx, uint32_t light, uint32_t width, uint32_t height, uint8_t* out_bits);
 
+/* restir_render frames of this context so far whose RIS read its candidates' target pdfs from the view's p-hat table
+ * (tuning "ris.phat", "ris.phat_after", "ris.phat_max_mb"): one float per (pixel, point light) of a view that stands still
+ * with its lights and materials unchanged -- N = 1, point lights (at most 128), at most 32 candidates, no initial
+ * visibility rays, with or without temporal reuse; other shapes run as before.  The first frame after the view, the
+ * geometry, the lights or the materials change frees it.  The table takes 4 bytes x the light count (padded to a multiple of 4) per pixel of the view's 32 x 8 tiles: 1,013 MiB for
+ * 1920 x 1080 and 128 lights.  A table over ris.phat_max_mb MiB, or one the device has no memory for, is not built and
+ * the frames run without it.  restir_phat_builds: how often it was built. */
+restir_status restir_phat_frames(restir_ctx* ctx, uint64_t* out_frames);
+restir_status restir_phat_builds(restir_ctx* ctx, uint64_t* out_builds);
+
+/* Test hook for that table, as the last frame left it (RESTIR_ERR_STATE when there is none for the kept G-buffer): for
+ * every pixel of that frame's view, width x height (RESTIR_ERR_INVALID when the frame's was another size; row-major from
+ * its first row), the stored target pdf of point light `light` (< num_lights, else RESTIR_ERR_INVALID); -1 where none is
+ * held -- a pixel of a background tile or one that shows no surface. */
+restir_status restir_debug_phat(restir_ctx* ctx, uint32_t light, uint32_t width, uint32_t height, float* out_phat);
+
 /* Test hook for those lists, as the last frame left them (RESTIR_ERR_STATE when there are none for the kept G-buffer):
  * for every pixel of that frame's owned rectangle, width x height (RESTIR_ERR_INVALID when the frame's was another
  * size; row-major from its first row, one byte each), the shadow ray from the

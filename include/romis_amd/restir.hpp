@@ -313,6 +313,23 @@ public:
         bits.assign(size_t(width) * height, 0);
         check(restir_debug_shadow_vis(ctx_, light, width, height, bits.data()), "restir_debug_shadow_vis");
     }
+    // Frames so far whose RIS read its candidates' target pdfs from the view's p-hat table, and the builds of that
+    // table (restir_phat_frames, restir_phat_builds)
+    uint64_t phatFrames() const {
+        uint64_t n = 0;
+        check(restir_phat_frames(ctx_, &n), "restir_phat_frames");
+        return n;
+    }
+    uint64_t phatBuilds() const {
+        uint64_t n = 0;
+        check(restir_phat_builds(ctx_, &n), "restir_phat_builds");
+        return n;
+    }
+    // Test hook (restir_debug_phat): width x height floats, the last frame's view (another size is refused)
+    void debugPhat(uint32_t light, std::vector<float>& phat, uint32_t width, uint32_t height) const {
+        phat.assign(size_t(width) * height, 0.0f);
+        check(restir_debug_phat(ctx_, light, width, height, phat.data()), "restir_debug_phat");
+    }
     // A snapshot of the last image (restir_image_begin): converted on the device, copied to pinned memory behind the
     // frame that produced it; returns without synchronising, so the next frame may be rendered at once
     PresentedImage present(restir_image_format format = RESTIR_IMAGE_RGBA8) {

@@ -46,12 +46,13 @@ SOURCES = [("kernels.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS)] + ABI_UNITS +
     ("reproject.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("shadow_lists.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("shadow_vis.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
+    ("phat_table.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("present.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("bvh.cpp", ["-x", "c++"]),
     ("screen.cpp", ["-x", "c++"]),
 ]
 HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
-           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "shadow_vis.h", "abi_error.h", "layout.h", "halo_segs.h", "present.h"]
+           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "shadow_vis.h", "phat_table.h", "abi_error.h", "layout.h", "halo_segs.h", "present.h"]
 
 
 def source_hash() -> str:
@@ -60,7 +61,7 @@ def source_hash() -> str:
     only when it matches)."""
     import hashlib
     h = hashlib.sha256()
-    for f in [SOURCES[0][0]] + [u for u, _ in ABI_UNITS] + HEADERS:
+    for f in [SOURCES[0][0], "phat_table.hip"] + [u for u, _ in ABI_UNITS] + HEADERS:
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(f.encode() + b"\0" + fh.read())
     h.update(" ".join([c for c in COMMON + DEVICE + KERNEL_FLAGS if not c.startswith("-I")]).encode())   # flags, not paths
@@ -106,6 +107,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_refit_check(force)
     build_shadow_lists_check(force)
     build_shadow_vis_layout(force)
+    build_phat_layout(force)
     if verbose:
         print(LIB)
     return LIB
@@ -171,6 +173,18 @@ def build_shadow_vis_layout(force: bool = False) -> str:
     tool = os.path.join(OUT, "tools", "shadow_vis_layout")
     src = os.path.join(ROOT, "tests", "cpp", "shadow_vis_layout.cpp")
     deps = [src, os.path.join(CSRC, "shadow_vis.h"), __file__]
+    if os.path.exists(src) and (force or _stale(tool, deps)):
+        os.makedirs(os.path.dirname(tool), exist_ok=True)
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", tool])
+    return tool
+
+
+def build_phat_layout(force: bool = False) -> str:
+    """tools/phat_layout: tests/cpp/phat_layout.cpp over csrc/phat_table.h with the host compiler -- the table's indices
+    as the header computes them (tests/test_phat_layout.py); no device code."""
+    tool = os.path.join(OUT, "tools", "phat_layout")
+    src = os.path.join(ROOT, "tests", "cpp", "phat_layout.cpp")
+    deps = [src, os.path.join(CSRC, "phat_table.h"), __file__]
     if os.path.exists(src) and (force or _stale(tool, deps)):
         os.makedirs(os.path.dirname(tool), exist_ok=True)
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", tool])

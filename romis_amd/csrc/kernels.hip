@@ -2847,6 +2847,7 @@ hipError_t launch_primary_ris(const Route& r, const SceneDev& s, const Region& r
                               hipStream_t stream) {
     if (r.kernel == Kernel::kNone) return hipSuccess;
     assert(r.ok && b.cam);
+    if (r.phat) return launch_gbuf_ris_phat(r, s, rg0, f, b, stream);   // (phat_table.hip)
     const Region rg = r.region(rg0);
     float* const hw = named(r.how, b.hout.w);
     uint32_t* const hm = named(r.hom, b.hout.m);

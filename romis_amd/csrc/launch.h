@@ -32,6 +32,7 @@ struct LaunchBufs {
     float* rgb = nullptr;              // final shading's image (the owned rect)
     const uint4* shadow_lists = nullptr;   // the view's shadow-list records (shadow_lists.h), for a route with `lists`
     const uint32_t* shadow_vis = nullptr;  // the view's visibility bits (shadow_vis.h), for a route with `bits`
+    const float* phat = nullptr;       // the view's p-hat table (phat_table.h), for a route with `phat`
     TemporalIn tin{};                  // primary + RIS + temporal: the predecessor grid
 };
 
@@ -44,6 +45,9 @@ hipError_t launch_ris(const Route& r, const SceneDev& s, const Region& rg, const
 // reads b.n_t, b.p_mat and b.flags as an earlier frame of the same view left them and writes none of them.
 hipError_t launch_primary_ris(const Route& r, const SceneDev& s, const Region& rg, const FeaturesDev& f, const LaunchBufs& b,
                               hipStream_t stream);
+// launch_primary_ris's launch for a kGbufRis route with `phat` (phat_table.hip)
+hipError_t launch_gbuf_ris_phat(const Route& r, const SceneDev& s, const Region& rg, const FeaturesDev& f, const LaunchBufs& b,
+                                hipStream_t stream);
 hipError_t launch_temporal(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key, const float* origin,
                            const float4* n_t, const float4* p_mat, const float4* ca, const float4* cb,
                            const float4* pa, const float4* pb, float4* oa, float4* ob, float2* odbg,

@@ -33,6 +33,7 @@
 #include "reproject.h"
 #include "restir_types.h"
 #include "shadow_lists.h"
+#include "phat_table.h"
 #include "shadow_vis.h"
 
 namespace romis {
@@ -315,6 +316,23 @@ struct restir_ctx {
     ShadowVisDev svis_dev{};
     uint64_t shadow_vis_frames = 0;                 // frames whose last pass read the bits (restir_shadow_vis_frames)
     uint64_t shadow_vis_builds = 0;                 // k_shadow_vis launches (restir_shadow_vis_builds)
+    // The p-hat table of the kept G-buffer (phat_table.h, tuning "ris.phat"): RIS's target pdf of every (pixel, point
+    // light), valid for what `phat_key` names -- that G-buffer, the light table and the materials (scene_gen) -- and for
+    // the launch `phat_dev` describes (the view, the tile flags, L, Features::shading; tex_on is the view record's).
+    DevBuf phat;
+    struct PhatKey {
+        bool valid = false;
+        uint64_t gbuf_epoch = 0, scene_gen = 0;
+    } phat_key;
+    // a table the device had no memory for: not asked for again while it would be the same table
+    struct PhatRefused {
+        bool valid = false;
+        uint64_t gbuf_epoch = 0, scene_gen = 0;
+        size_t bytes = 0;
+    } phat_refused;
+    PhatTableDev phat_dev{};
+    uint64_t phat_frames = 0;                       // frames whose RIS read the table (restir_phat_frames)
+    uint64_t phat_builds = 0;                       // k_phat_table launches (restir_phat_builds)
     int cur = 0;
     uint32_t rgb_w = 0, rgb_h = 0;
 
@@ -833,6 +851,13 @@ static void drop_shadow_vis(restir_ctx* c) {
     c->svis_valid = false;
     c->svis.release();
 }
+// Free the p-hat table (restir_ctx::phat) where nothing can read it again: the kept G-buffer it was built over is
+// replaced (a tracing frame), the lights or materials changed, another scene, a cap below its size, ris.phat off, the
+// context's end.  (hipFree waits for the kernels that read it.)
+static void drop_phat_table(restir_ctx* c) {
+    c->phat_key.valid = false;
+    c->phat.release();
+}
 static void drop_shadow_lists(restir_ctx* c) {
     c->slists_key.valid = false;
     c->slists.release();
@@ -849,6 +874,7 @@ void restir_destroy(restir_ctx* c) {
                           &c->rpj_map})
             b->release();
         drop_shadow_lists(c);
+        drop_phat_table(c);
         for (DevBuf* b : {&c->nodes, &c->nodes_q, &c->tri_v0, &c->tri_e1, &c->tri_e2, &c->tri_n0, &c->tri_n1, &c->tri_n2,
                           &c->materials, &c->lights, &c->light_c2, &c->light_c4, &c->light_col, &c->tex_texels, &c->tex_dims, &c->tri_uv, &c->uv, &c->n_t, &c->p_mat, &c->ra[0], &c->ra[1], &c->rb[0], &c->rb[1],
                           &c->dbg[0], &c->dbg[1], &c->rgb, &c->halo_scratch, &c->rec[0], &c->rec[1], &c->rp[0], &c->rp[1]})
@@ -1070,6 +1096,7 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
     c->gbuf.valid = false;   // another scene: the kept G-buffer is not its view
     HIP_TRY(hipSetDevice(c->device));
     drop_shadow_lists(c);    // ... nor are the lists its triangles' (a scene they serve builds its own)
+    drop_phat_table(c);      // ... nor the p-hat table its lights' and materials'
 
     // flatten triangles (mesh order = original index order, like the oracle)
     std::vector<BvhTriangle> tris;
@@ -1701,6 +1728,67 @@ static restir_status ensure_shadow_vis(restir_ctx* c, hipStream_t st) {
     return RESTIR_OK;
 }
 
+// The p-hat table a route with `phat` reads (k_gbuf_ris_n1_lds_pt_phat over view `rg`): kept when it was built for this
+// G-buffer, light table, materials and launch, else built now, on the frame's stream ahead of RIS.  false in `ok`: no
+// table (over ris.phat_max_mb, or no memory for it) -- the frame runs without it, which is no error.
+static restir_status ensure_phat_table(restir_ctx* c, const SceneDev& s, const Region& rg, const FeaturesDev& f, const float* origin,
+                                       const float4* n_t, const float4* p_mat, const uint8_t* tmiss, hipStream_t st, bool& ok) {
+    ok = false;
+    PhatTableDev d{};
+    d.s = s;
+    d.rg = rg;
+    d.f = f;
+    for (int i = 0; i < 3; i++) d.origin[i] = origin[i];
+    d.n_t = n_t;
+    d.p_mat = p_mat;
+    d.tmiss = tmiss;
+    const size_t bytes = pt_size(rg.vw, rg.vh, s.num_lights) * sizeof(float);
+    if (bytes > (size_t)c->tuning.ris_phat_max_mb << 20) {
+        drop_phat_table(c);   // (a table from before the cap was lowered)
+        return RESTIR_OK;
+    }
+    const PhatTableDev& h = c->phat_dev;
+    const bool same_launch = h.rg.W == rg.W && h.rg.H == rg.H && h.rg.vx0 == rg.vx0 && h.rg.vy0 == rg.vy0 && h.rg.vw == rg.vw &&
+                             h.rg.vh == rg.vh && h.rg.ps == rg.ps && h.rg.map2d == rg.map2d && h.n_t == n_t && h.p_mat == p_mat &&
+                             h.tmiss == tmiss && h.s.num_lights == s.num_lights && h.s.light_c2 == s.light_c2 &&
+                             h.s.materials == s.materials && h.s.num_materials == s.num_materials && h.s.tex_on == s.tex_on &&
+                             h.s.gbuf_uv == s.gbuf_uv && h.f.shading == f.shading &&
+                             !std::memcmp(h.origin, d.origin, sizeof(d.origin));
+    if (c->phat_key.valid && c->phat.p && c->phat_key.gbuf_epoch == c->gbuf_epoch && c->phat_key.scene_gen == c->scene_gen &&
+        same_launch) {
+        ok = true;
+        return RESTIR_OK;
+    }
+    c->phat_key.valid = false;
+    if (c->phat.bytes < bytes) {
+        // a table that does not fit the device's memory is not an error: the frame evaluates its p-hats
+        c->phat.release();
+        restir_ctx::PhatRefused& no = c->phat_refused;
+        if (no.valid && no.gbuf_epoch == c->gbuf_epoch && no.scene_gen == c->scene_gen && no.bytes == bytes) return RESTIR_OK;
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            no.valid = true;
+            no.gbuf_epoch = c->gbuf_epoch;
+            no.scene_gen = c->scene_gen;
+            no.bytes = bytes;
+            return RESTIR_OK;
+        }
+        no.valid = false;
+        c->phat.p = p;
+        c->phat.bytes = bytes;
+    }
+    d.tab = c->phat.as<float>();
+    HIP_TRY(launch_phat_table(d, st));
+    c->phat_builds++;
+    c->phat_dev = d;
+    c->phat_key.valid = true;
+    c->phat_key.gbuf_epoch = c->gbuf_epoch;
+    c->phat_key.scene_gen = c->scene_gen;
+    ok = true;
+    return RESTIR_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -1889,13 +1977,33 @@ restir_status Frame::ris_stage(const FramePlan& p) {
         ris = route_fused(ris_ask);
         gv = gbuf_view(c, s, camd, width, height, t, ris, tmiss);
         ris_ask.gbuf_cached = c->tuning.gbuf_reuse && !fb.records && gbuf_reusable(c->gbuf, gv);
-        if (ris_ask.gbuf_cached) ris = route_fused(ris_ask);
+        if (ris_ask.gbuf_cached) {
+            // ... and from the ris.phat_after-th such frame with the lights unchanged on, its candidates' target pdfs
+            // from the view's p-hat table (ris.phat); this frame's streak is the last one's + 1 (below)
+            const uint32_t streak = c->gbuf_streak_lights == c->scene_gen ? c->gbuf_streak + 1u : 1u;
+            ris_ask.phat = streak >= c->tuning.ris_phat_after;
+            ris = route_fused(ris_ask);
+            if (ris.phat) {
+                bool have = false;
+                ST_TRY(ensure_phat_table(c, s, ris.region(view), f, b.origin, b.n_t, b.p_mat, ris.flags ? tmiss : nullptr, st, have));
+                if (have) {
+                    b.phat = c->phat.as<float>();
+                    c->phat_frames++;
+                } else {
+                    ris_ask.phat = false;
+                    ris = route_fused(ris_ask);
+                }
+            }
+        }
     } else {
         ris = route_ris(s, view, f, c->tuning, ris_ask);
     }
     // kept by a frame that reuses it; a frame that traces replaces it once its launch is issued (any error return in
     // between leaves none)
     if (!ris_ask.gbuf_cached) c->gbuf.valid = false;
+    // the p-hat table goes with the G-buffer, the lights and the materials it was built from: a context that paused once
+    // and moves on does not keep its memory
+    if (c->phat.p && (!ris_ask.gbuf_cached || c->phat_key.scene_gen != c->scene_gen)) drop_phat_table(c);
     if (p.temporal_fused) {
         ST_TRY(use_prev(prev, c->device, st, c->pool.get()));   // the predecessor's records are complete (its producer's stream)
         b.tin = TemporalIn{fb.pa(prev), fb.pb(prev), restir_rng_key(c->seed, frame, RESTIR_STAGE_TEMPORAL, 0),
@@ -2791,6 +2899,47 @@ restir_status restir_shadow_vis_builds(restir_ctx* c, uint64_t* out_builds) {
     return RESTIR_OK;
 }
 
+restir_status restir_phat_frames(restir_ctx* c, uint64_t* out_frames) {
+    if (!c || !out_frames) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out_frames = c->phat_frames;
+    return RESTIR_OK;
+}
+
+restir_status restir_phat_builds(restir_ctx* c, uint64_t* out_builds) {
+    if (!c || !out_builds) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out_builds = c->phat_builds;
+    return RESTIR_OK;
+}
+
+// restir_debug_phat between its buffer's allocation and its release
+static restir_status debug_phat_run(restir_ctx* c, const PhatTableDev& d, uint32_t light, size_t n, DevBuf& bo, float* out) {
+    ST_TRY(bo.ensure(n * sizeof(float)));
+    hipError_t e = launch_debug_phat(d, light, bo.as<float>(), c->stream);
+    if (e != hipSuccess) return fail(RESTIR_ERR_HIP, "debug phat launch: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(out, bo.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RESTIR_OK;
+}
+
+restir_status restir_debug_phat(restir_ctx* c, uint32_t light, uint32_t width, uint32_t height, float* out_phat) {
+    if (!c || !out_phat) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->phat_key.valid || !c->phat.p || !c->gbuf.valid || c->phat_key.gbuf_epoch != c->gbuf_epoch ||
+        c->phat_key.scene_gen != c->scene_gen)
+        return fail(RESTIR_ERR_STATE, "restir_debug_phat: no p-hat table of the kept G-buffer (a frame builds it)");
+    const PhatTableDev& d = c->phat_dev;
+    if (width != d.rg.rw || height != d.rg.rh)
+        return fail(RESTIR_ERR_INVALID, "restir_debug_phat: the table covers %ux%u pixels, not %ux%u", d.rg.rw, d.rg.rh, width, height);
+    if (light >= d.s.num_lights) return fail(RESTIR_ERR_INVALID, "restir_debug_phat: light %u >= %u", light, d.s.num_lights);
+    DevBuf bo;
+    const restir_status st = debug_phat_run(c, d, light, (size_t)width * height, bo, out_phat);
+    bo.release();
+    return st;
+}
+
 // restir_debug_shadow_vis between its buffer's allocation and its release
 static restir_status debug_shadow_vis_run(restir_ctx* c, const ShadowVisDev& d, uint32_t light, size_t n, DevBuf& bo, uint8_t* out) {
     ST_TRY(bo.ensure(n));
@@ -3467,7 +3616,8 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     // knobs choose which launches carry an event pair and how it is created, the two *_after knobs on which reusing frame
     // a cache is built -- none of them reaches a kernel's arguments or launch shape, so no stored byte of the G-buffer,
     // the tile flags, the shadow lists or the visibility bits can differ (DESIGN.md §6 "Knobs that keep the caches")
-    static const char* const kKeepsCaches[] = {"timing.mask", "timing.every", "timing.fence", "final.lists_after", "final.vis_after"};
+    static const char* const kKeepsCaches[] = {"timing.mask", "timing.every", "timing.fence", "final.lists_after", "final.vis_after",
+                                              "ris.phat_after"};
     bool keeps = false;
     for (const char* k : kKeepsCaches) keeps = keeps || !std::strcmp(key, k);
     if (!keeps) c->gbuf.valid = false;
@@ -3519,6 +3669,12 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
         if (v < t.final_lists_after) return fail(RESTIR_ERR_INVALID, "final.vis_after: >= final.lists_after (%u)", t.final_lists_after);
         t.final_vis_after = v;
     }
+    else if (!std::strcmp(key, "ris.phat")) {
+        t.ris_phat = v;
+        if (!v) { HIP_TRY(hipSetDevice(c->device)); drop_phat_table(c); }
+    }
+    else if (!std::strcmp(key, "ris.phat_after")) { if (v < 1) return fail(RESTIR_ERR_INVALID, "ris.phat_after: >= 1"); t.ris_phat_after = v; }
+    else if (!std::strcmp(key, "ris.phat_max_mb")) t.ris_phat_max_mb = v;
     else if (!std::strcmp(key, "primary.tl")) t.primary_tl = v;
     else if (!std::strcmp(key, "gbuf.reuse")) t.gbuf_reuse = v;
     else if (!std::strcmp(key, "mis.chunk")) t.mis_chunk = v;   // applies from the next ensure_mis

@@ -211,6 +211,11 @@ struct Tuning {
     uint32_t gbuf_reuse = 1;       // restir_render: a frame whose view (scene upload, camera, image size, region) is the one
                                    // the context's G-buffer planes and tile flags hold runs the k_gbuf_ris family over
                                    // them instead of tracing the primary rays again; 0: every frame traces
+    uint32_t ris_phat = 1;         // restir_render: once a still view's G-buffer is reused, k_phat_table stores every (pixel,
+                                   // point light) target pdf (phat_table.h) and RIS reads its candidates' from it
+                                   // (k_gbuf_ris_n1_lds_pt_phat); 0: evaluated every frame
+    uint32_t ris_phat_after = 4;   // ... built by the frame whose streak of reusing frames reaches this
+    uint32_t ris_phat_max_mb = 2048; // ... unless the table would be larger than this many MiB (1080p x 128 lights: 1013)
     uint32_t mis_chunk = 0;       // R-OMIS samples per k_romis_samples / k_romis_accum pair; 0 = the scratch budget
 };
 

@@ -9,6 +9,7 @@
 
 #include "launch_shape.h"
 #include "shadow_lists.h"
+#include "phat_table.h"
 #include "shadow_vis.h"
 
 namespace romis {
@@ -67,6 +68,9 @@ struct Ask {
     bool shadow_lists = false;
     // ... and its visibility bits (shadow_vis.h) may be built too: such a pass reads its rays' answers
     bool shadow_vis = false;
+    // primary + RIS over a cached G-buffer: the view's p-hat table (phat_table.h) may be built: the N = 1 point-light
+    // member then reads its candidates' target pdfs from it
+    bool phat = false;
 };
 
 struct Route {
@@ -102,6 +106,7 @@ struct Route {
     bool lists = false;        // ... its rays over the shadow lists (k_spatial1hg_t2_final_lists)
     bool bits = false;         // ... their answers read from the visibility bits (k_spatial1hg_t2_final_vis; `vis` is the ray plane)
     uint32_t miss = 1;         // final: the miss shortcut is allowed (final.miss)
+    bool phat = false;         // kGbufRis: the candidates' target pdfs read from the p-hat table (k_gbuf_ris_n1_lds_pt_phat)
 
     Region region(Region rg) const {
         rg.map2d = map2d; rg.xcd_rows = xcd_rows; rg.xcd_cols = xcd_cols;
@@ -239,6 +244,11 @@ inline Route route_primary_ris(const SceneDev& s, const Region& rg, const Featur
         // the same family member (r.staged as the fused kernel decided it), its LDS without the BVH where no ray needs it
         r.kernel = Kernel::kGbufRis;
         r.lds = (f.initial_vis ? bvh : 0) + (r.staged ? (size_t)lt_stride(r.lt) * s.num_lights * 16 : 0);
+        // ... with its candidates' target pdfs from the view's p-hat table (ris.phat): the staged N = 1 point-light
+        // member writing both handle planes, no initial visibility rays, a shape the table's kernel serves (pt_fast)
+        r.phat = ask.phat && tu.ris_phat && r.n == 1u && r.lt == kLtPoint && r.staged && r.hom && !f.initial_vis && !ask.dbg &&
+                 pt_fast(s.num_lights, f.M);
+        if (r.phat) r.lds = pt_lds_bytes(s.num_lights);
     }
     return r;
 }
@@ -252,6 +262,7 @@ inline Route route_primary_ris_temporal(const SceneDev& s, const Region& rg, con
     r.flags = false;   // (no background tiles: the output is not the RIS result)
     r.skip = 0u;
     r.hom = r.how;     // both planes at N = 1 and 2
+    r.phat = r.phat && r.ok;   // (k_gbuf_ris_n1_lds_pt_phat_temporal)
     if (r.kernel != Kernel::kNone)
         r.kernel = !r.ok ? Kernel::kNone : ask.gbuf_cached ? Kernel::kGbufRisTemporal : Kernel::kPrimaryRisTemporal;
     return r;

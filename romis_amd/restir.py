@@ -381,6 +381,27 @@ class Renderer:
               "restir_debug_shadow_vis")
         return a
 
+    def phat_frames(self) -> int:
+        """render_restir frames so far whose RIS read its candidates' target pdfs from the view's p-hat table
+        (restir_phat_frames; tuning "ris.phat")."""
+        n = C.c_uint64()
+        check(self.lib, self.lib.restir_phat_frames(self.ctx, C.byref(n)), "restir_phat_frames")
+        return int(n.value)
+
+    def phat_builds(self) -> int:
+        """Builds of the p-hat table so far (restir_phat_builds)."""
+        n = C.c_uint64()
+        check(self.lib, self.lib.restir_phat_builds(self.ctx, C.byref(n)), "restir_phat_builds")
+        return int(n.value)
+
+    def debug_phat(self, light: int, width: int, height: int):
+        """[height][width] float32 plane of the last frame's view: the stored target pdf of point light `light` at every
+        pixel, -1 where none is held (restir_debug_phat)."""
+        a = np.zeros((height, width), np.float32)
+        check(self.lib, self.lib.restir_debug_phat(self.ctx, light, width, height, a.ctypes.data_as(C.POINTER(C.c_float))),
+              "restir_debug_phat")
+        return a
+
     # ---- timing ---------------------------------------------------------------------------------------
     def enable_timing(self, on: bool = True) -> None:
         check(self.lib, self.lib.restir_enable_timing(self.ctx, 1 if on else 0), "restir_enable_timing")
