@@ -447,6 +447,78 @@ void          restir_image_release(restir_image* image);
 restir_status restir_download_rgba8(restir_ctx* ctx, uint8_t* out_rgba, size_t pixels);
 restir_status restir_write_image_bmp(restir_ctx* ctx, const char* path);
 
+/* ---- accumulating frames: running mean, variance and converged image on the device -------------------------
+ * A context folds its last image -- what restir_download_rgb serves, 3 floats per owned pixel -- into a running mean
+ * and, with RESTIR_ACCUM_VARIANCE, a sum of squared deviations m2, one of each per float, without the image leaving
+ * the device.  Folding the n-th image value x (n = 1, 2, ...) uses inv_n = 1.0f / (float)n computed once on the host and
+ * three single float32 operations without contraction, in this order (Welford's recurrence with a reciprocal):
+ *     d = x - mean;   mean' = mean + d * inv_n;   m2' = m2 + d * (x - mean')
+ * IEEE special values propagate as the operations give them; a NaN's payload and sign are not part of the contract.
+ * Tone map AFTER averaging: render the frames with enable_tone_mapping = 0 and hand the tone-mapping fields to
+ * restir_accum_resolve (the mean of tone-mapped frames is biased dark).
+ *   restir_accum_begin      starts (or restarts) an accumulation with an empty state; the buffers -- 12 bytes per pixel, 24
+ *                           with the variance -- are created by the first add
+ *   restir_accum_add        folds the last image in; it only enqueues, on the context's stream behind the frame
+ *   restir_accum_resolve    writes the mean as the context's last image, tone mapped by tone's enable_tone_mapping /
+ *                           gamma / exposure with the final kernels' own arithmetic (tone == NULL: the mean's bits);
+ *                           restir_download_rgb, restir_image_begin, restir_download_rgba8 and restir_write_image_bmp
+ *                           then serve the resolved image.  It only enqueues and leaves the state as it is
+ *   restir_accum_stats_get  (needs the variance and two frames) synchronises the context's stream: est_mse = the mean
+ *                           over the finite floats of m2 / (n (n - 1)), the estimate of E|mean - expectation|^2 per
+ *                           float; mean_value = the mean of their means; nonfinite = the floats whose mean or m2 is
+ *                           not finite, left out of both.  Deterministic: a fixed two-stage reduction in double
+ *   restir_accum_download   test hook: the state as it stands, 3 W H floats each (m2 may be NULL; zeros are written
+ *                           for an accumulation without the variance); synchronises
+ *   restir_accum_end        closes the accumulation and frees the buffers (restir_destroy does so too)
+ *   restir_accum_fold       pure host: the same step over arrays, x folded into mean (and m2) as the n-th value -- the
+ *                           kernel's own text, bit for bit; for clients that fold tiles on the CPU
+ * An add folds an image a producer wrote -- restir_render, restir_render_mis_tile(s), restir_halo_end, restir_stage_final,
+ * restir_stage_mis_finish, or a restir_stage_upload of RESTIR_BUF_RGB -- and each such image once.  It is
+ * RESTIR_ERR_STATE, with nothing changed, when no accumulation is open, nothing has been rendered, a halo frame is
+ * between restir_halo_begin and restir_halo_end, the last image is a resolve's or was added already, its size is not
+ * the accumulation's (the first added image's), or RESTIR_ACCUM_MAX_FRAMES are folded.  restir_accum_resolve without a
+ * frame and restir_accum_stats_get with fewer than two, or without the variance, are RESTIR_ERR_STATE; a NULL argument,
+ * unknown flags, restir_accum_fold with n = 0 or n > RESTIR_ACCUM_MAX_FRAMES, and a download whose count is below
+ * 3 W H are RESTIR_ERR_INVALID.  An allocation the device refuses is RESTIR_ERR_HIP and closes the accumulation.
+ * No accumulation call touches the still view's caches (the kept G-buffer, the shadow lists, the visibility bits, the
+ * p-hat table, their streak): a view that stands still keeps them while it accumulates.  The launches have no
+ * RESTIR_K_* slot: restir_timings does not see them. */
+#define RESTIR_ACCUM_VARIANCE   1u
+#define RESTIR_ACCUM_MAX_FRAMES 16777215u   /* 2^24 - 1: (float)n is exact */
+typedef struct restir_accum_stats {
+    uint32_t width, height, frames, flags;
+    uint64_t nonfinite;   /* floats left out */
+    double   est_mse;     /* sum of terms / floats counted: estimate of E|mean - expectation|^2 per float */
+    double   mean_value;  /* sum of mean / floats counted */
+} restir_accum_stats;
+restir_status restir_accum_begin(restir_ctx* ctx, uint32_t flags);
+restir_status restir_accum_add(restir_ctx* ctx);
+restir_status restir_accum_resolve(restir_ctx* ctx, const restir_features* tone /* nullable */);
+restir_status restir_accum_stats_get(restir_ctx* ctx, restir_accum_stats* out);
+restir_status restir_accum_download(restir_ctx* ctx, float* mean, float* m2 /* nullable */, size_t count);
+restir_status restir_accum_end(restir_ctx* ctx);
+restir_status restir_accum_fold(float* mean, float* m2 /* nullable */, const float* x, size_t count, uint32_t n);
+
+/* "Render until it is good enough" in one call: begins a fresh accumulation (req->flags), then renders frames of one
+ * view by restir_render with enable_tone_mapping forced to 0 and adds each, with no host synchronisation between
+ * frames.  Every frame consumes its own frame index; with features->temporal_reuse each frame's grid is the next
+ * frame's predecessor (the first has none).  With req->target_mse > 0 (needs RESTIR_ACCUM_VARIANCE and check_every > 0,
+ * else RESTIR_ERR_INVALID) it takes the stats -- which synchronises -- after frame min_frames and then every check_every
+ * frames, and stops once est_mse <= target_mse (a check that cannot be taken yet, with one frame, counts as not
+ * met), or at max_frames.  Then it resolves with the caller's tone-mapping fields and fills out_stats (nullable; zeros
+ * but for the size, the frame count and the flags where the stats cannot be taken) and out_rgb (nullable, the resolved
+ * image as restir_render hands images back).  The accumulation stays open: the caller may add more or read the state.
+ * RESTIR_ERR_INVALID: max_frames == 0 or above RESTIR_ACCUM_MAX_FRAMES, min_frames > max_frames, unknown flags.  R-MIS /
+ * R-OMIS render whole images; `tile` follows restir_render's rules. */
+typedef struct restir_accum_request {
+    uint32_t flags, min_frames, max_frames, check_every;
+    double   target_mse;
+} restir_accum_request;
+restir_status restir_render_accumulate(restir_ctx* ctx, const restir_camera* cam, const restir_features* features,
+                                       uint32_t width, uint32_t height, const restir_tile* tile,
+                                       const restir_accum_request* req, restir_accum_stats* out_stats /* nullable */,
+                                       float* out_rgb /* nullable */);
+
 /* ---- stage-level access for parity tests and profiling ---------------------------------------------- *
  * Buffers are the device SoA layout (DESIGN.md "Data layout"), one entry per pixel of the computed region
  * (row-major, y = 0 bottom), and for reservoirs [N][pixels]:

@@ -347,6 +347,26 @@ public:
     void writeBitmapToFile(const std::filesystem::path& filePath) {
         check(restir_write_image_bmp(ctx_, filePath.string().c_str()), "restir_write_image_bmp");
     }
+    // Accumulating frames on the device (restir_accum_*): begin an empty state -- a running mean per float of the image
+    // and, with `variance`, the squared deviations the stats need --, add the last image after each render (render with
+    // enable_tone_mapping = 0), resolve the mean as the last image (tone mapped by `tone`'s enable_tone_mapping / gamma /
+    // exposure; nullptr: its own bits), which present / downloadRgba8 / writeBitmapToFile then serve
+    void accumBegin(bool variance = true) { check(restir_accum_begin(ctx_, variance ? RESTIR_ACCUM_VARIANCE : 0u), "restir_accum_begin"); }
+    void accumAdd() { check(restir_accum_add(ctx_), "restir_accum_add"); }
+    void accumResolve(const Features* tone = nullptr) { check(restir_accum_resolve(ctx_, tone), "restir_accum_resolve"); }
+    // needs the variance and two frames; synchronises
+    restir_accum_stats accumStats() {
+        restir_accum_stats s{};
+        check(restir_accum_stats_get(ctx_, &s), "restir_accum_stats_get");
+        return s;
+    }
+    // Test hook (restir_accum_download): the state as it stands, width x height x 3 floats each
+    void accumState(std::vector<float>& mean, std::vector<float>& m2, uint32_t width, uint32_t height) {
+        mean.assign(size_t(width) * height * 3, 0.0f);
+        m2.assign(size_t(width) * height * 3, 0.0f);
+        check(restir_accum_download(ctx_, mean.data(), m2.data(), mean.size()), "restir_accum_download");
+    }
+    void accumEnd() { check(restir_accum_end(ctx_), "restir_accum_end"); }
     restir_ctx* handle() const { return ctx_; }
 
 private:
@@ -394,6 +414,27 @@ inline std::shared_ptr<ReservoirGrid> renderReSTIR(Renderer& r, const std::share
                         prev ? prev->handle() : nullptr, &next, screen.rgb.data()),
           "restir_render");
     return std::make_shared<ReservoirGrid>(next);
+}
+
+// restir_render_accumulate: up to `frames` frames of one view rendered without tone mapping and averaged on the device
+// (with temporal_reuse each frame's grid is the next one's predecessor), the mean tone mapped by `features` into
+// `screen`.  With targetMse > 0 the loop checks the stats after frame minFrames and then every checkEvery frames and
+// stops once est_mse <= targetMse.  Returns the stats (zeros but for the size and the frame count with one frame or
+// without `variance`); the Renderer's accumulation stays open.
+inline restir_accum_stats renderAccumulated(Renderer& r, const Camera& camera, Screen& screen, const Features& features,
+                                            uint32_t frames, double targetMse = 0.0, uint32_t minFrames = 0,
+                                            uint32_t checkEvery = 8, bool variance = true) {
+    restir_accum_request req{};
+    req.flags = variance ? RESTIR_ACCUM_VARIANCE : 0u;
+    req.min_frames = minFrames;
+    req.max_frames = frames;
+    req.check_every = checkEvery;
+    req.target_mse = targetMse;
+    restir_accum_stats stats{};
+    check(restir_render_accumulate(r.handle(), &camera, &features, uint32_t(screen.width), uint32_t(screen.height), nullptr,
+                                   &req, &stats, screen.rgb.data()),
+          "restir_render_accumulate");
+    return stats;
 }
 
 // Motion-compensated temporal reuse (restir_frame_reproject): the predecessor grid `prev`, rendered from prevCamera,

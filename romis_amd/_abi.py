@@ -138,6 +138,22 @@ class SceneInfo(C.Structure):
                 ("light_scale", C.c_float), ("nodes_q_ok", C.c_uint32)]
 
 
+class AccumStats(C.Structure):
+    """restir_accum_stats: what an accumulation's mean still lacks (restir_accum_stats_get)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("frames", C.c_uint32), ("flags", C.c_uint32),
+                ("nonfinite", C.c_uint64), ("est_mse", C.c_double), ("mean_value", C.c_double)]
+
+
+class AccumRequest(C.Structure):
+    """restir_accum_request: how long restir_render_accumulate renders."""
+    _fields_ = [("flags", C.c_uint32), ("min_frames", C.c_uint32), ("max_frames", C.c_uint32),
+                ("check_every", C.c_uint32), ("target_mse", C.c_double)]
+
+
+RESTIR_ACCUM_VARIANCE = 1
+RESTIR_ACCUM_MAX_FRAMES = (1 << 24) - 1
+assert C.sizeof(AccumStats) == 40 and C.sizeof(AccumRequest) == 24
+
 RESTIR_MAX_TILES_X = 16
 RESTIR_MAX_TILES_Y = 16
 
@@ -240,6 +256,17 @@ SIGNATURES = {
     "restir_image_release": (None, [_P]),
     "restir_download_rgba8": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_size_t]),
     "restir_write_image_bmp": (C.c_int, [_P, C.c_char_p]),
+    "restir_accum_begin": (C.c_int, [_P, C.c_uint32]),
+    "restir_accum_add": (C.c_int, [_P]),
+    "restir_accum_resolve": (C.c_int, [_P, C.POINTER(Features)]),
+    "restir_accum_stats_get": (C.c_int, [_P, C.POINTER(AccumStats)]),
+    "restir_accum_download": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]),
+    "restir_accum_end": (C.c_int, [_P]),
+    "restir_accum_fold": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t,
+                                    C.c_uint32]),
+    "restir_render_accumulate": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Features), C.c_uint32, C.c_uint32,
+                                           C.POINTER(Tile), C.POINTER(AccumRequest), C.POINTER(AccumStats),
+                                           C.POINTER(C.c_float)]),
     "restir_stage_configure": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "restir_stage_upload": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     "restir_stage_download": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),

@@ -2277,16 +2277,6 @@ __device__ __forceinline__ uint32_t target_bin(const Bvh& b, v3 y) {
            ((qz & 1u) << 2) | ((qx & 1u) << 1) | (qy & 1u);
 }
 
-// exposureToneMapping (tone_mapping.cpp:8-11) of a finalShading colour; gamma = 1 (the Features default) skips the power
-// (pm_powf(x, 1) == x for every x)
-__device__ __forceinline__ v3 tone_map_rgb(const FeaturesDev& f, v3 color, const GlTabs& tb) {
-    if (!f.tone_map) return color;
-    const float g = 1.0f / f.gamma;
-    v3 e = vscale(mk(-color.x, -color.y, -color.z), f.exposure);
-    v3 mapped = mk(1.0f - gl_expf(tb, e.x), 1.0f - gl_expf(tb, e.y), 1.0f - gl_expf(tb, e.z));
-    return g == 1.0f ? mapped : mk(gl_powf(tb, mapped.x, g), gl_powf(tb, mapped.y, g), gl_powf(tb, mapped.z, g));
-}
-
 // QB: the shadow rays walk the 16-byte nodes (occluded_q, SceneDev::nodes_q; round 6) staged in LDS instead of the
 // 32-byte ones -- the walk is bound by LDS throughput (probes/s6)
 template <bool LDS_BVH, int NT, bool QB = false>

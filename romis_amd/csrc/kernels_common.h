@@ -708,6 +708,16 @@ __device__ __forceinline__ bool work_pixel(const Region& rg, uint32_t item, uint
     return rg.map2d ? tile_pixel_of(rg, item, x, y, p) : region_pixel(rg, item * 256u + threadIdx.x, x, y, p);
 }
 
+// exposureToneMapping (tone_mapping.cpp:8-11) of a finalShading colour; gamma = 1 (the Features default) skips the power
+// (pm_powf(x, 1) == x for every x)
+__device__ __forceinline__ v3 tone_map_rgb(const FeaturesDev& f, v3 color, const GlTabs& tb) {
+    if (!f.tone_map) return color;
+    const float g = 1.0f / f.gamma;
+    v3 e = vscale(mk(-color.x, -color.y, -color.z), f.exposure);
+    v3 mapped = mk(1.0f - gl_expf(tb, e.x), 1.0f - gl_expf(tb, e.y), 1.0f - gl_expf(tb, e.z));
+    return g == 1.0f ? mapped : mk(gl_powf(tb, mapped.x, g), gl_powf(tb, mapped.y, g), gl_powf(tb, mapped.z, g));
+}
+
 }  // namespace romis
 
 using namespace romis;

@@ -4,6 +4,7 @@
 // HIP device + stream, the uploaded scene (materials, lights, flattened BVH) and the per-frame device
 // buffers; every pass is one hand-written gfx950 kernel (kernels.hip) enqueued on the context's stream.
 #include "abi_error.h"
+#include "accum.h"
 #include "layout.h"
 
 #include <rccl/rccl.h>
@@ -335,6 +336,26 @@ struct restir_ctx {
     uint64_t phat_builds = 0;                       // k_phat_table launches (restir_phat_builds)
     int cur = 0;
     uint32_t rgb_w = 0, rgb_h = 0;
+    // Where the last image came from (restir_accum_add folds an image a producer wrote, and each once): rgb_serial counts
+    // the images the producers wrote -- restir_render, the MIS tile renders, restir_halo_end, the stage path's final /
+    // finish kernels and uploads of RESTIR_BUF_RGB --, rgb_from says what `rgb` holds now: nothing, the rgb_serial-th
+    // image, a buffer that has its size but not yet its pixels (restir_halo_begin, restir_stage_configure, a frame
+    // that failed half way), or a restir_accum_resolve's output
+    enum RgbFrom : uint32_t { RGB_NONE = 0, RGB_PRODUCED = 1, RGB_PENDING = 2, RGB_RESOLVED = 3 };
+    uint64_t rgb_serial = 0;
+    uint32_t rgb_from = RGB_NONE;
+    void image_pending(uint32_t w, uint32_t h) { rgb_w = w; rgb_h = h; rgb_from = RGB_PENDING; }
+    void image_produced() { rgb_serial++; rgb_from = RGB_PRODUCED; }
+
+    // accumulating frames (restir_accum_*, accum.h): the state planes, 3 floats per pixel of the first added image, and
+    // the stats kernel's per-block partials.  `open` with frames == 0 holds no buffer yet.  None of the still view's
+    // caches above is named here: no accumulation call touches them.
+    struct {
+        bool open = false;
+        uint32_t flags = 0, frames = 0, width = 0, height = 0;
+        uint64_t added_serial = 0;   // rgb_serial of the last image folded in
+        DevBuf mean, m2, partials;
+    } acc;
 
     // launch-shape knobs (restir_set_tuning)
     Tuning tuning{};
@@ -871,7 +892,7 @@ void restir_destroy(restir_ctx* c) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         for (DevBuf* b : {&c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
-                          &c->rpj_map})
+                          &c->rpj_map, &c->acc.mean, &c->acc.m2, &c->acc.partials})
             b->release();
         drop_shadow_lists(c);
         drop_phat_table(c);
@@ -1491,7 +1512,7 @@ static restir_status render_mis(restir_ctx* c, const restir_camera* cam, const r
     ST_TRY(ensure_work(c, W, H, f.N, true));
     ST_TRY(ensure_mis(c, features, W, H));
     ST_TRY(c->rgb.ensure((size_t)W * H * 12));
-    c->rgb_w = W; c->rgb_h = H;
+    c->image_pending(W, H);
     c->stage_ok = false;   // the stage buffers now hold this render's state
     const CameraDev camd = camera_dev(cam);
     const Region view = make_region(W, H, 0, 0, W, H, 0, 0, W, H);
@@ -1522,6 +1543,7 @@ static restir_status render_mis(restir_ctx* c, const restir_camera* cam, const r
             ST_TRY(save_alphas_visualisation(c, W, H, f.K + 1u));   // render.cpp:227-229
     }
     TIMED(c, RESTIR_K_MIS, launch_mis_finish(W, H, f, c->mis_acc.as<float>(), c->rgb.as<float>(), c->stream));
+    c->image_produced();
     if (out_rgb) {
         HIP_TRY(hipMemcpyAsync(out_rgb, c->rgb.p, (size_t)W * H * 12, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1579,7 +1601,7 @@ static restir_status render_mis_tile(restir_ctx* c, const restir_camera* cam, co
     ST_TRY(ensure_work(c, t.gwidth, t.gheight, f.N, true));
     ST_TRY(ensure_mis(c, features, W, H, t.width, t.height));
     ST_TRY(c->rgb.ensure(opx * 12));
-    c->rgb_w = t.width; c->rgb_h = t.height;
+    c->image_pending(t.width, t.height);
     c->stage_ok = false;   // the stage buffers now hold this render's state
     const CameraDev camd = camera_dev(cam);
     const Region view = make_region(W, H, t.gx0, t.gy0, t.gwidth, t.gheight, t.gx0, t.gy0, t.gwidth, t.gheight);
@@ -1609,6 +1631,7 @@ static restir_status render_mis_tile(restir_ctx* c, const restir_camera* cam, co
                                                      c->tuning, c->stream));
     }
     TIMED(c, RESTIR_K_MIS, launch_mis_finish(mt, f, c->mis_acc.as<float>(), c->rgb.as<float>(), c->stream));
+    c->image_produced();
     if (out_rgb) {
         HIP_TRY(hipMemcpyAsync(out_rgb, c->rgb.p, opx * 12, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2140,7 +2163,7 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
     ST_TRY(ensure_records(c, t.gwidth, t.gheight, fr.N, fr.fb));
     c->stage_ok = false;   // ensure_records re-sized the shared view state: the stage API must be reconfigured
     ST_TRY(fr.fb.rgb().ensure((size_t)t.width * t.height * 12));
-    c->rgb_w = t.width; c->rgb_h = t.height;
+    c->image_pending(t.width, t.height);
 
     fr.camd = camera_dev(cam);
     fr.view = fr.fb.region(make_region(width, height, t.gx0, t.gy0, t.gwidth, t.gheight, t.gx0, t.gy0, t.gwidth, t.gheight));
@@ -2153,6 +2176,7 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
     ST_TRY(fr.alloc(p));
     ST_TRY(fr.ris_stage(p));
     ST_TRY(fr.spatial_passes(p));
+    c->image_produced();   // the last pass wrote the image
     return fr.hand_off(p, out_next, out_rgb);
 }
 
@@ -2574,6 +2598,235 @@ restir_status restir_write_image_bmp(restir_ctx* c, const char* path) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// accumulating frames (include/restir_c.h "accumulating frames", accum.h).  Nothing here reads or writes
+// the still view's caches (gbuf, slists, svis, phat, gbuf_streak): a standing view keeps them while it accumulates.
+static void accum_close(restir_ctx* c) {
+    c->acc.open = false;
+    c->acc.frames = 0;
+    c->acc.mean.release();
+    c->acc.m2.release();
+    c->acc.partials.release();
+}
+
+// the caller holds c->mu
+static restir_status accum_add_locked(restir_ctx* c) {
+    auto& a = c->acc;
+    if (!a.open) return fail(RESTIR_ERR_STATE, "restir_accum_add before restir_accum_begin");
+    if (c->halo.active) return fail(RESTIR_ERR_STATE, "restir_accum_add between restir_halo_begin and restir_halo_end");
+    if (c->rgb_from == restir_ctx::RGB_RESOLVED)
+        return fail(RESTIR_ERR_STATE, "restir_accum_add: the last image is restir_accum_resolve's, not a frame");
+    if (c->rgb_from != restir_ctx::RGB_PRODUCED || (size_t)c->rgb_w * c->rgb_h == 0)
+        return fail(RESTIR_ERR_STATE, "restir_accum_add: nothing rendered yet");
+    if (a.frames > 0 && a.added_serial == c->rgb_serial)
+        return fail(RESTIR_ERR_STATE, "restir_accum_add: the last image was added already");
+    if (a.frames > 0 && (a.width != c->rgb_w || a.height != c->rgb_h))
+        return fail(RESTIR_ERR_STATE, "restir_accum_add: the last image is %ux%u, the accumulation %ux%u", c->rgb_w, c->rgb_h,
+                    a.width, a.height);
+    if (a.frames >= kAccumMaxFrames) return fail(RESTIR_ERR_STATE, "restir_accum_add: %u frames are folded already", a.frames);
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t count = (uint64_t)c->rgb_w * c->rgb_h * 3u;
+    const bool var = (a.flags & RESTIR_ACCUM_VARIANCE) != 0;
+    if (a.frames == 0) {   // the empty state: mean = m2 = 0
+        restir_status st = a.mean.ensure(count * 4);
+        if (st == RESTIR_OK && var) st = a.m2.ensure(count * 4);
+        if (st != RESTIR_OK) { accum_close(c); return st; }
+        HIP_TRY(hipMemsetAsync(a.mean.p, 0, count * 4, c->stream));
+        if (var) HIP_TRY(hipMemsetAsync(a.m2.p, 0, count * 4, c->stream));
+        a.width = c->rgb_w;
+        a.height = c->rgb_h;
+    }
+    const float inv_n = 1.0f / (float)(a.frames + 1u);
+    HIP_TRY(launch_accum_add(c->rgb.as<float>(), a.mean.as<float>(), var ? a.m2.as<float>() : nullptr, count, inv_n, c->stream));
+    a.frames++;
+    a.added_serial = c->rgb_serial;
+    return RESTIR_OK;
+}
+
+static restir_status accum_resolve_locked(restir_ctx* c, const restir_features* tone) {
+    auto& a = c->acc;
+    if (!a.open || a.frames == 0) return fail(RESTIR_ERR_STATE, "restir_accum_resolve: no frame is accumulated");
+    if (c->halo.active) return fail(RESTIR_ERR_STATE, "restir_accum_resolve between restir_halo_begin and restir_halo_end");
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t px = (uint64_t)a.width * a.height;
+    ST_TRY(c->rgb.ensure(px * 12));   // a render of another size may have come between
+    c->image_pending(a.width, a.height);
+    FeaturesDev d{};
+    if (tone) {
+        d.tone_map = tone->enable_tone_mapping;
+        d.gamma = tone->gamma;
+        d.exposure = tone->exposure;
+    }
+    HIP_TRY(launch_accum_resolve(a.mean.as<float>(), c->rgb.as<float>(), px, d, c->stream));
+    c->rgb_from = restir_ctx::RGB_RESOLVED;
+    return RESTIR_OK;
+}
+
+static void accum_stats_header(const restir_ctx* c, restir_accum_stats* out) {
+    *out = restir_accum_stats{};
+    out->width = c->acc.width;
+    out->height = c->acc.height;
+    out->frames = c->acc.frames;
+    out->flags = c->acc.flags;
+}
+
+static restir_status accum_stats_locked(restir_ctx* c, restir_accum_stats* out) {
+    auto& a = c->acc;
+    if (!a.open) return fail(RESTIR_ERR_STATE, "restir_accum_stats_get before restir_accum_begin");
+    if (!(a.flags & RESTIR_ACCUM_VARIANCE)) return fail(RESTIR_ERR_STATE, "restir_accum_stats_get needs RESTIR_ACCUM_VARIANCE");
+    if (a.frames < 2) return fail(RESTIR_ERR_STATE, "restir_accum_stats_get needs two frames, %u are accumulated", a.frames);
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t count = (uint64_t)a.width * a.height * 3u;
+    const uint64_t blocks = accum_stats_blocks(count);
+    ST_TRY(a.partials.ensure(blocks * sizeof(AccumPartial)));
+    const double nn1 = (double)a.frames * (double)(a.frames - 1u);
+    HIP_TRY(launch_accum_stats(a.mean.as<float>(), a.m2.as<float>(), count, nn1, a.partials.as<AccumPartial>(), c->stream));
+    std::vector<AccumPartial> host(blocks);
+    HIP_TRY(hipMemcpyAsync(host.data(), a.partials.p, blocks * sizeof(AccumPartial), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    double term = 0.0, value = 0.0;
+    uint64_t bad = 0;
+    for (const AccumPartial& p : host) {   // in index order
+        term += p.term;
+        value += p.value;
+        bad += p.nonfinite;
+    }
+    accum_stats_header(c, out);
+    out->nonfinite = bad;
+    const double counted = (double)(count - bad);   // 0 counted: 0 / 0, which no target meets
+    out->est_mse = term / counted;
+    out->mean_value = value / counted;
+    return RESTIR_OK;
+}
+
+restir_status restir_accum_begin(restir_ctx* c, uint32_t flags) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (flags & ~RESTIR_ACCUM_VARIANCE) return fail(RESTIR_ERR_INVALID, "restir_accum_begin: unknown flags 0x%x", flags);
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->acc.open = true;
+    c->acc.flags = flags;
+    c->acc.frames = 0;
+    c->acc.width = c->acc.height = 0;
+    c->acc.added_serial = 0;
+    return RESTIR_OK;
+}
+
+restir_status restir_accum_add(restir_ctx* c) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return accum_add_locked(c);
+}
+
+restir_status restir_accum_resolve(restir_ctx* c, const restir_features* tone) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return accum_resolve_locked(c, tone);
+}
+
+restir_status restir_accum_stats_get(restir_ctx* c, restir_accum_stats* out) {
+    if (!c || !out) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return accum_stats_locked(c, out);
+}
+
+restir_status restir_accum_download(restir_ctx* c, float* mean, float* m2, size_t count) {
+    if (!c || !mean) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto& a = c->acc;
+    if (!a.open || a.frames == 0) return fail(RESTIR_ERR_STATE, "restir_accum_download: no frame is accumulated");
+    const size_t need = (size_t)a.width * a.height * 3;
+    if (count < need) return fail(RESTIR_ERR_INVALID, "buffer holds %zu floats, need %zu", count, need);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(mean, a.mean.p, need * 4, hipMemcpyDeviceToHost, c->stream));
+    if (m2) {
+        if (a.flags & RESTIR_ACCUM_VARIANCE)
+            HIP_TRY(hipMemcpyAsync(m2, a.m2.p, need * 4, hipMemcpyDeviceToHost, c->stream));
+        else
+            std::memset(m2, 0, need * 4);
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RESTIR_OK;
+}
+
+restir_status restir_accum_end(restir_ctx* c) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    (void)hipSetDevice(c->device);
+    accum_close(c);   // (hipFree waits for the kernels that use the planes)
+    return RESTIR_OK;
+}
+
+restir_status restir_accum_fold(float* mean, float* m2, const float* x, size_t count, uint32_t n) {
+    if (!mean || !x) return fail(RESTIR_ERR_INVALID, "null argument");
+    if (n == 0 || n > kAccumMaxFrames) return fail(RESTIR_ERR_INVALID, "restir_accum_fold: n = %u outside 1..%u", n, kAccumMaxFrames);
+    const float inv_n = 1.0f / (float)n;
+    if (m2)
+        for (size_t i = 0; i < count; i++) accum_fold_var(x[i], inv_n, mean[i], m2[i]);
+    else
+        for (size_t i = 0; i < count; i++) accum_fold_mean(x[i], inv_n, mean[i]);
+    return RESTIR_OK;
+}
+
+// Every step takes the context's mutex for itself (restir_render's own, then the add's): calls on one context are
+// serialised by the context, and a caller that shares it between threads orders its calls as for any other sequence.
+restir_status restir_render_accumulate(restir_ctx* c, const restir_camera* cam, const restir_features* features, uint32_t width,
+                                       uint32_t height, const restir_tile* tile, const restir_accum_request* req,
+                                       restir_accum_stats* out_stats, float* out_rgb) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (!cam) return fail(RESTIR_ERR_INVALID, "camera is NULL");
+    if (!req) return fail(RESTIR_ERR_INVALID, "request is NULL");
+    ST_TRY(check_features(features));
+    if (req->flags & ~RESTIR_ACCUM_VARIANCE) return fail(RESTIR_ERR_INVALID, "restir_render_accumulate: unknown flags 0x%x", req->flags);
+    if (req->max_frames == 0 || req->max_frames > kAccumMaxFrames)
+        return fail(RESTIR_ERR_INVALID, "restir_render_accumulate: max_frames %u outside 1..%u", req->max_frames, kAccumMaxFrames);
+    if (req->min_frames > req->max_frames)
+        return fail(RESTIR_ERR_INVALID, "restir_render_accumulate: min_frames %u > max_frames %u", req->min_frames, req->max_frames);
+    const bool target = req->target_mse > 0.0;
+    if (target && !(req->flags & RESTIR_ACCUM_VARIANCE))
+        return fail(RESTIR_ERR_INVALID, "restir_render_accumulate: a target needs RESTIR_ACCUM_VARIANCE");
+    if (target && req->check_every == 0) return fail(RESTIR_ERR_INVALID, "restir_render_accumulate: a target needs check_every > 0");
+
+    restir_features f = *features;
+    f.enable_tone_mapping = 0;   // the mean is tone mapped, not the frames
+    const bool chain = f.ray_trace_mode == RESTIR_MODE_RESTIR && f.temporal_reuse;
+    ST_TRY(restir_accum_begin(c, req->flags));
+    restir_frame* prev = nullptr;
+    restir_status st = RESTIR_OK;
+    restir_accum_stats stats{};
+    for (uint32_t n = 1; n <= req->max_frames; n++) {
+        restir_frame* next = nullptr;
+        st = restir_render(c, cam, &f, width, height, tile, prev, chain ? &next : nullptr, nullptr);
+        if (prev) restir_frame_release(prev);
+        prev = next;
+        if (st != RESTIR_OK) break;
+        st = restir_accum_add(c);
+        if (st != RESTIR_OK) break;
+        if (target && n >= 2 && n >= req->min_frames && (n - req->min_frames) % req->check_every == 0) {
+            st = restir_accum_stats_get(c, &stats);
+            if (st != RESTIR_OK || stats.est_mse <= req->target_mse) break;
+        }
+    }
+    if (prev) restir_frame_release(prev);
+    ST_TRY(st);
+    ST_TRY(restir_accum_resolve(c, features));
+    if (out_stats) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        if ((c->acc.flags & RESTIR_ACCUM_VARIANCE) && c->acc.frames >= 2)
+            ST_TRY(accum_stats_locked(c, out_stats));
+        else
+            accum_stats_header(c, out_stats);
+    }
+    if (out_rgb) {
+        size_t count;
+        {
+            std::lock_guard<std::mutex> lk(c->mu);
+            count = (size_t)c->rgb_w * c->rgb_h * 3;
+        }
+        ST_TRY(restir_download_rgb(c, out_rgb, count));
+    }
+    return RESTIR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // stage API (parity tests): a whole width x height image, reservoir slot 0 = "current", slot 1 = "prev"
 restir_status restir_stage_configure(restir_ctx* c, uint32_t width, uint32_t height, uint32_t n) {
     if (!c || width == 0 || height == 0 || n < 1 || n > RESTIR_MAX_N) return fail(RESTIR_ERR_INVALID, "bad stage size");
@@ -2582,7 +2835,7 @@ restir_status restir_stage_configure(restir_ctx* c, uint32_t width, uint32_t hei
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(ensure_work(c, width, height, n, true));
     ST_TRY(c->rgb.ensure((size_t)width * height * 12));
-    c->rgb_w = width; c->rgb_h = height;
+    c->image_pending(width, height);
     c->stage_rg = make_region(width, height, 0, 0, width, height, 0, 0, width, height);
     c->stage_ok = true;
     c->cur = 0;
@@ -2629,6 +2882,7 @@ restir_status restir_stage_upload(restir_ctx* c, restir_buffer which, const void
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyAsync(b->p, host, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (which == RESTIR_BUF_RGB) c->image_produced();
     return RESTIR_OK;
 }
 
@@ -2754,6 +3008,7 @@ restir_status restir_stage_final(restir_ctx* c, const restir_camera* cam, const 
     const CameraDev camd = camera_dev(cam);
     TIMED(c, RESTIR_K_FINAL, launch_final(route_final(sd, c->stage_rg, d, c->tuning, Ask{}), sd, c->stage_rg, d,
                                           stage_bufs(c, camd, 0u, false), c->stream));
+    c->image_produced();
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RESTIR_OK;
 }
@@ -2811,6 +3066,7 @@ restir_status restir_stage_mis_finish(restir_ctx* c, const restir_features* f) {
     ST_TRY(scene_for(c, d, (size_t)c->vw * c->vh, sd));
     if (!c->mis_cap) return fail(RESTIR_ERR_STATE, "MIS buffers: run restir_stage_mis_accumulate first");
     TIMED(c, RESTIR_K_MIS, launch_mis_finish(c->vw, c->vh, d, c->mis_acc.as<float>(), c->rgb.as<float>(), c->stream));
+    c->image_produced();
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RESTIR_OK;
 }
@@ -3124,7 +3380,7 @@ restir_status restir_halo_begin_layout(restir_ctx* c, const restir_camera* cam, 
     h.nranks = tiles_x * tiles_y;
     h.interior_done = false;
     ST_TRY(c->rgb.ensure((size_t)t.width * t.height * 12));
-    c->rgb_w = t.width; c->rgb_h = t.height;
+    c->image_pending(t.width, t.height);
     h.W = width; h.H = height;
     h.view = fb.region(make_region(width, height, t.gx0, t.gy0, t.gwidth, t.gheight, t.gx0, t.gy0, t.gwidth, t.gheight));
     h.owned = fb.region(make_region(width, height, t.gx0, t.gy0, t.gwidth, t.gheight, t.x0, t.y0, t.width, t.height));
@@ -3560,6 +3816,7 @@ restir_status restir_halo_end(restir_ctx* c, restir_frame** out_next, float* out
     LaunchBufs b = fb.bufs(h.camd, 0u, h.cur, h.cur);
     b.flags = h.tmiss;
     TIMED(c, RESTIR_K_FINAL, launch_final(route_final(sd, h.owned, h.f, c->tuning, ask), sd, h.owned, h.f, b, c->stream));
+    c->image_produced();
     c->cur = h.cur;
     h.active = false;
     if (out_next) {

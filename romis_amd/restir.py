@@ -256,6 +256,71 @@ class Renderer:
         """restir_write_image_bmp: the last image as the BMP file Screen::writeBitmapToFile writes."""
         check(self.lib, self.lib.restir_write_image_bmp(self.ctx, os.fsencode(path)), "restir_write_image_bmp")
 
+    # ---- accumulating frames (include/restir_c.h "accumulating frames") -------------------------------
+    def accum_begin(self, variance: bool = True) -> None:
+        """restir_accum_begin: start (or restart) an accumulation with an empty state -- a running mean per float of the
+        image and, with `variance`, the sum of squared deviations the stats need."""
+        check(self.lib, self.lib.restir_accum_begin(self.ctx, _abi.RESTIR_ACCUM_VARIANCE if variance else 0),
+              "restir_accum_begin")
+
+    def accum_add(self) -> None:
+        """restir_accum_add: fold the last image in, on the device; only enqueues.  Render the frames with
+        enable_tone_mapping = 0 and tone map the mean (accum_resolve)."""
+        check(self.lib, self.lib.restir_accum_add(self.ctx), "restir_accum_add")
+
+    def accum_resolve(self, features=None) -> None:
+        """restir_accum_resolve: the mean becomes the last image -- tone mapped by `features`' enable_tone_mapping /
+        gamma / exposure, or its own bits without --, which download_rgb, present, download_rgba8 and write_bmp serve."""
+        check(self.lib, self.lib.restir_accum_resolve(self.ctx, C.byref(features) if features is not None else None),
+              "restir_accum_resolve")
+
+    def accum_stats(self) -> _abi.AccumStats:
+        """restir_accum_stats_get (needs the variance and two frames; synchronises): est_mse, the estimate of
+        E|mean - expectation|^2 per float, mean_value and the nonfinite floats left out of both."""
+        s = _abi.AccumStats()
+        check(self.lib, self.lib.restir_accum_stats_get(self.ctx, C.byref(s)), "restir_accum_stats_get")
+        return s
+
+    def accum_state(self, width: int | None = None, height: int | None = None):
+        """restir_accum_download: (mean, m2), each [height][width][3] float32, as the state stands (m2 zeros for an
+        accumulation without the variance); synchronises.  width x height is the accumulated images' size; without it
+        the size is asked of accum_stats(), which needs the variance and two frames."""
+        if width is None or height is None:
+            s = self.accum_stats()
+            width, height = s.width, s.height
+        mean, m2 = np.zeros((height, width, 3), np.float32), np.zeros((height, width, 3), np.float32)
+        FP = C.POINTER(C.c_float)
+        check(self.lib, self.lib.restir_accum_download(self.ctx, mean.ctypes.data_as(FP), m2.ctypes.data_as(FP), mean.size),
+              "restir_accum_download")
+        return mean, m2
+
+    def accum_end(self) -> None:
+        """restir_accum_end: close the accumulation and free its buffers."""
+        check(self.lib, self.lib.restir_accum_end(self.ctx), "restir_accum_end")
+
+    def render_accumulated(self, camera, width: int, height: int, features, frames: int, target_mse: float = 0.0,
+                           min_frames: int = 0, check_every: int = 8, variance: bool = True, tile=None,
+                           want_rgb: bool = True):
+        """restir_render_accumulate: a fresh accumulation of up to `frames` frames of one view, each rendered without
+        tone mapping and added on the device with no synchronisation between them (with temporal_reuse each frame's grid
+        is the next one's predecessor), then resolved with `features`' tone-mapping fields.  With target_mse > 0 (needs
+        `variance`) the stats are taken after frame min_frames and then every check_every frames and the loop stops once
+        est_mse <= target_mse.  Returns (rgb [h][w][3] of the resolved image or None, AccumStats); the accumulation stays
+        open."""
+        req = _abi.AccumRequest(flags=_abi.RESTIR_ACCUM_VARIANCE if variance else 0, min_frames=min_frames,
+                                max_frames=frames, check_every=check_every, target_mse=target_mse)
+        stats = _abi.AccumStats()
+        rgb = None
+        if want_rgb:
+            h_ = tile.height if tile is not None else height
+            w_ = tile.width if tile is not None else width
+            rgb = np.zeros((h_, w_, 3), np.float32)
+        check(self.lib, self.lib.restir_render_accumulate(
+            self.ctx, C.byref(camera), C.byref(features), width, height, C.byref(tile) if tile is not None else None,
+            C.byref(req), C.byref(stats), rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None),
+            "restir_render_accumulate")
+        return rgb, stats
+
     # ---- halo-mode frames (include/restir_c.h "halo-mode frames") -------------------------------------
     def halo_begin(self, prev, camera, width, height, features, tiles, rank, layout=None):
         """Primary rays on the tile + ring, RIS / temporal on the owned tile.  Returns (send_bytes, recv_bytes).
@@ -558,6 +623,19 @@ class Renderer:
 
 def rng_key(seed: int, frame: int, stage: int, pass_: int = 0) -> int:
     return _abi.load_library().restir_rng_key(seed, frame, stage, pass_)
+
+
+def accum_fold(mean: np.ndarray, m2: np.ndarray | None, x, n: int) -> None:
+    """restir_accum_fold (pure host): fold x into mean (and m2) IN PLACE as the n-th value -- contiguous float32 arrays of
+    one size; the device's own arithmetic, bit for bit."""
+    lib = _abi.load_library()
+    xa = np.ascontiguousarray(x, np.float32)
+    for a in (mean, m2):
+        if a is not None and (a.dtype != np.float32 or not a.flags.c_contiguous or a.size != xa.size):
+            raise ValueError("accum_fold: mean and m2 must be contiguous float32 arrays of x's size")
+    FP = C.POINTER(C.c_float)
+    check(lib, lib.restir_accum_fold(mean.ctypes.data_as(FP), m2.ctypes.data_as(FP) if m2 is not None else None,
+                                     xa.ctypes.data_as(FP), xa.size, n), "restir_accum_fold")
 
 
 def reproject_pixel(prev_cam: _abi.CameraFrame, width: int, height: int, point):
