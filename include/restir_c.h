@@ -519,6 +519,73 @@ restir_status restir_render_accumulate(restir_ctx* ctx, const restir_camera* cam
                                        const restir_accum_request* req, restir_accum_stats* out_stats /* nullable */,
                                        float* out_rgb /* nullable */);
 
+/* ---- the exact direct-lighting image, a kept reference and error figures against it -------------------------
+ * restir_render_exact writes, as the context's image, what every estimator here estimates: per owned pixel, with px the
+ * G-buffer record of `cam` at that pixel exactly as restir_stage_primary gives it,
+ *     color = (+0, +0, +0)
+ *     for i = 0 .. L-1, in light-table order:
+ *         sc = computeShading(features, px, light[i].position, light[i].colour)       shading.cpp:7-34
+ *         if (!testVisibilityLightSample(px.P, light[i].position)) sc = (+0, +0, +0)
+ *         color = color + sc                                     three float32 adds, no contraction
+ *     if (features->enable_tone_mapping) color = exposureToneMapping(color)          tone_mapping.cpp:8-11
+ *     rgb[(rect.h - 1 - (y - rect.y0)) * rect.w + (x - rect.x0)] = color             row 0 = top, as final shading
+ * That is, float32-added in light order, L runs of final shading (render.cpp:45-57) with N = 1, tone mapping off and
+ * every pixel's reservoir set to (position of light i, colour of light i, W = 1, M = 1): 0 + sc 1, / 1 and the running
+ * sum never produce -0, so the bits agree.  A miss pixel follows the same rule (whatever computeShading returns for the
+ * miss material); a scene with no lights gives the tone-mapped +0 image; enable_shading = 0 follows computeShading (kd per
+ * visible light).  Of `features` only enable_shading, enable_texture_mapping, enable_tone_mapping, gamma and exposure
+ * are read: ray_trace_mode and every sampling field are ignored.
+ * Scope: scenes whose lights are all point lights, or that have none, with any L.  A scene with a segment or
+ * parallelogram light is RESTIR_ERR_UNSUPPORTED with a message naming the light type -- an area light's integral is not
+ * a finite sum --, nothing is rendered and the last image is unchanged.  `tile` as restir_render's; the image is
+ * pixel-local, so a tile computes exactly its owned rectangle, with no ghost ring, and stitched tiles are the whole
+ * image bit for bit.  Between restir_halo_begin and restir_halo_end the call is RESTIR_ERR_STATE.
+ * The call is a producer: it writes the context's image and takes a new serial in the accumulator's rule above, so
+ * restir_accum_add, restir_image_begin, restir_download_rgb / _rgba8 and restir_write_image_bmp serve it; with
+ * out_rgb == NULL it only enqueues.  It consumes no frame index and draws no random number, and neither reads nor
+ * writes the kept G-buffer, the tile flags, the shadow lists, the visibility bits, the p-hat table or their streak: it
+ * traces its own G-buffer into scratch planes of its own.  Like restir_render it leaves the stage API unconfigured (the
+ * image buffer has the tile's size now).  Its launches have no RESTIR_K_* slot.
+ * Errors: a NULL argument or an inconsistent tile (RESTIR_ERR_INVALID), a call before restir_set_scene or inside a halo
+ * frame (RESTIR_ERR_STATE) and an unsupported scene are found before anything is written and leave the last image as it
+ * was.  An allocation or a launch the device refuses (RESTIR_ERR_HIP) comes later and may leave the image buffer, as a
+ * frame that failed half way does, with its size but not its pixels: nothing serves or adds it until a producer writes it. */
+restir_status restir_render_exact(restir_ctx* ctx, const restir_camera* cam, const restir_features* features,
+                                  uint32_t width, uint32_t height, const restir_tile* tile /* nullable */,
+                                  float* out_rgb /* nullable, as restir_render's */);
+
+/* A kept reference: restir_reference_set keeps a device copy of the last image -- any producer's, or a resolve's --, 12
+ * bytes per owned pixel; it only enqueues.  The copy is a snapshot: later renders, scene updates, new lights and
+ * accumulations leave it alone; clearing or replacing it is the caller's call.  Which domain it is in, linear or tone
+ * mapped, is the caller's choice: for RESTIR_ERROR_SRC_ACCUM_MEAN render it with enable_tone_mapping = 0, the mean is
+ * linear.
+ * restir_error_get compares a source with the reference on the device and synchronises; nothing leaves the device but
+ * the struct.  Per float, with a the source's and r the reference's value and d = (double)a - (double)r: a float whose
+ * a or r is not finite is left out and counted in `nonfinite`; over the others mse, mae, rel_mse and bias are the means
+ * of d d, |d|, d d / (r r + RESTIR_ERROR_REL_EPS) and d, max_abs the exact maximum of |d|, ref_mean the mean of r (0 / 0
+ * where nothing is counted).  The reduction is deterministic -- block b of 4096 floats, sixteen entries per lane added
+ * in index order in double, a fixed tree over the block's lanes, the blocks' partials added in index order on the
+ * host; no float atomics -- and restir_error_measure (pure host) is the same arithmetic over two arrays, bit for bit.
+ * Every error leaves all state untouched.  RESTIR_ERR_STATE: restir_reference_set without a produced or resolved image, or
+ * between restir_halo_begin and restir_halo_end; restir_error_get without a reference, with a source that is absent (no
+ * image; no open accumulation or no frame in it) or whose size is not the reference's.  RESTIR_ERR_INVALID: a NULL
+ * argument, an unknown source, count == 0.  RESTIR_ERR_HIP: an allocation the device refuses. */
+#define RESTIR_ERROR_SRC_IMAGE      0u   /* the context's last image */
+#define RESTIR_ERROR_SRC_ACCUM_MEAN 1u   /* the open accumulation's mean (linear: compare with a reference rendered without tone mapping) */
+#define RESTIR_ERROR_REL_EPS        1e-2 /* relative MSE's denominator: r*r + eps */
+typedef struct restir_error_stats {
+    uint32_t width, height, source, frames;   /* frames: the accumulation's count, 0 for SRC_IMAGE */
+    uint64_t counted, nonfinite;              /* floats compared / left out because a or r is not finite */
+    double   mse, mae, rel_mse, bias;         /* means over the counted floats of d*d, |d|, d*d/(r*r+eps), d;  d = (double)a - (double)r */
+    double   max_abs;                         /* max |d| over the counted floats, exact */
+    double   ref_mean;                        /* mean of r over the counted floats */
+} restir_error_stats;
+restir_status restir_reference_set(restir_ctx* ctx);     /* keep a device copy of the last image (any producer, or a resolve) as the reference; enqueues */
+restir_status restir_reference_clear(restir_ctx* ctx);   /* frees it; restir_destroy does so too */
+restir_status restir_reference_info(restir_ctx* ctx, uint32_t* width, uint32_t* height, int* present);
+restir_status restir_error_get(restir_ctx* ctx, uint32_t source, restir_error_stats* out);   /* synchronises */
+restir_status restir_error_measure(const float* a, const float* r, size_t count, restir_error_stats* out);   /* pure host, same arithmetic */
+
 /* ---- stage-level access for parity tests and profiling ---------------------------------------------- *
  * Buffers are the device SoA layout (DESIGN.md "Data layout"), one entry per pixel of the computed region
  * (row-major, y = 0 bottom), and for reservoirs [N][pixels]:

@@ -367,6 +367,22 @@ public:
         check(restir_accum_download(ctx_, mean.data(), m2.data(), mean.size()), "restir_accum_download");
     }
     void accumEnd() { check(restir_accum_end(ctx_), "restir_accum_end"); }
+    // The exact direct-lighting image of a point-light scene (restir_render_exact) as the last image: per pixel the
+    // float32 sum over every light, in table order, of computeShading times visibility, tone mapped by `features`.  A
+    // producer like a frame; rgb (nullable): width x height x 3 floats, row 0 = top; nullptr only enqueues
+    void renderExact(const Camera& camera, const Features& features, uint32_t width, uint32_t height, float* rgb = nullptr) {
+        check(restir_render_exact(ctx_, &camera, &features, width, height, nullptr, rgb), "restir_render_exact");
+    }
+    // Keep a device copy of the last image as the reference (a snapshot; referenceClear frees it), and the error figures
+    // of the last image (RESTIR_ERROR_SRC_IMAGE) or the open accumulation's mean (RESTIR_ERROR_SRC_ACCUM_MEAN) against
+    // it, reduced on the device; error() synchronises
+    void referenceSet() { check(restir_reference_set(ctx_), "restir_reference_set"); }
+    void referenceClear() { check(restir_reference_clear(ctx_), "restir_reference_clear"); }
+    restir_error_stats error(uint32_t source = RESTIR_ERROR_SRC_IMAGE) {
+        restir_error_stats s{};
+        check(restir_error_get(ctx_, source, &s), "restir_error_get");
+        return s;
+    }
     restir_ctx* handle() const { return ctx_; }
 
 private:
@@ -435,6 +451,11 @@ inline restir_accum_stats renderAccumulated(Renderer& r, const Camera& camera, S
                                    &req, &stats, screen.rgb.data()),
           "restir_render_accumulate");
     return stats;
+}
+
+// restir_render_exact into `screen`: the exact image every estimator configuration here estimates (point lights only)
+inline void renderExact(Renderer& r, const Camera& camera, Screen& screen, const Features& features) {
+    r.renderExact(camera, features, uint32_t(screen.width), uint32_t(screen.height), screen.rgb.data());
 }
 
 // Motion-compensated temporal reuse (restir_frame_reproject): the predecessor grid `prev`, rendered from prevCamera,

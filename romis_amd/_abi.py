@@ -154,6 +154,19 @@ RESTIR_ACCUM_VARIANCE = 1
 RESTIR_ACCUM_MAX_FRAMES = (1 << 24) - 1
 assert C.sizeof(AccumStats) == 40 and C.sizeof(AccumRequest) == 24
 
+
+class ErrorStats(C.Structure):
+    """restir_error_stats: a source's error figures against the kept reference (restir_error_get, restir_error_measure)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("source", C.c_uint32), ("frames", C.c_uint32),
+                ("counted", C.c_uint64), ("nonfinite", C.c_uint64), ("mse", C.c_double), ("mae", C.c_double),
+                ("rel_mse", C.c_double), ("bias", C.c_double), ("max_abs", C.c_double), ("ref_mean", C.c_double)]
+
+
+RESTIR_ERROR_SRC_IMAGE = 0
+RESTIR_ERROR_SRC_ACCUM_MEAN = 1
+RESTIR_ERROR_REL_EPS = 1e-2
+assert C.sizeof(ErrorStats) == 80
+
 RESTIR_MAX_TILES_X = 16
 RESTIR_MAX_TILES_Y = 16
 
@@ -267,6 +280,13 @@ SIGNATURES = {
     "restir_render_accumulate": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Features), C.c_uint32, C.c_uint32,
                                            C.POINTER(Tile), C.POINTER(AccumRequest), C.POINTER(AccumStats),
                                            C.POINTER(C.c_float)]),
+    "restir_render_exact": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Features), C.c_uint32, C.c_uint32, C.POINTER(Tile),
+                                      C.POINTER(C.c_float)]),
+    "restir_reference_set": (C.c_int, [_P]),
+    "restir_reference_clear": (C.c_int, [_P]),
+    "restir_reference_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "restir_error_get": (C.c_int, [_P, C.c_uint32, C.POINTER(ErrorStats)]),
+    "restir_error_measure": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.POINTER(ErrorStats)]),
     "restir_stage_configure": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "restir_stage_upload": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     "restir_stage_download": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),

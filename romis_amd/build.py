@@ -49,11 +49,12 @@ SOURCES = [("kernels.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS)] + ABI_UNITS +
     ("phat_table.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("present.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("accum.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
+    ("exact.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("bvh.cpp", ["-x", "c++"]),
     ("screen.cpp", ["-x", "c++"]),
 ]
 HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
-           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "shadow_vis.h", "phat_table.h", "abi_error.h", "layout.h", "halo_segs.h", "present.h", "accum.h"]
+           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "shadow_vis.h", "phat_table.h", "abi_error.h", "layout.h", "halo_segs.h", "present.h", "accum.h", "exact.h"]
 
 
 def source_hash() -> str:
@@ -220,7 +221,8 @@ def main(argv=None) -> int:
 # drive (tests/test_cpp_wrapper.py).  Built on the build host next to the library; the GPU box runs the prebuilt ones.
 CPP_PROGRAMS = [("render_scene.cpp", "render_scene"), ("render_threads.cpp", "render_threads"),
                 ("write_outputs.cpp", "write_outputs"), ("update_scene.cpp", "update_scene"),
-                ("present_frames.cpp", "present_frames"), ("accumulate_frames.cpp", "accumulate_frames")]
+                ("present_frames.cpp", "present_frames"), ("accumulate_frames.cpp", "accumulate_frames"),
+                ("exact_image.cpp", "exact_image")]
 CPP_DIR = os.path.join(ROOT, "tests", "cpp")
 
 

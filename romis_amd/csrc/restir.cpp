@@ -5,6 +5,7 @@
 // buffers; every pass is one hand-written gfx950 kernel (kernels.hip) enqueued on the context's stream.
 #include "abi_error.h"
 #include "accum.h"
+#include "exact.h"
 #include "layout.h"
 
 #include <rccl/rccl.h>
@@ -417,6 +418,14 @@ struct restir_ctx {
     double ms[RESTIR_K_COUNT] = {0};
     uint64_t launches[RESTIR_K_COUNT] = {0};
     uint64_t timing_seq[RESTIR_K_COUNT] = {0};   // launches seen per kernel (timing.every sampling)
+
+    // The exact image and the error figures (restir_render_exact, restir_reference_*, restir_error_get; exact.h), behind
+    // everything a frame reads.  restir_render_exact's own scratch: the G-buffer planes of its view -- never the frame
+    // path's planes, so the kept G-buffer and what is built over it stay as they are.  ref: the kept reference, 3 floats
+    // per pixel of the image it was copied from (ref_w x ref_h; no buffer: none), and k_error_stats' partials.
+    DevBuf exact_nt, exact_pm, exact_uv;
+    DevBuf ref, err_partials;
+    uint32_t ref_w = 0, ref_h = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -892,7 +901,8 @@ void restir_destroy(restir_ctx* c) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         for (DevBuf* b : {&c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
-                          &c->rpj_map, &c->acc.mean, &c->acc.m2, &c->acc.partials})
+                          &c->rpj_map, &c->acc.mean, &c->acc.m2, &c->acc.partials, &c->exact_nt, &c->exact_pm, &c->exact_uv,
+                          &c->ref, &c->err_partials})
             b->release();
         drop_shadow_lists(c);
         drop_phat_table(c);
@@ -2823,6 +2833,154 @@ restir_status restir_render_accumulate(restir_ctx* c, const restir_camera* cam, 
         }
         ST_TRY(restir_download_rgb(c, out_rgb, count));
     }
+    return RESTIR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the exact image, the kept reference and the error figures (include/restir_c.h, exact.h, DESIGN.md §6 "Exact image and
+// error figures").  Nothing here reads or writes the frame path's G-buffer planes or what is built over them (gbuf,
+// tmiss, slists, svis, phat, gbuf_streak), the frame index or the stage buffers.
+restir_status restir_render_exact(restir_ctx* c, const restir_camera* cam, const restir_features* features, uint32_t width,
+                                  uint32_t height, const restir_tile* tile, float* out_rgb) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (!cam) return fail(RESTIR_ERR_INVALID, "camera is NULL");
+    if (!features) return fail(RESTIR_ERR_INVALID, "features is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_render_exact before restir_set_scene");
+    if (c->halo.active) return fail(RESTIR_ERR_STATE, "restir_render_exact between restir_halo_begin and restir_halo_end");
+    if (c->sdev.num_lights > 0 && c->sdev.light_types != (1u << RESTIR_LIGHT_POINT)) {
+        const char* what = (c->sdev.light_types & (1u << RESTIR_LIGHT_SEGMENT)) ? "segment" : "parallelogram";
+        return fail(RESTIR_ERR_UNSUPPORTED, "restir_render_exact: the scene holds a %s light; the exact image is the finite sum "
+                                            "over point lights only", what);
+    }
+    restir_tile t;
+    ST_TRY(frame_tile(tile, width, height, 0, t));
+    HIP_TRY(hipSetDevice(c->device));
+
+    // the owned rectangle is the view: the image is pixel-local, a tile's ghost ring is not computed
+    const size_t npx = (size_t)t.width * t.height;
+    ST_TRY(c->exact_nt.ensure(npx * 16));
+    ST_TRY(c->exact_pm.ensure(npx * 16));
+    FeaturesDev f{};
+    f.shading = features->enable_shading;
+    f.texture = features->enable_texture_mapping;
+    f.tone_map = features->enable_tone_mapping;
+    f.gamma = features->gamma;
+    f.exposure = features->exposure;
+    SceneDev s;
+    ST_TRY(scene_for(c, f, npx, s, &c->exact_uv));
+    ST_TRY(c->rgb.ensure(npx * 12));
+    c->image_pending(t.width, t.height);
+    c->stage_ok = false;   // the image buffer has another size now: the stage API must be reconfigured, as after restir_render
+
+    const CameraDev camd = camera_dev(cam);
+    const Region view = make_region(width, height, t.x0, t.y0, t.width, t.height, t.x0, t.y0, t.width, t.height);
+    LaunchBufs b;
+    b.cam = &camd; b.origin = camd.origin;
+    b.n_t = c->exact_nt.as<float4>(); b.p_mat = c->exact_pm.as<float4>();
+    set_launch_events(nullptr, nullptr);   // no RESTIR_K_* slot: restir_timings does not see these launches
+    HIP_TRY(launch_primary(route_primary(s, view, c->tuning), s, view, b, c->stream));
+    HIP_TRY(launch_exact(s, view, f, camd.origin, b.n_t, b.p_mat, c->rgb.as<float>(), c->stream));
+    c->image_produced();
+    if (out_rgb) {
+        HIP_TRY(hipMemcpyAsync(out_rgb, c->rgb.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return RESTIR_OK;
+}
+
+restir_status restir_reference_set(restir_ctx* c) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->halo.active) return fail(RESTIR_ERR_STATE, "restir_reference_set between restir_halo_begin and restir_halo_end");
+    const size_t bytes = (size_t)c->rgb_w * c->rgb_h * 12;
+    if ((c->rgb_from != restir_ctx::RGB_PRODUCED && c->rgb_from != restir_ctx::RGB_RESOLVED) || bytes == 0)
+        return fail(RESTIR_ERR_STATE, "restir_reference_set: nothing rendered yet");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->ref.p || c->ref.bytes < bytes) {   // the old reference stands until the new buffer does
+        DevBuf nb;
+        ST_TRY(nb.ensure(bytes));
+        c->ref.release();
+        c->ref = nb;
+    }
+    c->ref_w = c->rgb_w;
+    c->ref_h = c->rgb_h;
+    HIP_TRY(hipMemcpyAsync(c->ref.p, c->rgb.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return RESTIR_OK;
+}
+
+restir_status restir_reference_clear(restir_ctx* c) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    (void)hipSetDevice(c->device);
+    c->ref.release();   // (hipFree waits for the kernels that read it)
+    c->ref_w = c->ref_h = 0;
+    return RESTIR_OK;
+}
+
+restir_status restir_reference_info(restir_ctx* c, uint32_t* width, uint32_t* height, int* present) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (width) *width = c->ref_w;
+    if (height) *height = c->ref_h;
+    if (present) *present = c->ref.p ? 1 : 0;
+    return RESTIR_OK;
+}
+
+static void error_stats_fill(const ErrorSums& t, restir_error_stats* out) {
+    out->counted = t.counted;
+    out->nonfinite = t.nonfinite;
+    const double n = (double)t.counted;   // 0 counted: 0 / 0
+    out->mse = t.se / n;
+    out->mae = t.ae / n;
+    out->rel_mse = t.rel / n;
+    out->bias = t.d / n;
+    out->max_abs = t.max_abs;
+    out->ref_mean = t.ref / n;
+}
+
+restir_status restir_error_get(restir_ctx* c, uint32_t source, restir_error_stats* out) {
+    if (!c || !out) return fail(RESTIR_ERR_INVALID, "null argument");
+    if (source != RESTIR_ERROR_SRC_IMAGE && source != RESTIR_ERROR_SRC_ACCUM_MEAN)
+        return fail(RESTIR_ERR_INVALID, "restir_error_get: unknown source %u", source);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->ref.p) return fail(RESTIR_ERR_STATE, "restir_error_get before restir_reference_set");
+    const float* a;
+    uint32_t w, h, frames = 0;
+    if (source == RESTIR_ERROR_SRC_IMAGE) {
+        if ((c->rgb_from != restir_ctx::RGB_PRODUCED && c->rgb_from != restir_ctx::RGB_RESOLVED) || (size_t)c->rgb_w * c->rgb_h == 0)
+            return fail(RESTIR_ERR_STATE, "restir_error_get: nothing rendered yet");
+        a = c->rgb.as<float>(); w = c->rgb_w; h = c->rgb_h;
+    } else {
+        if (!c->acc.open || c->acc.frames == 0) return fail(RESTIR_ERR_STATE, "restir_error_get: no frame is accumulated");
+        a = c->acc.mean.as<float>(); w = c->acc.width; h = c->acc.height; frames = c->acc.frames;
+    }
+    if (w != c->ref_w || h != c->ref_h)
+        return fail(RESTIR_ERR_STATE, "restir_error_get: the source is %ux%u, the reference %ux%u", w, h, c->ref_w, c->ref_h);
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t count = (uint64_t)w * h * 3u;
+    const uint64_t blocks = error_blocks(count);
+    ST_TRY(c->err_partials.ensure(blocks * sizeof(ErrorSums)));
+    HIP_TRY(launch_error_stats(a, c->ref.as<float>(), count, c->err_partials.as<ErrorSums>(), c->stream));
+    std::vector<ErrorSums> host(blocks);
+    HIP_TRY(hipMemcpyAsync(host.data(), c->err_partials.p, blocks * sizeof(ErrorSums), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    ErrorSums total;
+    error_zero(total);
+    for (const ErrorSums& p : host) error_merge(total, p);   // in index order
+    *out = restir_error_stats{};
+    out->width = w; out->height = h; out->source = source; out->frames = frames;
+    error_stats_fill(total, out);
+    return RESTIR_OK;
+}
+
+restir_status restir_error_measure(const float* a, const float* r, size_t count, restir_error_stats* out) {
+    if (!a || !r || !out) return fail(RESTIR_ERR_INVALID, "null argument");
+    if (count == 0) return fail(RESTIR_ERR_INVALID, "restir_error_measure: count is 0");
+    ErrorSums total;
+    error_measure_host(a, r, count, total);
+    *out = restir_error_stats{};
+    error_stats_fill(total, out);
     return RESTIR_OK;
 }
 

@@ -321,6 +321,47 @@ class Renderer:
             "restir_render_accumulate")
         return rgb, stats
 
+    # ---- the exact image and error figures (include/restir_c.h "the exact direct-lighting image") ------
+    def render_exact(self, camera, width: int, height: int, features, tile=None, download: bool = True):
+        """restir_render_exact: the exact direct-lighting image of a point-light scene -- per pixel the float32 sum, in
+        light-table order, of computeShading times visibility over every light, tone mapped by `features` -- written as
+        the context's image (a producer: accum_add, present, download_rgb and write_bmp serve it).  Only `features`'
+        shading, texture and tone-mapping fields are read; no frame index is consumed.  Returns rgb [h][w][3] (row 0 =
+        top) of the tile's owned rectangle, or None with download=False, which only enqueues."""
+        rgb = None
+        if download:
+            h_ = tile.height if tile is not None else height
+            w_ = tile.width if tile is not None else width
+            rgb = np.zeros((h_, w_, 3), np.float32)
+        check(self.lib, self.lib.restir_render_exact(
+            self.ctx, C.byref(camera), C.byref(features), width, height, C.byref(tile) if tile is not None else None,
+            rgb.ctypes.data_as(C.POINTER(C.c_float)) if download else None), "restir_render_exact")
+        return rgb
+
+    def reference_set(self) -> None:
+        """restir_reference_set: keep a device copy of the last image as the reference error() compares with; enqueues."""
+        check(self.lib, self.lib.restir_reference_set(self.ctx), "restir_reference_set")
+
+    def reference_clear(self) -> None:
+        """restir_reference_clear: free the kept reference."""
+        check(self.lib, self.lib.restir_reference_clear(self.ctx), "restir_reference_clear")
+
+    def reference_info(self):
+        """restir_reference_info: (width, height, present) of the kept reference."""
+        w, h, present = C.c_uint32(), C.c_uint32(), C.c_int()
+        check(self.lib, self.lib.restir_reference_info(self.ctx, C.byref(w), C.byref(h), C.byref(present)),
+              "restir_reference_info")
+        return w.value, h.value, bool(present.value)
+
+    def error(self, source: str | int = "image") -> _abi.ErrorStats:
+        """restir_error_get (synchronises): true MSE, MAE, relative MSE, bias and the largest deviation of the last image
+        ("image") or of the open accumulation's mean ("accum") against the kept reference, reduced on the device."""
+        src = {"image": _abi.RESTIR_ERROR_SRC_IMAGE, "accum": _abi.RESTIR_ERROR_SRC_ACCUM_MEAN}[source] \
+            if isinstance(source, str) else int(source)
+        s = _abi.ErrorStats()
+        check(self.lib, self.lib.restir_error_get(self.ctx, src, C.byref(s)), "restir_error_get")
+        return s
+
     # ---- halo-mode frames (include/restir_c.h "halo-mode frames") -------------------------------------
     def halo_begin(self, prev, camera, width, height, features, tiles, rank, layout=None):
         """Primary rays on the tile + ring, RIS / temporal on the owned tile.  Returns (send_bytes, recv_bytes).
@@ -636,6 +677,20 @@ def accum_fold(mean: np.ndarray, m2: np.ndarray | None, x, n: int) -> None:
     FP = C.POINTER(C.c_float)
     check(lib, lib.restir_accum_fold(mean.ctypes.data_as(FP), m2.ctypes.data_as(FP) if m2 is not None else None,
                                      xa.ctypes.data_as(FP), xa.size, n), "restir_accum_fold")
+
+
+def error_measure(a, r) -> _abi.ErrorStats:
+    """restir_error_measure (pure host): the error figures of array a against the reference r -- float32 arrays of one
+    size -- by the device reduction's own arithmetic and order, bit for bit (width, height, source and frames are 0)."""
+    lib = _abi.load_library()
+    aa, ra = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(r, np.float32)
+    if aa.size != ra.size:
+        raise ValueError("error_measure: a and r must have one size")
+    FP = C.POINTER(C.c_float)
+    s = _abi.ErrorStats()
+    check(lib, lib.restir_error_measure(aa.ctypes.data_as(FP), ra.ctypes.data_as(FP), aa.size, C.byref(s)),
+          "restir_error_measure")
+    return s
 
 
 def reproject_pixel(prev_cam: _abi.CameraFrame, width: int, height: int, point):
