@@ -586,6 +586,65 @@ restir_status restir_reference_info(restir_ctx* ctx, uint32_t* width, uint32_t* 
 restir_status restir_error_get(restir_ctx* ctx, uint32_t source, restir_error_stats* out);   /* synchronises */
 restir_status restir_error_measure(const float* a, const float* r, size_t count, restir_error_stats* out);   /* pure host, same arithmetic */
 
+/* ---- denoising the last image: an edge-avoiding a-trous wavelet filter guided by the G-buffer ---------------
+ * restir_denoise filters the context's last image in place (Dammertz et al. 2010, geometry terms only: no colour or
+ * luminance term).  Every step below is one float32 operation without contraction, divide and sqrt correctly rounded;
+ * restir_denoise_host (pure host) is the same arithmetic over arrays, bit for bit.
+ * Inputs: the image c (w x h float3, row 0 = top) and the G-buffer of the same rectangle exactly as
+ * restir_stage_primary gives it: n_t = (N unnormalised, t), p_mat = (P, bits(material)), row y = 0 at the bottom -- the
+ * image row of G-buffer row y is h - 1 - y.
+ * Per pixel, once:  l2 = (N.x N.x + N.y N.y) + N.z N.z;  the pixel is flat when its material is the miss material
+ * (num_materials - 1), or !(l2 > 0), or l2 is not finite;  otherwise g = N / sqrt(l2), component by component.
+ * Levels i = 0 .. iterations - 1 with step s = 2^i, each reading the level before.  For pixel p:
+ *     sw = +0, sc = (+0, +0, +0)
+ *     for dy = -2 .. 2 (image rows), for dx = -2 .. 2:   q = p + s (dx, dy),  h = k[dy] k[dx],  k = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *         q outside the image, or c_q with a component that is not finite: skipped
+ *         q == p:  w = h                                          (no edge term: sw >= 9/64)
+ *         else:    skipped unless material(q) == material(p) as 32-bit patterns;
+ *                  both flat: w = h;  exactly one flat: skipped;  neither:
+ *                      cn = (g_p.x g_q.x + g_p.y g_q.y) + g_p.z g_q.z;  cn = cn > 0 ? cn : 0;  cn = cn cn, normal_power_log2 times
+ *                      d = P_q - P_p;  e = (g_p.x d.x + g_p.y d.y) + g_p.z d.z
+ *                      inv_s = 1.0f / (sigma_plane t_p);  r = e inv_s;  wp = 1.0f - r r;  w = h (cn wp)
+ *                  skipped unless w > 0 (a NaN fails the test)
+ *         sw = sw + w;  sc.j = sc.j + w c_q.j
+ *     out.j = sc.j / sw
+ * A pixel whose own colour is not finite keeps its input's bits at every level.  After the last level restir_denoise
+ * applies exposureToneMapping (the final kernels' own) when `tone` asks for it; of `tone` only enable_tone_mapping, gamma
+ * and exposure are read, NULL is no tone mapping.  The viewer's loop: render with enable_tone_mapping = 0, denoise with
+ * the tone fields, present.  restir_denoise_host has no tone-mapping step; its `out` must not overlap its inputs.
+ * The image is any producer's (a frame, an exact image, an upload of RESTIR_BUF_RGB) or a resolve's, an earlier
+ * restir_denoise's included.  `tile` follows restir_render_exact's rules; the owned rectangle must have the image's size.
+ * Taps outside the owned rectangle are skipped like taps outside the image: an image denoised tile by tile differs from
+ * the whole image's within 2 (2^iterations - 1) pixels of a seam.
+ * The result is marked like restir_accum_resolve's: downloads, presentation, restir_write_image_bmp,
+ * restir_reference_set, restir_error_get(RESTIR_ERROR_SRC_IMAGE) and another restir_denoise serve it, restir_accum_add
+ * refuses it (RESTIR_ERR_STATE).  With out_rgb == NULL the call only enqueues.
+ * Towards frame state the call behaves like restir_render_exact: it traces its own guides into scratch planes of its
+ * own, consumes no frame index and neither reads nor writes the kept G-buffer, the tile flags, the shadow lists, the
+ * visibility bits, the p-hat table or their streak; it leaves the stage API unconfigured; its launches have no
+ * RESTIR_K_* slot.  The guides are kept and reused while the camera, width, height, tile and the scene's geometry are
+ * unchanged: restir_set_scene and restir_update_meshes drop them, restir_set_lights does not;
+ * restir_denoise_guide_builds counts the traces.
+ * Errors are found before anything is written and leave the image as it was.  RESTIR_ERR_INVALID: a NULL argument (ctx,
+ * camera, params), parameters out of range, an inconsistent tile.  RESTIR_ERR_STATE: no scene, no image, an owned
+ * rectangle that has not the image's size, a call between restir_halo_begin and restir_halo_end. */
+#define RESTIR_DENOISE_MAX_ITERATIONS 5u
+typedef struct restir_denoise_params {
+    uint32_t iterations;         /* 1 .. RESTIR_DENOISE_MAX_ITERATIONS; the filter's reach is 2 (2^iterations - 1) pixels.  The default is 2:
+                                  * at 1920 x 1080 a third level blurs the lighting itself and every error figure rises again
+                                  * (README "Denoising a frame") */
+    uint32_t normal_power_log2;  /* 0 .. 7: the normal term is max(g_p . g_q, 0)^(2^normal_power_log2) */
+    float    sigma_plane;        /* finite, > 0: the plane term's support as a fraction of the view distance t */
+    uint32_t flags;              /* 0 */
+} restir_denoise_params;
+void restir_denoise_params_default(restir_denoise_params* out);   /* 2, 5, 0.01f, 0 */
+restir_status restir_denoise(restir_ctx* ctx, const restir_camera* cam, uint32_t width, uint32_t height,
+                             const restir_tile* tile /* nullable */, const restir_denoise_params* params,
+                             const restir_features* tone /* nullable */, float* out_rgb /* nullable */);
+restir_status restir_denoise_host(const float* rgb, const float* n_t, const float* p_mat, uint32_t w, uint32_t h,
+                                  uint32_t miss_material, const restir_denoise_params* params, float* out);   /* pure host, same arithmetic */
+restir_status restir_denoise_guide_builds(restir_ctx* ctx, uint64_t* out);   /* guide traces so far */
+
 /* ---- stage-level access for parity tests and profiling ---------------------------------------------- *
  * Buffers are the device SoA layout (DESIGN.md "Data layout"), one entry per pixel of the computed region
  * (row-major, y = 0 bottom), and for reservoirs [N][pixels]:

@@ -42,6 +42,11 @@ struct Features : restir_features {
     Features() { restir_features_default(this); }
 };
 
+// restir_denoise_params with its defaults (2 levels, normal exponent 2^5, plane support 0.01 t)
+struct DenoiseParams : restir_denoise_params {
+    DenoiseParams() { restir_denoise_params_default(this); }
+};
+
 // The reference's own struct Features (src/utils/common.h:89-136) -> Features, field by field by the reference's
 // member names (any type with those members works, so the reference's header is not needed here).  The enums
 // keep their values: RayTraceMode {ReSTIR, RMIS, ROMIS} (common.h:25-29) = restir_mode,
@@ -383,6 +388,19 @@ public:
         check(restir_error_get(ctx_, source, &s), "restir_error_get");
         return s;
     }
+    // The edge-avoiding a-trous filter over the last image, in place (restir_denoise): guided by the normal, position and
+    // material of camera's G-buffer, traced once per view and kept.  tone (nullable): its tone-mapping fields are applied
+    // after the last level -- render with enable_tone_mapping = 0, denoise with the tone fields, present.  The result is
+    // marked like a resolve.  rgb (nullable): width x height x 3 floats, row 0 = top; nullptr only enqueues
+    void denoise(const Camera& camera, uint32_t width, uint32_t height, const DenoiseParams& params = DenoiseParams(),
+                 const Features* tone = nullptr, float* rgb = nullptr) {
+        check(restir_denoise(ctx_, &camera, width, height, nullptr, &params, tone, rgb), "restir_denoise");
+    }
+    uint64_t denoiseGuideBuilds() const {
+        uint64_t n = 0;
+        check(restir_denoise_guide_builds(ctx_, &n), "restir_denoise_guide_builds");
+        return n;
+    }
     restir_ctx* handle() const { return ctx_; }
 
 private:
@@ -451,6 +469,19 @@ inline restir_accum_stats renderAccumulated(Renderer& r, const Camera& camera, S
                                    &req, &stats, screen.rgb.data()),
           "restir_render_accumulate");
     return stats;
+}
+
+// restir_denoise_host: Renderer::denoise's arithmetic on the host, bit for bit, without the tone-mapping step.  rgb: w x h x
+// 3 floats, row 0 = top; n_t, p_mat: w x h x 4 floats as restir_stage_primary gives them (row y = 0 at the bottom);
+// missMaterial: the scene's material count (the miss material's index)
+inline std::vector<float> denoiseHost(const std::vector<float>& rgb, const std::vector<float>& n_t, const std::vector<float>& p_mat,
+                                      uint32_t w, uint32_t h, uint32_t missMaterial, const DenoiseParams& params = DenoiseParams()) {
+    const size_t npx = size_t(w) * h;
+    if (rgb.size() != 3 * npx || n_t.size() != 4 * npx || p_mat.size() != 4 * npx)
+        throw std::runtime_error("denoiseHost: rgb, n_t and p_mat must hold 3, 4 and 4 floats per pixel");
+    std::vector<float> out(3 * npx);
+    check(restir_denoise_host(rgb.data(), n_t.data(), p_mat.data(), w, h, missMaterial, &params, out.data()), "restir_denoise_host");
+    return out;
 }
 
 // restir_render_exact into `screen`: the exact image every estimator configuration here estimates (point lights only)

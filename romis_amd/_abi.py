@@ -167,6 +167,16 @@ RESTIR_ERROR_SRC_ACCUM_MEAN = 1
 RESTIR_ERROR_REL_EPS = 1e-2
 assert C.sizeof(ErrorStats) == 80
 
+
+class DenoiseParams(C.Structure):
+    """restir_denoise_params: the a-trous filter's levels, normal exponent (as log2) and plane-term support."""
+    _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_plane", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+RESTIR_DENOISE_MAX_ITERATIONS = 5
+assert C.sizeof(DenoiseParams) == 16
+
 RESTIR_MAX_TILES_X = 16
 RESTIR_MAX_TILES_Y = 16
 
@@ -287,6 +297,12 @@ SIGNATURES = {
     "restir_reference_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "restir_error_get": (C.c_int, [_P, C.c_uint32, C.POINTER(ErrorStats)]),
     "restir_error_measure": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.POINTER(ErrorStats)]),
+    "restir_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
+    "restir_denoise": (C.c_int, [_P, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(Tile), C.POINTER(DenoiseParams),
+                                 C.POINTER(Features), C.POINTER(C.c_float)]),
+    "restir_denoise_host": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.POINTER(DenoiseParams), C.POINTER(C.c_float)]),
+    "restir_denoise_guide_builds": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "restir_stage_configure": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "restir_stage_upload": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     "restir_stage_download": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),

@@ -5,6 +5,7 @@
 // buffers; every pass is one hand-written gfx950 kernel (kernels.hip) enqueued on the context's stream.
 #include "abi_error.h"
 #include "accum.h"
+#include "denoise.h"
 #include "exact.h"
 #include "layout.h"
 
@@ -40,6 +41,7 @@
 
 namespace romis {
 bool write_bmp_words(const char* path, uint32_t width, uint32_t height, const uint32_t* words);   // screen.cpp
+restir_status denoise_params_check(const restir_denoise_params* p, const char* who);               // denoise_host.cpp
 }
 using namespace romis;
 
@@ -426,6 +428,19 @@ struct restir_ctx {
     DevBuf exact_nt, exact_pm, exact_uv;
     DevBuf ref, err_partials;
     uint32_t ref_w = 0, ref_h = 0;
+
+    // restir_denoise (denoise.h), behind everything a frame reads like the exact image: the planes of its own view --
+    // dn_nt (.., t), dn_pf (P, flat), dn_ga (g, material), dn_uv what the primary kernel writes for a textured scene --
+    // valid for the view dn_key names, and the two images its levels alternate between.
+    DevBuf dn_nt, dn_pf, dn_ga, dn_uv, dn_tmp[2];
+    struct DenoiseKey {
+        bool valid = false;
+        uint64_t geom_gen = 0;
+        uint32_t cam[9] = {};                      // CameraDev: quat, origin, half_w, half_h, as bits
+        uint32_t width = 0, height = 0;
+        restir_tile tile{};
+    } dn_key;
+    uint64_t dn_guide_builds = 0;                   // guide traces (restir_denoise_guide_builds)
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -902,7 +917,7 @@ void restir_destroy(restir_ctx* c) {
         (void)hipStreamSynchronize(c->stream);
         for (DevBuf* b : {&c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
                           &c->rpj_map, &c->acc.mean, &c->acc.m2, &c->acc.partials, &c->exact_nt, &c->exact_pm, &c->exact_uv,
-                          &c->ref, &c->err_partials})
+                          &c->ref, &c->err_partials, &c->dn_nt, &c->dn_pf, &c->dn_ga, &c->dn_uv, &c->dn_tmp[0], &c->dn_tmp[1]})
             b->release();
         drop_shadow_lists(c);
         drop_phat_table(c);
@@ -2624,7 +2639,7 @@ static restir_status accum_add_locked(restir_ctx* c) {
     if (!a.open) return fail(RESTIR_ERR_STATE, "restir_accum_add before restir_accum_begin");
     if (c->halo.active) return fail(RESTIR_ERR_STATE, "restir_accum_add between restir_halo_begin and restir_halo_end");
     if (c->rgb_from == restir_ctx::RGB_RESOLVED)
-        return fail(RESTIR_ERR_STATE, "restir_accum_add: the last image is restir_accum_resolve's, not a frame");
+        return fail(RESTIR_ERR_STATE, "restir_accum_add: the last image is restir_accum_resolve's or restir_denoise's, not a frame");
     if (c->rgb_from != restir_ctx::RGB_PRODUCED || (size_t)c->rgb_w * c->rgb_h == 0)
         return fail(RESTIR_ERR_STATE, "restir_accum_add: nothing rendered yet");
     if (a.frames > 0 && a.added_serial == c->rgb_serial)
@@ -2981,6 +2996,103 @@ restir_status restir_error_measure(const float* a, const float* r, size_t count,
     error_measure_host(a, r, count, total);
     *out = restir_error_stats{};
     error_stats_fill(total, out);
+    return RESTIR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// denoising the last image (include/restir_c.h "denoising the last image", denoise.h, DESIGN.md §6 "Denoising a frame").
+// Like the exact image, nothing here reads or writes the frame path's G-buffer planes or what is built over them, the
+// frame index or the stage buffers.
+restir_status restir_denoise(restir_ctx* c, const restir_camera* cam, uint32_t width, uint32_t height, const restir_tile* tile,
+                             const restir_denoise_params* params, const restir_features* tone, float* out_rgb) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (!cam) return fail(RESTIR_ERR_INVALID, "camera is NULL");
+    ST_TRY(denoise_params_check(params, "restir_denoise"));
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_denoise before restir_set_scene");
+    if (c->halo.active) return fail(RESTIR_ERR_STATE, "restir_denoise between restir_halo_begin and restir_halo_end");
+    restir_tile t;
+    ST_TRY(frame_tile(tile, width, height, 0, t));
+    if ((c->rgb_from != restir_ctx::RGB_PRODUCED && c->rgb_from != restir_ctx::RGB_RESOLVED) || (size_t)c->rgb_w * c->rgb_h == 0)
+        return fail(RESTIR_ERR_STATE, "restir_denoise: nothing rendered yet");
+    if (t.width != c->rgb_w || t.height != c->rgb_h)
+        return fail(RESTIR_ERR_STATE, "restir_denoise: the last image is %ux%u, the owned rectangle %ux%u", c->rgb_w, c->rgb_h,
+                    t.width, t.height);
+    HIP_TRY(hipSetDevice(c->device));
+
+    const size_t npx = (size_t)t.width * t.height;
+    const CameraDev camd = camera_dev(cam);
+    restir_ctx::DenoiseKey want;
+    want.valid = true;
+    want.geom_gen = c->geom_gen;
+    const float camf[9] = {camd.quat.x, camd.quat.y, camd.quat.z, camd.quat.w, camd.origin[0], camd.origin[1], camd.origin[2],
+                           camd.half_w, camd.half_h};
+    std::memcpy(want.cam, camf, sizeof(want.cam));
+    want.width = width; want.height = height;
+    want.tile = t;
+    const restir_ctx::DenoiseKey& have = c->dn_key;
+    const bool keep = have.valid && have.geom_gen == want.geom_gen && !std::memcmp(have.cam, want.cam, sizeof(have.cam)) &&
+                      have.width == want.width && have.height == want.height && !std::memcmp(&have.tile, &want.tile, sizeof(restir_tile));
+    // every buffer first: a refused allocation leaves the image as it was
+    const uint32_t levels = params->iterations;
+    if (!keep) {
+        c->dn_key.valid = false;
+        ST_TRY(c->dn_nt.ensure(npx * 16));
+        ST_TRY(c->dn_pf.ensure(npx * 16));
+        ST_TRY(c->dn_ga.ensure(npx * 16));
+    }
+    ST_TRY(c->dn_tmp[0].ensure(npx * 12));
+    if (levels > 2u) ST_TRY(c->dn_tmp[1].ensure(npx * 12));
+    set_launch_events(nullptr, nullptr);   // no RESTIR_K_* slot: restir_timings does not see these launches
+    if (!keep) {
+        FeaturesDev f{};
+        SceneDev s;
+        ST_TRY(scene_for(c, f, npx, s, &c->dn_uv));
+        const Region view = make_region(width, height, t.x0, t.y0, t.width, t.height, t.x0, t.y0, t.width, t.height);
+        LaunchBufs b;
+        b.cam = &camd; b.origin = camd.origin;
+        b.n_t = c->dn_nt.as<float4>(); b.p_mat = c->dn_pf.as<float4>();
+        HIP_TRY(launch_primary(route_primary(s, view, c->tuning), s, view, b, c->stream));
+        HIP_TRY(launch_denoise_guides(b.n_t, b.p_mat, c->dn_ga.as<float4>(), npx, s.num_materials - 1u, c->stream));
+        c->dn_key = want;
+        c->dn_guide_builds++;
+    }
+    c->stage_ok = false;   // like restir_render_exact: the stage API is to be configured again
+
+    FeaturesDev tf{};
+    if (tone) {
+        tf.tone_map = tone->enable_tone_mapping;
+        tf.gamma = tone->gamma;
+        tf.exposure = tone->exposure;
+    }
+    // level 0 reads the image (a copy of it when it is the last level too), level i the level before, the last writes
+    // the image: rgb -> tmp0 -> tmp1 -> tmp0 -> ... -> rgb
+    float* rgb = c->rgb.as<float>();
+    const float* in = rgb;
+    c->rgb_from = restir_ctx::RGB_PENDING;   // (a launch the device refuses leaves the buffer without an image)
+    if (levels == 1u) {
+        HIP_TRY(hipMemcpyAsync(c->dn_tmp[0].p, rgb, npx * 12, hipMemcpyDeviceToDevice, c->stream));
+        in = c->dn_tmp[0].as<float>();
+    }
+    for (uint32_t level = 0; level < levels; level++) {
+        const bool last = level + 1u == levels;
+        float* out = last ? rgb : c->dn_tmp[level & 1u].as<float>();
+        HIP_TRY(launch_denoise_level(in, out, c->dn_nt.as<float4>(), c->dn_ga.as<float4>(), c->dn_pf.as<float4>(), t.width, t.height,
+                                     level, params->normal_power_log2, params->sigma_plane, last ? &tf : nullptr, c->stream));
+        in = out;
+    }
+    c->rgb_from = restir_ctx::RGB_RESOLVED;
+    if (out_rgb) {
+        HIP_TRY(hipMemcpyAsync(out_rgb, c->rgb.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return RESTIR_OK;
+}
+
+restir_status restir_denoise_guide_builds(restir_ctx* c, uint64_t* out) {
+    if (!c || !out) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->dn_guide_builds;
     return RESTIR_OK;
 }
 

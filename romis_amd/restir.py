@@ -362,6 +362,33 @@ class Renderer:
         check(self.lib, self.lib.restir_error_get(self.ctx, src, C.byref(s)), "restir_error_get")
         return s
 
+    # ---- denoising the last image (include/restir_c.h "denoising the last image") ----------------------
+    def denoise(self, camera, width: int, height: int, tile=None, params=None, tone=None, download: bool = True):
+        """restir_denoise: the edge-avoiding a-trous filter over the context's last image, in place, guided by the
+        normal, position and material of `camera`'s G-buffer (traced once per view and kept).  params: a
+        DenoiseParams (None: the defaults); tone: a Features whose tone-mapping fields are applied after the last level
+        (None: none).  The result is marked like a resolve: present, download_rgb, write_bmp, reference_set and error
+        serve it, accum_add refuses it.  Returns rgb [h][w][3] (row 0 = top) of the tile's owned rectangle, or None
+        with download=False, which only enqueues."""
+        if params is None:
+            params = denoise_params()
+        rgb = None
+        if download:
+            h_ = tile.height if tile is not None else height
+            w_ = tile.width if tile is not None else width
+            rgb = np.zeros((h_, w_, 3), np.float32)
+        check(self.lib, self.lib.restir_denoise(
+            self.ctx, C.byref(camera), width, height, C.byref(tile) if tile is not None else None, C.byref(params),
+            C.byref(tone) if tone is not None else None,
+            rgb.ctypes.data_as(C.POINTER(C.c_float)) if download else None), "restir_denoise")
+        return rgb
+
+    def denoise_guide_builds(self) -> int:
+        """restir_denoise_guide_builds: how often denoise() traced its guides (a still view traces them once)."""
+        n = C.c_uint64()
+        check(self.lib, self.lib.restir_denoise_guide_builds(self.ctx, C.byref(n)), "restir_denoise_guide_builds")
+        return n.value
+
     # ---- halo-mode frames (include/restir_c.h "halo-mode frames") -------------------------------------
     def halo_begin(self, prev, camera, width, height, features, tiles, rank, layout=None):
         """Primary rays on the tile + ring, RIS / temporal on the owned tile.  Returns (send_bytes, recv_bytes).
@@ -691,6 +718,42 @@ def error_measure(a, r) -> _abi.ErrorStats:
     check(lib, lib.restir_error_measure(aa.ctypes.data_as(FP), ra.ctypes.data_as(FP), aa.size, C.byref(s)),
           "restir_error_measure")
     return s
+
+
+def denoise_params(iterations: int | None = None, normal_power_log2: int | None = None,
+                   sigma_plane: float | None = None) -> _abi.DenoiseParams:
+    """restir_denoise_params_default, with the given fields replaced."""
+    lib = _abi.load_library()
+    p = _abi.DenoiseParams()
+    lib.restir_denoise_params_default(C.byref(p))
+    if iterations is not None:
+        p.iterations = iterations
+    if normal_power_log2 is not None:
+        p.normal_power_log2 = normal_power_log2
+    if sigma_plane is not None:
+        p.sigma_plane = sigma_plane
+    return p
+
+
+def denoise_host(rgb, n_t, p_mat, miss_material: int, params=None) -> np.ndarray:
+    """restir_denoise_host (pure host): Renderer.denoise's arithmetic, bit for bit, without the tone-mapping step.  rgb
+    [h][w][3] (row 0 = top); n_t, p_mat [h][w][4] or [h * w][4] as stage_primary gives them (row y = 0 at the bottom,
+    p_mat's w the material's bits); miss_material: the scene's num_materials - 1.  Returns the filtered [h][w][3]."""
+    lib = _abi.load_library()
+    c = np.ascontiguousarray(rgb, np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("denoise_host: rgb must be [h][w][3]")
+    h, w = c.shape[:2]
+    nt, pm = np.ascontiguousarray(n_t, np.float32), np.ascontiguousarray(p_mat, np.float32)
+    if nt.size != 4 * w * h or pm.size != 4 * w * h:
+        raise ValueError("denoise_host: n_t and p_mat must hold 4 floats per pixel of rgb")
+    if params is None:
+        params = denoise_params()
+    out = np.zeros_like(c)
+    FP = C.POINTER(C.c_float)
+    check(lib, lib.restir_denoise_host(c.ctypes.data_as(FP), nt.ctypes.data_as(FP), pm.ctypes.data_as(FP), w, h,
+                                       miss_material, C.byref(params), out.ctypes.data_as(FP)), "restir_denoise_host")
+    return out
 
 
 def reproject_pixel(prev_cam: _abi.CameraFrame, width: int, height: int, point):
