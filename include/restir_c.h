@@ -643,7 +643,82 @@ restir_status restir_denoise(restir_ctx* ctx, const restir_camera* cam, uint32_t
                              const restir_features* tone /* nullable */, float* out_rgb /* nullable */);
 restir_status restir_denoise_host(const float* rgb, const float* n_t, const float* p_mat, uint32_t w, uint32_t h,
                                   uint32_t miss_material, const restir_denoise_params* params, float* out);   /* pure host, same arithmetic */
-restir_status restir_denoise_guide_builds(restir_ctx* ctx, uint64_t* out);   /* guide traces so far */
+restir_status restir_denoise_guide_builds(restir_ctx* ctx, uint64_t* out);   /* guide traces so far, restir_denoise_lum's included */
+
+/* ---- denoising with a variance-guided luminance term ---------------------------------------------------------
+ * restir_denoise_lum is restir_denoise with one more factor per tap: a rational luminance weight whose scale is the
+ * pixel's own measured noise (after SVGF, Schied et al. 2017, with 1 / (1 + r r) in place of exp(-r): no expf).  A
+ * per-pixel variance plane travels through the levels next to the colour.  Every step below is one float32 operation
+ * without contraction, divide and sqrt correctly rounded, fabsf exact; restir_denoise_lum_host (pure host) is the same
+ * arithmetic over arrays, bit for bit.  Guides, flat rule, k, h, g_p, P, t, material: restir_denoise's, above.
+ * Luminance:  l(c) = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b.
+ * clean(v) = v when v > 0 and v is finite, else +0: every entry of the initial variance plane v (one float per pixel,
+ * image rows) is stored through it.
+ * RESTIR_DENOISE_VAR_ACCUM: the input colour is the open accumulation's mean, exactly the bits restir_accum_resolve(ctx,
+ *   NULL) would write, whatever the last image is; it needs an open accumulation with RESTIR_ACCUM_VARIANCE, n >= 2 frames
+ *   and the owned rectangle's size, else RESTIR_ERR_STATE and nothing changed.  With inv = 1.0f / ((float)n (float)(n - 1)),
+ *   computed once on the host:  s.j = sqrtf(m2.j inv) per channel;  sl = l(s);  v = clean(sl sl).  The channels' standard
+ *   errors are added, not their variances: the three channels of a ReSTIR sample share one contribution weight, so their
+ *   noise is correlated and the luminance's deviation is the weighted sum of the channels'.  The accumulation is read
+ *   only: its state, its count and the still view's caches are untouched.
+ * RESTIR_DENOISE_VAR_SPATIAL: the input colour is the last image, under restir_denoise's rules.  For a centre p whose
+ *   colour is finite:
+ *     s0 = s1 = s2 = +0;  inv_s = 1.0f / (geo.sigma_plane t_p)
+ *     for dy = -3 .. 3 (image rows), for dx = -3 .. 3:   q = p + (dx, dy)
+ *         q outside the rectangle, or c_q with a component that is not finite: skipped
+ *         q == p:  w = 1.0f
+ *         else:    w = restir_denoise's geometry weight of the tap with h = 1.0f (its material and flat rules
+ *                  included: a tap they skip has w = 0);  skipped unless w > 0
+ *         l_q = l(c_q);  s0 = s0 + w;  s1 = s1 + w l_q;  s2 = s2 + w (l_q l_q)
+ *     m1 = s1 / s0;  v = clean(s2 / s0 - m1 m1)
+ *   A centre whose colour is not finite has v = +0.
+ * Levels i = 0 .. geo.iterations - 1 with step s = 2^i, each reading the colour and the variance of the level before.
+ * For a pixel p whose colour is finite:
+ *     gn = gd = +0
+ *     for dy = -1 .. 1, for dx = -1 .. 1 (unit offsets at every level):   q = p + (dx, dy), skipped outside the rectangle
+ *         gw = g[dy] g[dx],  g = (1/4, 1/2, 1/4);  gn = gn + gw v_q;  gd = gd + gw
+ *     gv = gn / gd;  inv_den = 1.0f / (sigma_lum sqrtf(gv) + 1e-6f);  l_p = l(c_p)
+ *     sw = +0, sc = (+0, +0, +0), sv = +0
+ *     the 25 taps of restir_denoise in its order, its skip rules unchanged, the centre's w = h;  for every other tap
+ *         w_geo = restir_denoise's w (0 where its material or flat rule skips the tap)
+ *         r = fabsf(l(c_q) - l_p) inv_den;  wl = 1.0f / (1.0f + r r);  w = w_geo wl
+ *         skipped unless w > 0 (an infinite r gives wl = 0, a NaN fails the test)
+ *     per contributing tap:  sw = sw + w;  sc.j = sc.j + w c_q.j;  sv = sv + (w w) v_q
+ *     out.j = sc.j / sw;  v_out = sv / (sw sw)         (v_out is stored as computed, not through clean)
+ * A pixel whose own colour is not finite keeps its colour's bits and its v at every level; its v is read by its
+ * neighbours' gv like any other.  After the last level restir_denoise_lum applies the tone map as restir_denoise does;
+ * the host function has none.
+ * restir_denoise_lum_host: var == NULL runs the SPATIAL estimate, otherwise var is the initial plane (w x h floats, image
+ * rows), read through clean; params->variance_source is checked and otherwise ignored.  A caller that wants ACCUM's plane
+ * computes it from restir_accum_download.  out_var (nullable) receives the last level's variance plane; the outputs must
+ * not overlap the inputs.
+ * State: the call uses restir_denoise's guide planes and their key -- a view traced by one call is not traced again by the
+ * other, restir_denoise_guide_builds counts both.  The result is marked like restir_denoise's; tiles, halo frames, NULL
+ * arguments, range errors and the frame state follow restir_denoise's rules.  RESTIR_ERR_INVALID in addition: an unknown
+ * variance_source, a sigma_lum that is not a positive finite number, flags != 0, geo out of range.  Errors are found
+ * before anything is written.  restir_denoise_lum_variance_download copies the last successful call's final variance
+ * plane (count >= W H floats, else RESTIR_ERR_INVALID; no such call since the planes were last dropped: RESTIR_ERR_STATE)
+ * and synchronises: a test hook. */
+#define RESTIR_DENOISE_VAR_SPATIAL 0u   /* variance estimated from the image itself */
+#define RESTIR_DENOISE_VAR_ACCUM   1u   /* image = the open accumulation's mean, variance from its m2 */
+typedef struct restir_denoise_lum_params {
+    restir_denoise_params geo;   /* as restir_denoise's; geo.flags == 0 */
+    uint32_t variance_source;    /* RESTIR_DENOISE_VAR_* */
+    float    sigma_lum;          /* finite, > 0: the luminance term's support in standard deviations.  The default stays 4, with geo's 2
+                                  * levels, after the sweep of {1, 2, 4, 8} x 1 .. 5 levels at 1920 x 1080: 2 leaves one C2 frame's
+                                  * MSE above restir_denoise's (0.649 against 0.485, 4: 0.471); 8 is level with 4 on one frame and
+                                  * loses on every mean (16 frames: MSE 0.257 against 0.179) (README "Denoising with a luminance
+                                  * term") */
+    uint32_t flags;              /* 0 */
+} restir_denoise_lum_params;
+void restir_denoise_lum_params_default(restir_denoise_lum_params* out);   /* restir_denoise's defaults, SPATIAL, 4.0f, 0 */
+restir_status restir_denoise_lum(restir_ctx* ctx, const restir_camera* cam, uint32_t width, uint32_t height,
+                                 const restir_tile* tile /* nullable */, const restir_denoise_lum_params* params,
+                                 const restir_features* tone /* nullable */, float* out_rgb /* nullable */);
+restir_status restir_denoise_lum_host(const float* rgb, const float* var /* nullable: the spatial estimate */, const float* n_t,
+                                      const float* p_mat, uint32_t w, uint32_t h, uint32_t miss_material,
+                                      const restir_denoise_lum_params* params, float* out_rgb, float* out_var /* nullable */);
+restir_status restir_denoise_lum_variance_download(restir_ctx* ctx, float* var, size_t count);   /* the last call's final variance plane; synchronises */
 
 /* ---- stage-level access for parity tests and profiling ---------------------------------------------- *
  * Buffers are the device SoA layout (DESIGN.md "Data layout"), one entry per pixel of the computed region

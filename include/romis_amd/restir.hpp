@@ -47,6 +47,11 @@ struct DenoiseParams : restir_denoise_params {
     DenoiseParams() { restir_denoise_params_default(this); }
 };
 
+// restir_denoise_lum_params with its defaults (DenoiseParams', the spatial variance estimate, sigma_lum 4)
+struct DenoiseLumParams : restir_denoise_lum_params {
+    DenoiseLumParams() { restir_denoise_lum_params_default(this); }
+};
+
 // The reference's own struct Features (src/utils/common.h:89-136) -> Features, field by field by the reference's
 // member names (any type with those members works, so the reference's header is not needed here).  The enums
 // keep their values: RayTraceMode {ReSTIR, RMIS, ROMIS} (common.h:25-29) = restir_mode,
@@ -395,6 +400,13 @@ public:
     void denoise(const Camera& camera, uint32_t width, uint32_t height, const DenoiseParams& params = DenoiseParams(),
                  const Features* tone = nullptr, float* rgb = nullptr) {
         check(restir_denoise(ctx_, &camera, width, height, nullptr, &params, tone, rgb), "restir_denoise");
+    }
+    // denoise with a variance-guided luminance term (restir_denoise_lum).  With params.variance_source =
+    // RESTIR_DENOISE_VAR_ACCUM the image is the open accumulation's mean (two frames at least, with the variance) and the
+    // variance its m2's; otherwise the last image, with a variance estimated from it
+    void denoiseLum(const Camera& camera, uint32_t width, uint32_t height, const DenoiseLumParams& params = DenoiseLumParams(),
+                    const Features* tone = nullptr, float* rgb = nullptr) {
+        check(restir_denoise_lum(ctx_, &camera, width, height, nullptr, &params, tone, rgb), "restir_denoise_lum");
     }
     uint64_t denoiseGuideBuilds() const {
         uint64_t n = 0;

@@ -177,6 +177,17 @@ class DenoiseParams(C.Structure):
 RESTIR_DENOISE_MAX_ITERATIONS = 5
 assert C.sizeof(DenoiseParams) == 16
 
+
+class DenoiseLumParams(C.Structure):
+    """restir_denoise_lum_params: restir_denoise's parameters, where the variance comes from and the luminance term's
+    support in standard deviations."""
+    _fields_ = [("geo", DenoiseParams), ("variance_source", C.c_uint32), ("sigma_lum", C.c_float), ("flags", C.c_uint32)]
+
+
+RESTIR_DENOISE_VAR_SPATIAL = 0
+RESTIR_DENOISE_VAR_ACCUM = 1
+assert C.sizeof(DenoiseLumParams) == 28
+
 RESTIR_MAX_TILES_X = 16
 RESTIR_MAX_TILES_Y = 16
 
@@ -303,6 +314,13 @@ SIGNATURES = {
     "restir_denoise_host": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
                                       C.c_uint32, C.POINTER(DenoiseParams), C.POINTER(C.c_float)]),
     "restir_denoise_guide_builds": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "restir_denoise_lum_params_default": (None, [C.POINTER(DenoiseLumParams)]),
+    "restir_denoise_lum": (C.c_int, [_P, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(Tile), C.POINTER(DenoiseLumParams),
+                                     C.POINTER(Features), C.POINTER(C.c_float)]),
+    "restir_denoise_lum_host": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                          C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DenoiseLumParams), C.POINTER(C.c_float),
+                                          C.POINTER(C.c_float)]),
+    "restir_denoise_lum_variance_download": (C.c_int, [_P, C.POINTER(C.c_float), C.c_size_t]),
     "restir_stage_configure": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "restir_stage_upload": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     "restir_stage_download": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),

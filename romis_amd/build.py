@@ -224,7 +224,8 @@ def main(argv=None) -> int:
 CPP_PROGRAMS = [("render_scene.cpp", "render_scene"), ("render_threads.cpp", "render_threads"),
                 ("write_outputs.cpp", "write_outputs"), ("update_scene.cpp", "update_scene"),
                 ("present_frames.cpp", "present_frames"), ("accumulate_frames.cpp", "accumulate_frames"),
-                ("exact_image.cpp", "exact_image"), ("denoise_frames.cpp", "denoise_frames")]
+                ("exact_image.cpp", "exact_image"), ("denoise_frames.cpp", "denoise_frames"),
+                ("denoise_lum_frames.cpp", "denoise_lum_frames")]
 CPP_DIR = os.path.join(ROOT, "tests", "cpp")
 
 

@@ -42,6 +42,7 @@
 namespace romis {
 bool write_bmp_words(const char* path, uint32_t width, uint32_t height, const uint32_t* words);   // screen.cpp
 restir_status denoise_params_check(const restir_denoise_params* p, const char* who);               // denoise_host.cpp
+restir_status denoise_lum_params_check(const restir_denoise_lum_params* p, const char* who);
 }
 using namespace romis;
 
@@ -441,6 +442,11 @@ struct restir_ctx {
         restir_tile tile{};
     } dn_key;
     uint64_t dn_guide_builds = 0;                   // guide traces (restir_denoise_guide_builds)
+    // restir_denoise_lum's variance planes, one float per pixel, which its levels alternate between; they live and die
+    // with the guide planes.  dn_var_px != 0: dn_var[dn_var_last] holds the last call's final plane of that many pixels
+    DevBuf dn_var[2];
+    uint32_t dn_var_last = 0;
+    size_t dn_var_px = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -917,7 +923,8 @@ void restir_destroy(restir_ctx* c) {
         (void)hipStreamSynchronize(c->stream);
         for (DevBuf* b : {&c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
                           &c->rpj_map, &c->acc.mean, &c->acc.m2, &c->acc.partials, &c->exact_nt, &c->exact_pm, &c->exact_uv,
-                          &c->ref, &c->err_partials, &c->dn_nt, &c->dn_pf, &c->dn_ga, &c->dn_uv, &c->dn_tmp[0], &c->dn_tmp[1]})
+                          &c->ref, &c->err_partials, &c->dn_nt, &c->dn_pf, &c->dn_ga, &c->dn_uv, &c->dn_tmp[0], &c->dn_tmp[1],
+                          &c->dn_var[0], &c->dn_var[1]})
             b->release();
         drop_shadow_lists(c);
         drop_phat_table(c);
@@ -3003,6 +3010,58 @@ restir_status restir_error_measure(const float* a, const float* r, size_t count,
 // denoising the last image (include/restir_c.h "denoising the last image", denoise.h, DESIGN.md §6 "Denoising a frame").
 // Like the exact image, nothing here reads or writes the frame path's G-buffer planes or what is built over them, the
 // frame index or the stage buffers.
+// The guide planes restir_denoise and restir_denoise_lum share.  denoise_guides_alloc compares the view with the kept
+// planes' key and sizes the planes where it differs; denoise_guides_trace then traces them (once per view).  The caller
+// holds c->mu and has set the device.
+struct DenoiseView {
+    CameraDev camd;
+    restir_ctx::DenoiseKey want;
+    bool keep = false;
+};
+
+static restir_status denoise_guides_alloc(restir_ctx* c, const restir_camera* cam, uint32_t width, uint32_t height,
+                                          const restir_tile& t, DenoiseView& v) {
+    const size_t npx = (size_t)t.width * t.height;
+    v.camd = camera_dev(cam);
+    const CameraDev& camd = v.camd;
+    restir_ctx::DenoiseKey& want = v.want;
+    want.valid = true;
+    want.geom_gen = c->geom_gen;
+    const float camf[9] = {camd.quat.x, camd.quat.y, camd.quat.z, camd.quat.w, camd.origin[0], camd.origin[1], camd.origin[2],
+                           camd.half_w, camd.half_h};
+    std::memcpy(want.cam, camf, sizeof(want.cam));
+    want.width = width; want.height = height;
+    want.tile = t;
+    const restir_ctx::DenoiseKey& have = c->dn_key;
+    v.keep = have.valid && have.geom_gen == want.geom_gen && !std::memcmp(have.cam, want.cam, sizeof(have.cam)) &&
+             have.width == want.width && have.height == want.height && !std::memcmp(&have.tile, &want.tile, sizeof(restir_tile));
+    if (!v.keep) {
+        c->dn_key.valid = false;
+        c->dn_var_px = 0;   // the variance planes live with the guides
+        ST_TRY(c->dn_nt.ensure(npx * 16));
+        ST_TRY(c->dn_pf.ensure(npx * 16));
+        ST_TRY(c->dn_ga.ensure(npx * 16));
+    }
+    return RESTIR_OK;
+}
+
+static restir_status denoise_guides_trace(restir_ctx* c, uint32_t width, uint32_t height, const restir_tile& t, DenoiseView& v) {
+    if (v.keep) return RESTIR_OK;
+    const size_t npx = (size_t)t.width * t.height;
+    FeaturesDev f{};
+    SceneDev s;
+    ST_TRY(scene_for(c, f, npx, s, &c->dn_uv));
+    const Region view = make_region(width, height, t.x0, t.y0, t.width, t.height, t.x0, t.y0, t.width, t.height);
+    LaunchBufs b;
+    b.cam = &v.camd; b.origin = v.camd.origin;
+    b.n_t = c->dn_nt.as<float4>(); b.p_mat = c->dn_pf.as<float4>();
+    HIP_TRY(launch_primary(route_primary(s, view, c->tuning), s, view, b, c->stream));
+    HIP_TRY(launch_denoise_guides(b.n_t, b.p_mat, c->dn_ga.as<float4>(), npx, s.num_materials - 1u, c->stream));
+    c->dn_key = v.want;
+    c->dn_guide_builds++;
+    return RESTIR_OK;
+}
+
 restir_status restir_denoise(restir_ctx* c, const restir_camera* cam, uint32_t width, uint32_t height, const restir_tile* tile,
                              const restir_denoise_params* params, const restir_features* tone, float* out_rgb) {
     if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
@@ -3021,42 +3080,14 @@ restir_status restir_denoise(restir_ctx* c, const restir_camera* cam, uint32_t w
     HIP_TRY(hipSetDevice(c->device));
 
     const size_t npx = (size_t)t.width * t.height;
-    const CameraDev camd = camera_dev(cam);
-    restir_ctx::DenoiseKey want;
-    want.valid = true;
-    want.geom_gen = c->geom_gen;
-    const float camf[9] = {camd.quat.x, camd.quat.y, camd.quat.z, camd.quat.w, camd.origin[0], camd.origin[1], camd.origin[2],
-                           camd.half_w, camd.half_h};
-    std::memcpy(want.cam, camf, sizeof(want.cam));
-    want.width = width; want.height = height;
-    want.tile = t;
-    const restir_ctx::DenoiseKey& have = c->dn_key;
-    const bool keep = have.valid && have.geom_gen == want.geom_gen && !std::memcmp(have.cam, want.cam, sizeof(have.cam)) &&
-                      have.width == want.width && have.height == want.height && !std::memcmp(&have.tile, &want.tile, sizeof(restir_tile));
+    DenoiseView view;
     // every buffer first: a refused allocation leaves the image as it was
     const uint32_t levels = params->iterations;
-    if (!keep) {
-        c->dn_key.valid = false;
-        ST_TRY(c->dn_nt.ensure(npx * 16));
-        ST_TRY(c->dn_pf.ensure(npx * 16));
-        ST_TRY(c->dn_ga.ensure(npx * 16));
-    }
+    ST_TRY(denoise_guides_alloc(c, cam, width, height, t, view));
     ST_TRY(c->dn_tmp[0].ensure(npx * 12));
     if (levels > 2u) ST_TRY(c->dn_tmp[1].ensure(npx * 12));
     set_launch_events(nullptr, nullptr);   // no RESTIR_K_* slot: restir_timings does not see these launches
-    if (!keep) {
-        FeaturesDev f{};
-        SceneDev s;
-        ST_TRY(scene_for(c, f, npx, s, &c->dn_uv));
-        const Region view = make_region(width, height, t.x0, t.y0, t.width, t.height, t.x0, t.y0, t.width, t.height);
-        LaunchBufs b;
-        b.cam = &camd; b.origin = camd.origin;
-        b.n_t = c->dn_nt.as<float4>(); b.p_mat = c->dn_pf.as<float4>();
-        HIP_TRY(launch_primary(route_primary(s, view, c->tuning), s, view, b, c->stream));
-        HIP_TRY(launch_denoise_guides(b.n_t, b.p_mat, c->dn_ga.as<float4>(), npx, s.num_materials - 1u, c->stream));
-        c->dn_key = want;
-        c->dn_guide_builds++;
-    }
+    ST_TRY(denoise_guides_trace(c, width, height, t, view));
     c->stage_ok = false;   // like restir_render_exact: the stage API is to be configured again
 
     FeaturesDev tf{};
@@ -3086,6 +3117,110 @@ restir_status restir_denoise(restir_ctx* c, const restir_camera* cam, uint32_t w
         HIP_TRY(hipMemcpyAsync(out_rgb, c->rgb.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
+    return RESTIR_OK;
+}
+
+// restir_denoise with the variance-guided luminance term (include/restir_c.h "denoising with a variance-guided
+// luminance term").  The colour takes restir_denoise's way through the scratch images; the variance alternates between
+// dn_var[0] and dn_var[1], level i reading dn_var[i & 1].
+restir_status restir_denoise_lum(restir_ctx* c, const restir_camera* cam, uint32_t width, uint32_t height, const restir_tile* tile,
+                                 const restir_denoise_lum_params* params, const restir_features* tone, float* out_rgb) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (!cam) return fail(RESTIR_ERR_INVALID, "camera is NULL");
+    ST_TRY(denoise_lum_params_check(params, "restir_denoise_lum"));
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_denoise_lum before restir_set_scene");
+    if (c->halo.active) return fail(RESTIR_ERR_STATE, "restir_denoise_lum between restir_halo_begin and restir_halo_end");
+    restir_tile t;
+    ST_TRY(frame_tile(tile, width, height, 0, t));
+    const bool from_accum = params->variance_source == RESTIR_DENOISE_VAR_ACCUM;
+    const auto& a = c->acc;
+    if (from_accum) {
+        if (!a.open) return fail(RESTIR_ERR_STATE, "restir_denoise_lum: RESTIR_DENOISE_VAR_ACCUM without an open accumulation");
+        if (!(a.flags & RESTIR_ACCUM_VARIANCE))
+            return fail(RESTIR_ERR_STATE, "restir_denoise_lum: RESTIR_DENOISE_VAR_ACCUM needs RESTIR_ACCUM_VARIANCE");
+        if (a.frames < 2)
+            return fail(RESTIR_ERR_STATE, "restir_denoise_lum: RESTIR_DENOISE_VAR_ACCUM needs two frames, %u are accumulated", a.frames);
+        if (t.width != a.width || t.height != a.height)
+            return fail(RESTIR_ERR_STATE, "restir_denoise_lum: the accumulation is %ux%u, the owned rectangle %ux%u", a.width,
+                        a.height, t.width, t.height);
+    } else {
+        if ((c->rgb_from != restir_ctx::RGB_PRODUCED && c->rgb_from != restir_ctx::RGB_RESOLVED) || (size_t)c->rgb_w * c->rgb_h == 0)
+            return fail(RESTIR_ERR_STATE, "restir_denoise_lum: nothing rendered yet");
+        if (t.width != c->rgb_w || t.height != c->rgb_h)
+            return fail(RESTIR_ERR_STATE, "restir_denoise_lum: the last image is %ux%u, the owned rectangle %ux%u", c->rgb_w,
+                        c->rgb_h, t.width, t.height);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+
+    const size_t npx = (size_t)t.width * t.height;
+    const restir_denoise_params& geo = params->geo;
+    const uint32_t levels = geo.iterations;
+    DenoiseView view;
+    // every buffer first: a refused allocation leaves the image as it was
+    ST_TRY(denoise_guides_alloc(c, cam, width, height, t, view));
+    ST_TRY(c->dn_tmp[0].ensure(npx * 12));
+    if (levels > 2u) ST_TRY(c->dn_tmp[1].ensure(npx * 12));
+    c->dn_var_px = 0;
+    ST_TRY(c->dn_var[0].ensure(npx * 4));
+    ST_TRY(c->dn_var[1].ensure(npx * 4));
+    if (from_accum && (c->rgb.bytes < npx * 12 || !c->rgb.p)) {   // a render of another size may have come between
+        c->rgb_from = restir_ctx::RGB_NONE;
+        ST_TRY(c->rgb.ensure(npx * 12));
+    }
+    set_launch_events(nullptr, nullptr);   // no RESTIR_K_* slot: restir_timings does not see these launches
+    ST_TRY(denoise_guides_trace(c, width, height, t, view));
+    c->stage_ok = false;
+
+    FeaturesDev tf{};
+    if (tone) {
+        tf.tone_map = tone->enable_tone_mapping;
+        tf.gamma = tone->gamma;
+        tf.exposure = tone->exposure;
+    }
+    const float4 *n_t = c->dn_nt.as<float4>(), *ga = c->dn_ga.as<float4>(), *pf = c->dn_pf.as<float4>();
+    float* rgb = c->rgb.as<float>();
+    if (from_accum) {
+        // the mean becomes the image, as restir_accum_resolve(ctx, NULL) would write it; the accumulation is only read
+        c->image_pending(a.width, a.height);
+        const float inv = 1.0f / ((float)a.frames * (float)(a.frames - 1u));
+        HIP_TRY(launch_denoise_var_accum(a.mean.as<float>(), a.m2.as<float>(), rgb, c->dn_var[0].as<float>(), npx, inv, c->stream));
+    } else {
+        c->rgb_from = restir_ctx::RGB_PENDING;   // (a launch the device refuses leaves the buffer without an image)
+        HIP_TRY(launch_denoise_var_spatial(rgb, c->dn_var[0].as<float>(), n_t, ga, pf, t.width, t.height, geo.normal_power_log2,
+                                           geo.sigma_plane, c->stream));
+    }
+    const float* in = rgb;
+    if (levels == 1u) {
+        HIP_TRY(hipMemcpyAsync(c->dn_tmp[0].p, rgb, npx * 12, hipMemcpyDeviceToDevice, c->stream));
+        in = c->dn_tmp[0].as<float>();
+    }
+    for (uint32_t level = 0; level < levels; level++) {
+        const bool last = level + 1u == levels;
+        float* out = last ? rgb : c->dn_tmp[level & 1u].as<float>();
+        HIP_TRY(launch_denoise_level_lum(in, out, c->dn_var[level & 1u].as<float>(), c->dn_var[(level + 1u) & 1u].as<float>(), n_t, ga,
+                                         pf, t.width, t.height, level, geo.normal_power_log2, geo.sigma_plane, params->sigma_lum,
+                                         last ? &tf : nullptr, c->stream));
+        in = out;
+    }
+    c->rgb_from = restir_ctx::RGB_RESOLVED;
+    c->dn_var_last = levels & 1u;
+    c->dn_var_px = npx;
+    if (out_rgb) {
+        HIP_TRY(hipMemcpyAsync(out_rgb, c->rgb.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return RESTIR_OK;
+}
+
+restir_status restir_denoise_lum_variance_download(restir_ctx* c, float* var, size_t count) {
+    if (!c || !var) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->dn_var_px == 0) return fail(RESTIR_ERR_STATE, "restir_denoise_lum_variance_download: no restir_denoise_lum result is kept");
+    if (count < c->dn_var_px) return fail(RESTIR_ERR_INVALID, "buffer holds %zu floats, need %zu", count, c->dn_var_px);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(var, c->dn_var[c->dn_var_last].p, c->dn_var_px * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return RESTIR_OK;
 }
 

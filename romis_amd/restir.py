@@ -383,6 +383,36 @@ class Renderer:
             rgb.ctypes.data_as(C.POINTER(C.c_float)) if download else None), "restir_denoise")
         return rgb
 
+    def denoise_lum(self, camera, width: int, height: int, tile=None, params=None, tone=None, download: bool = True):
+        """restir_denoise_lum: denoise() with a variance-guided luminance term.  params: a DenoiseLumParams (None: the
+        defaults); with variance_source = RESTIR_DENOISE_VAR_ACCUM the image is the open accumulation's mean and the
+        variance comes from its m2, otherwise the last image is filtered with a variance estimated from it.  Returns
+        rgb [h][w][3] (row 0 = top) of the tile's owned rectangle, or None with download=False, which only enqueues."""
+        if params is None:
+            params = denoise_lum_params()
+        rgb = None
+        if download:
+            h_ = tile.height if tile is not None else height
+            w_ = tile.width if tile is not None else width
+            rgb = np.zeros((h_, w_, 3), np.float32)
+        check(self.lib, self.lib.restir_denoise_lum(
+            self.ctx, C.byref(camera), width, height, C.byref(tile) if tile is not None else None, C.byref(params),
+            C.byref(tone) if tone is not None else None,
+            rgb.ctypes.data_as(C.POINTER(C.c_float)) if download else None), "restir_denoise_lum")
+        self._denoise_lum_shape = (tile.height, tile.width) if tile is not None else (height, width)
+        return rgb
+
+    def denoise_lum_variance(self) -> np.ndarray:
+        """restir_denoise_lum_variance_download: the last denoise_lum's final variance plane [h][w] (row 0 = top) of its
+        owned rectangle; synchronises.  A test hook."""
+        shape = getattr(self, "_denoise_lum_shape", None)
+        if shape is None:
+            raise RuntimeError("denoise_lum_variance before denoise_lum")
+        var = np.zeros(shape, np.float32)
+        check(self.lib, self.lib.restir_denoise_lum_variance_download(self.ctx, var.ctypes.data_as(C.POINTER(C.c_float)), var.size),
+              "restir_denoise_lum_variance_download")
+        return var
+
     def denoise_guide_builds(self) -> int:
         """restir_denoise_guide_builds: how often denoise() traced its guides (a still view traces them once)."""
         n = C.c_uint64()
@@ -733,6 +763,52 @@ def denoise_params(iterations: int | None = None, normal_power_log2: int | None 
     if sigma_plane is not None:
         p.sigma_plane = sigma_plane
     return p
+
+
+def denoise_lum_params(iterations: int | None = None, normal_power_log2: int | None = None, sigma_plane: float | None = None,
+                       variance_source: int | None = None, sigma_lum: float | None = None) -> _abi.DenoiseLumParams:
+    """restir_denoise_lum_params_default, with the given fields replaced."""
+    lib = _abi.load_library()
+    p = _abi.DenoiseLumParams()
+    lib.restir_denoise_lum_params_default(C.byref(p))
+    if iterations is not None:
+        p.geo.iterations = iterations
+    if normal_power_log2 is not None:
+        p.geo.normal_power_log2 = normal_power_log2
+    if sigma_plane is not None:
+        p.geo.sigma_plane = sigma_plane
+    if variance_source is not None:
+        p.variance_source = variance_source
+    if sigma_lum is not None:
+        p.sigma_lum = sigma_lum
+    return p
+
+
+def denoise_lum_host(rgb, n_t, p_mat, miss_material: int, params=None, var=None):
+    """restir_denoise_lum_host (pure host): Renderer.denoise_lum's arithmetic, bit for bit, without the tone-mapping step.
+    rgb, n_t, p_mat, miss_material as denoise_host's; var [h][w] (row 0 = top): the initial variance plane, None: the
+    spatial estimate.  Returns (the filtered rgb [h][w][3], the last level's variance plane [h][w])."""
+    lib = _abi.load_library()
+    c = np.ascontiguousarray(rgb, np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("denoise_lum_host: rgb must be [h][w][3]")
+    h, w = c.shape[:2]
+    nt, pm = np.ascontiguousarray(n_t, np.float32), np.ascontiguousarray(p_mat, np.float32)
+    if nt.size != 4 * w * h or pm.size != 4 * w * h:
+        raise ValueError("denoise_lum_host: n_t and p_mat must hold 4 floats per pixel of rgb")
+    FP = C.POINTER(C.c_float)
+    v = None
+    if var is not None:
+        v = np.ascontiguousarray(var, np.float32)
+        if v.size != w * h:
+            raise ValueError("denoise_lum_host: var must hold one float per pixel of rgb")
+    if params is None:
+        params = denoise_lum_params()
+    out, out_var = np.zeros_like(c), np.zeros((h, w), np.float32)
+    check(lib, lib.restir_denoise_lum_host(c.ctypes.data_as(FP), v.ctypes.data_as(FP) if v is not None else None,
+                                           nt.ctypes.data_as(FP), pm.ctypes.data_as(FP), w, h, miss_material, C.byref(params),
+                                           out.ctypes.data_as(FP), out_var.ctypes.data_as(FP)), "restir_denoise_lum_host")
+    return out, out_var
 
 
 def denoise_host(rgb, n_t, p_mat, miss_material: int, params=None) -> np.ndarray:
