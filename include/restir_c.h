@@ -960,6 +960,21 @@ restir_status restir_debug_shadow_vis(restir_ctx* ctx, uint32_t light, uint32_t 
 restir_status restir_phat_frames(restir_ctx* ctx, uint64_t* out_frames);
 restir_status restir_phat_builds(restir_ctx* ctx, uint64_t* out_builds);
 
+/* RIS look-ahead (tuning "frames.ahead", "frames.ahead_after", "frames.ahead_prio").  A restir_render frame of a still
+ * view whose RIS reads the p-hat table, without temporal reuse, launches the next frame's RIS on a second stream of the
+ * context beside its own last pass, into a second set of handle and pdf-cache planes (12 bytes per pixel of the view);
+ * the next restir_render call takes that result, and launches no RIS, when everything the result depends on is what the
+ * call asks for -- seed, frame index, view, scene, table, features, knobs -- and otherwise runs as if there had been
+ * none.  Frames are bit for bit the frames of frames.ahead = 0.  frames.ahead: 0 off, 1 (default) the look-ahead
+ * enqueued behind the last pass, 2 before it; frames.ahead_after: from this many consecutive reusing frames (default 4,
+ * and never before the table is read); frames.ahead_prio: 1 creates the second stream at the lowest priority.
+ * restir_synchronize, restir_timings, scene and light updates and restir_destroy wait for the second stream too; a
+ * look-ahead launch is timed as RESTIR_K_PRIMARY_RIS.  A view that moves after a pause pays for one launch that is
+ * never read (restir_ahead_discards counts them); restir_set_seed always drops a pending result.
+ * restir_ahead_frames: the frames so far that took their RIS result from a look-ahead. */
+restir_status restir_ahead_frames(restir_ctx* ctx, uint64_t* out_frames);
+restir_status restir_ahead_discards(restir_ctx* ctx, uint64_t* out_discards);
+
 /* Test hook for that table, as the last frame left it (RESTIR_ERR_STATE when there is none for the kept G-buffer): for
  * every pixel of that frame's view, width x height (RESTIR_ERR_INVALID when the frame's was another size; row-major from
  * its first row), the stored target pdf of point light `light` (< num_lights, else RESTIR_ERR_INVALID); -1 where none is

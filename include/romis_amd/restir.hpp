@@ -335,6 +335,18 @@ public:
         check(restir_phat_builds(ctx_, &n), "restir_phat_builds");
         return n;
     }
+    // Frames so far that took their RIS result from the look-ahead the frame before launched, and the results no frame
+    // took (restir_ahead_frames, restir_ahead_discards)
+    uint64_t aheadFrames() const {
+        uint64_t n = 0;
+        check(restir_ahead_frames(ctx_, &n), "restir_ahead_frames");
+        return n;
+    }
+    uint64_t aheadDiscards() const {
+        uint64_t n = 0;
+        check(restir_ahead_discards(ctx_, &n), "restir_ahead_discards");
+        return n;
+    }
     // Test hook (restir_debug_phat): width x height floats, the last frame's view (another size is refused)
     void debugPhat(uint32_t light, std::vector<float>& phat, uint32_t width, uint32_t height) const {
         phat.assign(size_t(width) * height, 0.0f);

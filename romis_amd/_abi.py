@@ -386,6 +386,8 @@ SIGNATURES = {
     "restir_debug_shadow_vis": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]),
     "restir_phat_frames": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "restir_phat_builds": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "restir_ahead_frames": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "restir_ahead_discards": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "restir_debug_phat": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "restir_scene_info": (C.c_int, [_P, C.POINTER(SceneInfo)]),
     "restir_enable_timing": (C.c_int, [_P, C.c_int]),

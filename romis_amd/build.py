@@ -56,7 +56,7 @@ SOURCES = [("kernels.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS)] + ABI_UNITS +
     ("screen.cpp", ["-x", "c++"]),
 ]
 HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
-           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "shadow_vis.h", "phat_table.h", "abi_error.h", "layout.h", "halo_segs.h", "present.h", "accum.h", "exact.h", "denoise.h"]
+           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "shadow_vis.h", "phat_table.h", "abi_error.h", "layout.h", "halo_segs.h", "present.h", "accum.h", "exact.h", "denoise.h", "ris_ahead.h"]
 
 
 def source_hash() -> str:
@@ -112,6 +112,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_shadow_lists_check(force)
     build_shadow_vis_layout(force)
     build_phat_layout(force)
+    build_ris_ahead_key(force)
     if verbose:
         print(LIB)
     return LIB
@@ -189,6 +190,18 @@ def build_phat_layout(force: bool = False) -> str:
     tool = os.path.join(OUT, "tools", "phat_layout")
     src = os.path.join(ROOT, "tests", "cpp", "phat_layout.cpp")
     deps = [src, os.path.join(CSRC, "phat_table.h"), __file__]
+    if os.path.exists(src) and (force or _stale(tool, deps)):
+        os.makedirs(os.path.dirname(tool), exist_ok=True)
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", tool])
+    return tool
+
+
+def build_ris_ahead_key(force: bool = False) -> str:
+    """tools/ris_ahead_key: tests/cpp/ris_ahead_key.cpp over csrc/ris_ahead.h with the host compiler -- the look-ahead
+    key's comparison, one case per member (tests/test_ris_ahead_key.py); no device code, no HIP header."""
+    tool = os.path.join(OUT, "tools", "ris_ahead_key")
+    src = os.path.join(ROOT, "tests", "cpp", "ris_ahead_key.cpp")
+    deps = [src, os.path.join(CSRC, "ris_ahead.h"), __file__]
     if os.path.exists(src) and (force or _stale(tool, deps)):
         os.makedirs(os.path.dirname(tool), exist_ok=True)
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", tool])

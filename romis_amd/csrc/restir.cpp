@@ -38,6 +38,7 @@
 #include "shadow_lists.h"
 #include "phat_table.h"
 #include "shadow_vis.h"
+#include "ris_ahead.h"
 
 namespace romis {
 bool write_bmp_words(const char* path, uint32_t width, uint32_t height, const uint32_t* words);   // screen.cpp
@@ -338,6 +339,32 @@ struct restir_ctx {
     PhatTableDev phat_dev{};
     uint64_t phat_frames = 0;                       // frames whose RIS read the table (restir_phat_frames)
     uint64_t phat_builds = 0;                       // k_phat_table launches (restir_phat_builds)
+    // RIS look-ahead (ris_ahead.h, tuning "frames.ahead"; DESIGN.md §6 "RIS look-ahead"): on a still view served by the
+    // p-hat table without temporal reuse, frame f + 1's RIS runs on `stream` beside frame f's last pass and writes the
+    // plane set frame f does not read -- set 0 is (hnd[0], rp[0]), set 1 (hnd, rp) here: 12 B a pixel of the view.
+    // `valid`: a result keyed `key` is in (or on its way into) set `set`; the next restir_render takes it when its own
+    // key is equal and launches no RIS, else marks it invalid (discards) and runs as if there had been none.
+    struct {
+        uint32_t on = 1, after = 4, prio = 0;       // knobs frames.ahead (2: RIS enqueued before the last pass), _after, _prio
+        hipStream_t stream = nullptr;               // created by the first eligible frame, non-blocking
+        uint32_t stream_prio = 0;                   // frames.ahead_prio the stream was created with
+        DevBuf hnd, rp;
+        // done[s]: after the look-ahead launch into set s; consumed[s]: after the last pass that read set s; ready: on
+        // the frame's stream once the G-buffer and the table the launches read are final.  *_ev: the one a stream has
+        // yet to wait for (null: none, or everything before it was synchronised)
+        hipEvent_t done[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr}, ready = nullptr;
+        hipEvent_t done_ev = nullptr, consumed_ev[2] = {nullptr, nullptr};
+        bool ready_ok = false;
+        uint64_t ready_epoch = 0, ready_build = 0;  // the G-buffer and table build `ready` was recorded behind
+        bool valid = false;
+        int set = 0;
+        RisAheadKey key;
+        uint64_t tuning_gen = 0;
+        uint64_t frames = 0, discards = 0;          // restir_ahead_frames, restir_ahead_discards
+        // the event the next timed_begin's launch records as its stop event when it carries no timing pair
+        hipEvent_t stop_hint = nullptr;
+        hipStream_t stop_hint_stream = nullptr;
+    } ahead;
     int cur = 0;
     uint32_t rgb_w = 0, rgb_h = 0;
     // Where the last image came from (restir_accum_add folds an image a producer wrote, and each once): rgb_serial counts
@@ -672,7 +699,8 @@ hipError_t timing_event_create(const restir_ctx* c, hipEvent_t* e) {
 restir_status timed_begin(restir_ctx* c, int kernel, Pending& p) {
     p.kernel = kernel;
     p.start = p.stop = nullptr;
-    set_launch_events(nullptr, nullptr);
+    // (a launch without a timing pair records the look-ahead's event, if one is asked for, as its stop event)
+    set_launch_events(nullptr, c->ahead.stop_hint);
     if (!c->timing || !((c->tuning.timing_mask >> kernel) & 1u)) return RESTIR_OK;
     if (c->tuning.timing_every > 1u && (c->timing_seq[kernel]++ % c->tuning.timing_every) != 0u) return RESTIR_OK;
     for (hipEvent_t* e : {&p.start, &p.stop}) {
@@ -686,7 +714,11 @@ restir_status timed_begin(restir_ctx* c, int kernel, Pending& p) {
 restir_status timed_end(restir_ctx* c, Pending& p, hipError_t launch_err) {
     const bool used = launch_events_used();
     set_launch_events(nullptr, nullptr);
+    const hipEvent_t hint = c->ahead.stop_hint;
+    c->ahead.stop_hint = nullptr;
     if (launch_err != hipSuccess) return fail(RESTIR_ERR_HIP, "kernel launch: %s", hipGetErrorString(launch_err));
+    // the look-ahead's event where the dispatch did not carry it: a timed launch (its pair went instead), or none at all
+    if (hint && (p.start || !used)) HIP_TRY(hipEventRecord(hint, c->ahead.stop_hint_stream));
     if (!p.start) return RESTIR_OK;
     if (!used) {   // nothing launched (empty region): the events were never recorded
         c->free_events.push_back(p.start);
@@ -697,9 +729,33 @@ restir_status timed_end(restir_ctx* c, Pending& p, hipError_t launch_err) {
     return RESTIR_OK;
 }
 
+// Wait for everything the context has enqueued: its stream and the look-ahead's.  Every site where something the frame
+// kernels read is about to change or be freed, or where the caller is told that the work is done, comes through here.
+hipError_t sync_streams(restir_ctx* c) {
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (c->ahead.stream) {
+        const hipError_t e2 = hipStreamSynchronize(c->ahead.stream);
+        if (e == hipSuccess) e = e2;
+    }
+    // nothing is left to wait for
+    c->ahead.done_ev = c->ahead.consumed_ev[0] = c->ahead.consumed_ev[1] = nullptr;
+    return e;
+}
+
+// Drop a look-ahead result: mark it invalid (counted) and wait for its launch -- nothing is cancelled.  For whatever
+// changes what the launch read or will write outside restir_render: a seed, a knob, the stage and halo paths, a scene.
+void ahead_drop(restir_ctx* c) {
+    if (c->ahead.valid) {
+        c->ahead.valid = false;
+        c->ahead.discards++;
+    }
+    if (c->ahead.stream) (void)hipStreamSynchronize(c->ahead.stream);
+    c->ahead.done_ev = nullptr;
+}
+
 restir_status collect_timings(restir_ctx* c) {
     if (c->pending.empty()) return RESTIR_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(sync_streams(c));
     for (Pending& p : c->pending) {
         float ms = 0.0f;
         HIP_TRY(hipEventElapsedTime(&ms, p.start, p.stop));
@@ -756,13 +812,16 @@ struct FrameBufs {
     bool records;
     size_t npx;
     uint32_t N;
+    // the plane set grid 0's handles and pdf cache lie in (1: restir_ctx::ahead's, a look-ahead result the frame took)
+    int set0 = 0;
+    const DevBuf& hnd(int i) const { return i == 0 && set0 ? c->ahead.hnd : c->hnd[i]; }
     float4* pm() const { return c->p_mat.as<float4>(); }
     DevBuf& rgb() const { return c->rgb; }
     DevBuf& uv() const { return c->uv; }
     DevBuf& vis() const { return c->vis; }
     // the sample-handle planes of rec[i]: W then M | index << 24, one 4-byte plane each (ensure_handles)
     Handles h(int i) const {
-        float* w = c->hnd[i].as<float>();
+        float* w = hnd(i).as<float>();
         return w ? Handles{w, reinterpret_cast<uint32_t*>(w + npx)} : Handles{nullptr, nullptr};
     }
     // frame handles: the same planes at the tail of rec[i] (planes layout, ensure_records), handed on with the records to
@@ -782,7 +841,7 @@ struct FrameBufs {
     float4* rb(int i) const { return c->rec[i].as<float4>() + (records ? 2 : npx * N); }
     float4* nt2() const { return records ? c->rec[1].as<float4>() : nullptr; }
     // the target-pdf cache planes (N = 1 planes layout only)
-    float* rp(int i) const { return (!records && N == 1) ? c->rp[i].as<float>() : nullptr; }
+    float* rp(int i) const { return (!records && N == 1) ? (i == 0 && set0 ? c->ahead.rp : c->rp[i]).as<float>() : nullptr; }
     const float4* pa(const restir_frame* f) const { return f->rec.as<float4>() + (records ? 1 : 0); }
     const float4* pb(const restir_frame* f) const { return f->rec.as<float4>() + (records ? 2 : npx * N); }
     Region region(Region r) const { return records ? with_records(r, N) : r; }
@@ -906,6 +965,7 @@ static void drop_shadow_vis(restir_ctx* c) {
 // replaced (a tracing frame), the lights or materials changed, another scene, a cap below its size, ris.phat off, the
 // context's end.  (hipFree waits for the kernels that read it.)
 static void drop_phat_table(restir_ctx* c) {
+    if (c->phat.p) ahead_drop(c);   // a look-ahead launch may be reading it on the other stream
     c->phat_key.valid = false;
     c->phat.release();
 }
@@ -920,8 +980,8 @@ void restir_destroy(restir_ctx* c) {
     {
         std::lock_guard<std::mutex> lk(c->mu);
         (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-        for (DevBuf* b : {&c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
+        (void)sync_streams(c);   // a look-ahead launch may still be in flight
+        for (DevBuf* b : {&c->ahead.hnd, &c->ahead.rp, &c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
                           &c->rpj_map, &c->acc.mean, &c->acc.m2, &c->acc.partials, &c->exact_nt, &c->exact_pm, &c->exact_uv,
                           &c->ref, &c->err_partials, &c->dn_nt, &c->dn_pf, &c->dn_ga, &c->dn_uv, &c->dn_tmp[0], &c->dn_tmp[1],
                           &c->dn_var[0], &c->dn_var[1]})
@@ -937,6 +997,9 @@ void restir_destroy(restir_ctx* c) {
         c->pool->close();   // frames still alive free their records themselves on release
         release_rccl(c);
         release_images(c);
+        for (hipEvent_t ev : {c->ahead.done[0], c->ahead.done[1], c->ahead.consumed[0], c->ahead.consumed[1], c->ahead.ready})
+            if (ev) (void)hipEventDestroy(ev);
+        if (c->ahead.stream) (void)hipStreamDestroy(c->ahead.stream);
         (void)hipStreamDestroy(c->stream);
     }
     delete c;
@@ -945,6 +1008,10 @@ void restir_destroy(restir_ctx* c) {
 restir_status restir_set_seed(restir_ctx* c, uint32_t seed, uint32_t frame_index) {
     if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
     std::lock_guard<std::mutex> lk(c->mu);
+    if (c->ahead.valid) {   // keyed by the seed and frame index that were: dropped, whatever the new ones are
+        HIP_TRY(hipSetDevice(c->device));
+        ahead_drop(c);
+    }
     c->seed = seed;
     c->frame_index = frame_index;
     return RESTIR_OK;
@@ -1091,7 +1158,7 @@ static restir_status upload_lights(restir_ctx* c, const restir_light* lights, ui
     std::vector<float> lcol(4 * std::max<uint32_t>(num_lights, 1), 0.0f);   // c0 of every light (kLtRegular)
     for (uint32_t i = 0; i < num_lights; i++) std::memcpy(&lcol[4 * i], &lt[28 * i + 12], 12);
     ST_TRY(c->light_col.upload(lcol.data(), lcol.size() * 4, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));   // host vectors go out of scope
+    HIP_TRY(sync_streams(c));   // host vectors go out of scope
 
     SceneDev& s = c->sdev;
     s.lights = c->lights.as<float4>();
@@ -1146,7 +1213,7 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
             return fail(RESTIR_ERR_INVALID, "mesh %u: kd_texture %u of %u textures", m, meshes[m].material.kd_texture,
                         num_textures);
     std::lock_guard<std::mutex> lk(c->mu);
-    c->gbuf.valid = false;   // another scene: the kept G-buffer is not its view
+    c->gbuf.valid = false; ahead_drop(c);   // another scene: the kept G-buffer is not its view
     HIP_TRY(hipSetDevice(c->device));
     drop_shadow_lists(c);    // ... nor are the lists its triangles' (a scene they serve builds its own)
     drop_phat_table(c);      // ... nor the p-hat table its lights' and materials'
@@ -1257,7 +1324,7 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
     const float* q_s = qn.s;
     const bool q_ok = qn.ok;
 
-    HIP_TRY(hipStreamSynchronize(c->stream));   // previous frames (either slot) may still read the old scene
+    HIP_TRY(sync_streams(c));   // previous frames (either slot) may still read the old scene
     ST_TRY(c->nodes.upload(nodes.data(), nodes.size() * 4, c->stream));
     ST_TRY(c->nodes_q.upload(nq.data(), nq.size() * 4, c->stream));
     ST_TRY(c->tri_v0.upload(v0.data(), v0.size() * 4, c->stream));
@@ -1333,7 +1400,7 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
     ST_TRY(c->level_nodes.upload(level_nodes.data(), level_nodes.size() * 4, c->stream));
     ST_TRY(c->level_start.upload(level_start.data(), level_start.size() * 4, c->stream));
     if (!refit_fits_lds(NN, (uint32_t)T)) ST_TRY(c->refit_raw.ensure((size_t)NN * 32));
-    HIP_TRY(hipStreamSynchronize(c->stream));   // host vectors go out of scope
+    HIP_TRY(sync_streams(c));   // host vectors go out of scope
     c->bvh_levels = levels;
     c->topo_q_ok = q_ok;
     for (uint32_t m = 0; m < num_meshes; m++) {
@@ -1436,7 +1503,7 @@ restir_status restir_update_meshes(restir_ctx* c, const restir_mesh_update* upda
         any_normals = any_normals || (up.normals && up.num_vertices);
     }
     HIP_TRY(hipSetDevice(c->device));
-    c->gbuf.valid = false;   // the kept G-buffer is the old geometry's: the next frame traces
+    c->gbuf.valid = false; ahead_drop(c);   // the kept G-buffer is the old geometry's: the next frame traces
     c->geom_gen = ++g_scene_gens;
     for (uint32_t u = 0; u < count; u++) {
         const restir_mesh_update& up = updates[u];
@@ -1455,7 +1522,7 @@ restir_status restir_update_meshes(restir_ctx* c, const restir_mesh_update* upda
     HIP_TRY(launch_refit_boxes(r, c->stream));
     float root[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (s.num_nodes) HIP_TRY(hipMemcpyAsync(root, c->nodes.p, sizeof(root), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's arrays may be freed on return; the root box is here
+    HIP_TRY(sync_streams(c));   // the caller's arrays may be freed on return; the root box is here
     if (s.num_nodes) {
         // quantize_nodes' grid over the new padded root; its q_ok beyond the topology's is a finite grid
         FlatBvh rootb;
@@ -1484,7 +1551,7 @@ restir_status restir_set_lights(restir_ctx* c, const restir_light* lights, uint3
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_set_lights before restir_set_scene");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));   // previous frames (either slot) may still read the old tables
+    HIP_TRY(sync_streams(c));   // previous frames (either slot) may still read the old tables
     return upload_lights(c, lights, num_lights);
 }
 
@@ -1540,7 +1607,7 @@ static restir_status render_mis(restir_ctx* c, const restir_camera* cam, const r
     if (W == 0 || H == 0) return fail(RESTIR_ERR_INVALID, "empty image %ux%u", W, H);
     ST_TRY(check_romis_window(features, W, H));
     const FeaturesDev f = to_dev(features);
-    c->gbuf.valid = false;   // k_primary writes n_t / p_mat below
+    c->gbuf.valid = false; ahead_drop(c);   // k_primary writes n_t / p_mat below
     ST_TRY(ensure_work(c, W, H, f.N, true));
     ST_TRY(ensure_mis(c, features, W, H));
     ST_TRY(c->rgb.ensure((size_t)W * H * 12));
@@ -1629,7 +1696,7 @@ static restir_status render_mis_tile(restir_ctx* c, const restir_camera* cam, co
     if (f.mode == RESTIR_MODE_ROMIS && features->save_alphas_visualisation && !c->renders_dir.empty())
         return fail(RESTIR_ERR_UNSUPPORTED, "alpha visualisation on a screen tile: the per-distribution bitmaps are whole-image files");
     const size_t vpx = (size_t)t.gwidth * t.gheight, opx = (size_t)t.width * t.height;
-    c->gbuf.valid = false;   // k_primary writes n_t / p_mat below
+    c->gbuf.valid = false; ahead_drop(c);   // k_primary writes n_t / p_mat below
     ST_TRY(ensure_work(c, t.gwidth, t.gheight, f.N, true));
     ST_TRY(ensure_mis(c, features, W, H, t.width, t.height));
     ST_TRY(c->rgb.ensure(opx * 12));
@@ -1815,6 +1882,7 @@ static restir_status ensure_phat_table(restir_ctx* c, const SceneDev& s, const R
         return RESTIR_OK;
     }
     c->phat_key.valid = false;
+    ahead_drop(c);   // the table is written or freed below: no look-ahead launch may still read it
     if (c->phat.bytes < bytes) {
         // a table that does not fit the device's memory is not an error: the frame evaluates its p-hats
         c->phat.release();
@@ -1882,6 +1950,12 @@ struct Frame {
     uint8_t *vis, *tmiss;            // alloc: the own-pixel ray plane and the tile flags, null where the plan has none
     Route last;                      // the route that produced grid cur (rp_out: its pdf cache holds its samples' pdfs)
     int cur;
+    // ris_stage: the frame may run the next frame's RIS beside its last pass (restir_ctx::ahead) -- its own key, and its
+    // RIS launch as routed, which the look-ahead repeats with the next frame's RNG key into the other plane set
+    bool ahead_ok;
+    RisAheadKey ahead_key;
+    Route ahead_route;
+    LaunchBufs ahead_b;
 
     Region pass_rect(uint32_t pass) const { return grow_rect(owned, (passes - 1u - pass) * f.R); }
     Ask pass_ask(const FramePlan& p, uint32_t pass, bool rp_ok) const {
@@ -1913,6 +1987,12 @@ struct Frame {
     }
     restir_status alloc(const FramePlan& p);
     restir_status ris_stage(const FramePlan& p);
+    restir_status ahead_prepare(const FramePlan& p, const Route& ris);
+    restir_status look_ahead();
+    void ahead_consumed_hint() {
+        c->ahead.stop_hint = c->ahead.consumed_ev[fb.set0] = c->ahead.consumed[fb.set0];
+        c->ahead.stop_hint_stream = st;
+    }
     restir_status spatial_passes(const FramePlan& p);
     restir_status hand_off(const FramePlan& p, restir_frame** out_next, float* out_rgb);
 };
@@ -2053,6 +2133,33 @@ restir_status Frame::ris_stage(const FramePlan& p) {
     } else {
         ris = route_ris(s, view, f, c->tuning, ris_ask);
     }
+    // RIS look-ahead (frames.ahead): a frame of a still view served by the table, without temporal reuse, whose passes
+    // read RIS's handles and pdf cache alone (the reservoir planes are dead) takes its RIS result from the look-ahead
+    // the last frame launched when that result is keyed as this frame is, and launches the next frame's behind its own
+    // last pass.  Any other frame, and a result keyed otherwise, runs exactly as without: the result is marked invalid
+    // and this stream waits for its launch.
+    bool took = false;
+    const uint32_t streak_now = c->gbuf_streak_lights == c->scene_gen ? c->gbuf_streak + 1u : 1u;
+    if (c->ahead.on && p.fused && !p.temporal && p.handles && ris.phat && b.phat && ris.kernel == Kernel::kGbufRis &&
+        ris.res_dead && ris.hom && ris.rp_out && !ris.dbg && !fb.records && streak_now >= c->ahead.after) {
+        ST_TRY(ahead_prepare(p, ris));
+        if (c->ahead.valid && ris_ahead_key_equal(c->ahead.key, ahead_key)) {
+            if (c->ahead.done_ev) HIP_TRY(hipStreamWaitEvent(st, c->ahead.done_ev, 0));
+            c->ahead.done_ev = nullptr;
+            c->ahead.valid = false;
+            c->ahead.frames++;
+            fb.set0 = c->ahead.set;
+            took = true;
+        }
+    }
+    if (!took) {
+        if (c->ahead.valid) {
+            c->ahead.valid = false;
+            c->ahead.discards++;
+        }
+        if (c->ahead.done_ev) HIP_TRY(hipStreamWaitEvent(st, c->ahead.done_ev, 0));
+        c->ahead.done_ev = nullptr;
+    }
     // kept by a frame that reuses it; a frame that traces replaces it once its launch is issued (any error return in
     // between leaves none)
     if (!ris_ask.gbuf_cached) c->gbuf.valid = false;
@@ -2066,7 +2173,11 @@ restir_status Frame::ris_stage(const FramePlan& p) {
         TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ris, s, view, f, b, st));
         used_prev(prev, st, c->pool.get());
     } else if (p.fused) {
-        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ris, s, view, f, b, st));
+        if (ahead_ok) {
+            ahead_route = ris;
+            ahead_b = b;
+        }
+        if (!took) TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ris, s, view, f, b, st));   // (took: grid 0 is the look-ahead's)
     } else {
         TIMED(c, RESTIR_K_PRIMARY, launch_primary(route_primary(s, view, c->tuning), s, view, b, st));
         TIMED(c, RESTIR_K_RIS, launch_ris(ris, s, view, f, b, st));
@@ -2097,6 +2208,84 @@ restir_status Frame::ris_stage(const FramePlan& p) {
     return RESTIR_OK;
 }
 
+// What an eligible frame needs of restir_ctx::ahead -- the stream (at the priority frames.ahead_prio asks), the events,
+// plane set 1 -- and the frame's own key
+restir_status Frame::ahead_prepare(const FramePlan& p, const Route& ris) {
+    auto& a = c->ahead;
+    if (a.stream && a.stream_prio != a.prio) {   // the knob changed: another stream (ahead_drop waited for the old one)
+        ahead_drop(c);
+        HIP_TRY(hipStreamDestroy(a.stream));
+        a.stream = nullptr;
+        a.ready_ok = false;
+    }
+    if (!a.stream) {
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&a.stream, hipStreamNonBlocking, a.prio ? least : 0));
+        a.stream_prio = a.prio;
+    }
+    // (the events a launch records within its dispatch, as the timing pairs are: timing_event_create)
+    for (hipEvent_t* e : {&a.done[0], &a.done[1], &a.consumed[0], &a.consumed[1], &a.ready})
+        if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableSystemFence));
+    const size_t px = (size_t)t.gwidth * t.gheight;
+    if (a.hnd.bytes < c->hnd[0].bytes || a.rp.bytes < px * 4) {
+        ahead_drop(c);   // (a result in the smaller planes)
+        ST_TRY(a.hnd.ensure(c->hnd[0].bytes));
+        ST_TRY(a.rp.ensure(px * 4));
+    }
+    RisAheadKey k;
+    k.seed = c->seed; k.frame = frame;
+    k.gbuf_epoch = c->gbuf_epoch; k.scene_gen = c->scene_gen; k.geom_gen = c->geom_gen; k.phat_build = c->phat_builds;
+    static_assert(sizeof(k.cam) == sizeof(c->gbuf.cam) && sizeof(k.tile) == sizeof(restir_tile) &&
+                  sizeof(k.features) == sizeof(FeaturesDev), "RisAheadKey holds the view's and the features' words");
+    std::memcpy(k.cam, c->gbuf.cam, sizeof(k.cam));
+    k.width = width; k.height = height;
+    std::memcpy(k.tile, &t, sizeof(k.tile));
+    k.tex_on = s.tex_on;
+    std::memcpy(k.features, &f, sizeof(k.features));
+    k.passes = passes;
+    k.route_grid = ris.grid; k.route_lds = (uint32_t)ris.lds;
+    k.route_bits = (ris.how ? 1u : 0u) | (ris.hom ? 2u : 0u) | (ris.res_dead ? 4u : 0u) | (ris.flags ? 8u : 0u) | (ris.skip & 3u) << 4 |
+                   (ris.rp_out ? 64u : 0u) | (ris.staged ? 128u : 0u) | (ris.mode & 3u) << 8 | (ris.map2d & 3u) << 10 |
+                   ((uint32_t)ris.lt & 7u) << 12 | (ris.n & 3u) << 15 | (p.skip_mode & 3u) << 17;
+    k.tuning_gen = a.tuning_gen;
+    ahead_key = k;
+    ahead_ok = true;
+    return RESTIR_OK;
+}
+
+// The next frame's RIS on the look-ahead stream, into the plane set this frame does not read: this frame's own launch
+// again under the key (seed, frame + 1, RIS, 0).  It reads the kept G-buffer, the tile flags and the table, which no
+// frame kernel writes while they stand, and writes planes whose last reader's event it waits for.
+restir_status Frame::look_ahead() {
+    auto& a = c->ahead;
+    const int wset = ris_ahead_other_set(fb.set0);
+    if (!a.ready_ok || a.ready_epoch != c->gbuf_epoch || a.ready_build != c->phat_builds) {
+        // the G-buffer and the table were written on the frame's stream: once per build
+        HIP_TRY(hipEventRecord(a.ready, st));
+        HIP_TRY(hipStreamWaitEvent(a.stream, a.ready, 0));
+        a.ready_ok = true;
+        a.ready_epoch = c->gbuf_epoch;
+        a.ready_build = c->phat_builds;
+    }
+    if (a.consumed_ev[wset]) HIP_TRY(hipStreamWaitEvent(a.stream, a.consumed_ev[wset], 0));
+    a.consumed_ev[wset] = nullptr;
+    LaunchBufs b = ahead_b;
+    b.key = restir_rng_key(c->seed, frame + 1u, RESTIR_STAGE_RIS, 0);
+    FrameBufs out = fb;
+    out.set0 = wset;
+    b.hout = out.h(0);
+    b.rp_out = out.rp(0);
+    a.stop_hint = a.done[wset];
+    a.stop_hint_stream = a.stream;
+    TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ahead_route, s, view, f, b, a.stream));
+    a.done_ev = a.done[wset];
+    a.set = wset;
+    a.key = ris_ahead_next(ahead_key);
+    a.valid = true;
+    return RESTIR_OK;
+}
+
 // For each pass: route, launch, from grid cur into its partner; then final shading unless the last pass ran it
 restir_status Frame::spatial_passes(const FramePlan& p) {
     LaunchBufs b;
@@ -2123,6 +2312,8 @@ restir_status Frame::spatial_passes(const FramePlan& p) {
             }
         }
         if (pass + 1 == passes) b.hout = fb.fh(nxt);   // (frame_handles; the route names them)
+        // the frame's last launch records the event the look-ahead's next write of grid 0's plane set waits for
+        if (ahead_ok && pass + 1 == passes && last.final_done) ahead_consumed_hint();
         TIMED(c, RESTIR_K_SPATIAL, launch_spatial(last, s, pr, f, b, st));
         cur = nxt;
     }
@@ -2133,6 +2324,7 @@ restir_status Frame::spatial_passes(const FramePlan& p) {
         b = fb.bufs(camd, 0u, cur, cur);
         b.vis = vis;
         b.flags = tmiss;
+        if (ahead_ok) ahead_consumed_hint();
         TIMED(c, RESTIR_K_FINAL, launch_final(route_final(s, owned, f, c->tuning, fin_ask), s, owned, f, b, st));
     }
     c->cur = cur;
@@ -2192,6 +2384,8 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
     if (features->temporal_reuse && prev != nullptr)
         ST_TRY(check_prev(c, prev, fr.N, t, width, height, "frame's region", fr.passes > 0));
 
+    // (another view size may reallocate planes a look-ahead launch reads or writes)
+    if (t.gwidth != c->vw || t.gheight != c->vh || fr.N != c->N) ahead_drop(c);
     ST_TRY(ensure_records(c, t.gwidth, t.gheight, fr.N, fr.fb));
     c->stage_ok = false;   // ensure_records re-sized the shared view state: the stage API must be reconfigured
     ST_TRY(fr.fb.rgb().ensure((size_t)t.width * t.height * 12));
@@ -2207,7 +2401,10 @@ restir_status restir_render(restir_ctx* c, const restir_camera* cam, const resti
     const FramePlan p = plan_frame(fr);
     ST_TRY(fr.alloc(p));
     ST_TRY(fr.ris_stage(p));
+    // the next frame's RIS beside this frame's last pass (frames.ahead; 2: enqueued before the pass, 1: after it)
+    if (fr.ahead_ok && c->ahead.on == 2u) ST_TRY(fr.look_ahead());
     ST_TRY(fr.spatial_passes(p));
+    if (fr.ahead_ok && c->ahead.on != 2u) ST_TRY(fr.look_ahead());
     c->image_produced();   // the last pass wrote the image
     return fr.hand_off(p, out_next, out_rgb);
 }
@@ -2441,7 +2638,7 @@ restir_status restir_synchronize(restir_ctx* c) {
     if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(sync_streams(c));
     return RESTIR_OK;
 }
 
@@ -3236,7 +3433,7 @@ restir_status restir_denoise_guide_builds(restir_ctx* c, uint64_t* out) {
 restir_status restir_stage_configure(restir_ctx* c, uint32_t width, uint32_t height, uint32_t n) {
     if (!c || width == 0 || height == 0 || n < 1 || n > RESTIR_MAX_N) return fail(RESTIR_ERR_INVALID, "bad stage size");
     std::lock_guard<std::mutex> lk(c->mu);
-    c->gbuf.valid = false;   // the stages write the frame path's G-buffer planes
+    c->gbuf.valid = false; ahead_drop(c);   // the stages write the frame path's G-buffer planes
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(ensure_work(c, width, height, n, true));
     ST_TRY(c->rgb.ensure((size_t)width * height * 12));
@@ -3278,7 +3475,7 @@ static restir_status stage_buffer(restir_ctx* c, restir_buffer which, DevBuf** o
 restir_status restir_stage_upload(restir_ctx* c, restir_buffer which, const void* host, size_t bytes) {
     if (!c || !host) return fail(RESTIR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    c->gbuf.valid = false;
+    c->gbuf.valid = false; ahead_drop(c);
     if (!c->stage_ok) return fail(RESTIR_ERR_STATE, "restir_stage_configure first");
     DevBuf* b;
     size_t need;
@@ -3294,7 +3491,7 @@ restir_status restir_stage_upload(restir_ctx* c, restir_buffer which, const void
 restir_status restir_stage_download(restir_ctx* c, restir_buffer which, void* host, size_t bytes) {
     if (!c || !host) return fail(RESTIR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    c->gbuf.valid = false;   // (stage_buffer may allocate the uv plane)
+    c->gbuf.valid = false; ahead_drop(c);   // (stage_buffer may allocate the uv plane)
     if (!c->stage_ok) return fail(RESTIR_ERR_STATE, "restir_stage_configure first");
     DevBuf* b;
     size_t need;
@@ -3309,7 +3506,7 @@ restir_status restir_stage_download(restir_ctx* c, restir_buffer which, void* ho
 #define STAGE_PRELUDE()                                                             \
     if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");                         \
     std::lock_guard<std::mutex> lk(c->mu);                                          \
-    c->gbuf.valid = false;                                                          \
+    c->gbuf.valid = false; ahead_drop(c);                                                        \
     if (!c->stage_ok) return fail(RESTIR_ERR_STATE, "restir_stage_configure first"); \
     if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_set_scene first");      \
     HIP_TRY(hipSetDevice(c->device));                                               \
@@ -3574,6 +3771,20 @@ restir_status restir_phat_builds(restir_ctx* c, uint64_t* out_builds) {
     return RESTIR_OK;
 }
 
+restir_status restir_ahead_frames(restir_ctx* c, uint64_t* out_frames) {
+    if (!c || !out_frames) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out_frames = c->ahead.frames;
+    return RESTIR_OK;
+}
+
+restir_status restir_ahead_discards(restir_ctx* c, uint64_t* out_discards) {
+    if (!c || !out_discards) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out_discards = c->ahead.discards;
+    return RESTIR_OK;
+}
+
 // restir_debug_phat between its buffer's allocation and its release
 static restir_status debug_phat_run(restir_ctx* c, const PhatTableDev& d, uint32_t light, size_t n, DevBuf& bo, float* out) {
     ST_TRY(bo.ensure(n * sizeof(float)));
@@ -3747,7 +3958,7 @@ restir_status restir_halo_begin_layout(restir_ctx* c, const restir_camera* cam, 
     ST_TRY(check_features(features));
     ST_TRY(layout_check(layout));
     std::lock_guard<std::mutex> lk(c->mu);
-    c->gbuf.valid = false;   // a halo frame writes the same G-buffer planes and flags (and keeps the tracing kernels)
+    c->gbuf.valid = false; ahead_drop(c);   // a halo frame writes the same G-buffer planes and flags (and keeps the tracing kernels)
     if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_halo_begin before restir_set_scene");
     HIP_TRY(hipSetDevice(c->device));
     const FeaturesDev f = to_dev(features);
@@ -4279,10 +4490,10 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     // a cache is built -- none of them reaches a kernel's arguments or launch shape, so no stored byte of the G-buffer,
     // the tile flags, the shadow lists or the visibility bits can differ (DESIGN.md §6 "Knobs that keep the caches")
     static const char* const kKeepsCaches[] = {"timing.mask", "timing.every", "timing.fence", "final.lists_after", "final.vis_after",
-                                              "ris.phat_after"};
+                                              "ris.phat_after", "frames.ahead_after"};
     bool keeps = false;
     for (const char* k : kKeepsCaches) keeps = keeps || !std::strcmp(key, k);
-    if (!keeps) c->gbuf.valid = false;
+    if (!keeps) { c->gbuf.valid = false; ahead_drop(c); c->ahead.tuning_gen++; }
     Tuning& t = c->tuning;
     const uint32_t v = (uint32_t)value;
     if (!std::strcmp(key, "primary.lds")) t.primary_lds = v;
@@ -4337,6 +4548,9 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     }
     else if (!std::strcmp(key, "ris.phat_after")) { if (v < 1) return fail(RESTIR_ERR_INVALID, "ris.phat_after: >= 1"); t.ris_phat_after = v; }
     else if (!std::strcmp(key, "ris.phat_max_mb")) t.ris_phat_max_mb = v;
+    else if (!std::strcmp(key, "frames.ahead")) { if (v > 2) return fail(RESTIR_ERR_INVALID, "frames.ahead: 0 (off), 1 or 2 (RIS enqueued first)"); c->ahead.on = v; }
+    else if (!std::strcmp(key, "frames.ahead_after")) { if (v < 1) return fail(RESTIR_ERR_INVALID, "frames.ahead_after: >= 1"); c->ahead.after = v; }
+    else if (!std::strcmp(key, "frames.ahead_prio")) { if (v > 1) return fail(RESTIR_ERR_INVALID, "frames.ahead_prio: 0 or 1"); c->ahead.prio = v; }
     else if (!std::strcmp(key, "primary.tl")) t.primary_tl = v;
     else if (!std::strcmp(key, "gbuf.reuse")) t.gbuf_reuse = v;
     else if (!std::strcmp(key, "mis.chunk")) t.mis_chunk = v;   // applies from the next ensure_mis

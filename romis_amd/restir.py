@@ -557,6 +557,19 @@ class Renderer:
         check(self.lib, self.lib.restir_phat_builds(self.ctx, C.byref(n)), "restir_phat_builds")
         return int(n.value)
 
+    def ahead_frames(self) -> int:
+        """render_restir frames so far that took their RIS result from the look-ahead the frame before launched
+        (restir_ahead_frames; tuning "frames.ahead")."""
+        n = C.c_uint64()
+        check(self.lib, self.lib.restir_ahead_frames(self.ctx, C.byref(n)), "restir_ahead_frames")
+        return int(n.value)
+
+    def ahead_discards(self) -> int:
+        """Look-ahead results so far that no frame took (restir_ahead_discards)."""
+        n = C.c_uint64()
+        check(self.lib, self.lib.restir_ahead_discards(self.ctx, C.byref(n)), "restir_ahead_discards")
+        return int(n.value)
+
     def debug_phat(self, light: int, width: int, height: int):
         """[height][width] float32 plane of the last frame's view: the stored target pdf of point light `light` at every
         pixel, -1 where none is held (restir_debug_phat)."""
