@@ -720,6 +720,103 @@ restir_status restir_denoise_lum_host(const float* rgb, const float* var /* null
                                       const restir_denoise_lum_params* params, float* out_rgb, float* out_var /* nullable */);
 restir_status restir_denoise_lum_variance_download(restir_ctx* ctx, float* var, size_t count);   /* the last call's final variance plane; synchronises */
 
+/* ---- a reprojected image history: accumulating while the camera moves ----------------------------------------
+ * restir_accum_* folds pixel p into pixel p and so needs a still view.  The history keeps, per pixel, a mean, the
+ * population variance S of the samples and a sample count n, and every restir_history_advance moves them to the new
+ * camera before it folds the last image in: the temporal half of SVGF (Schied et al. 2017).  restir_history_denoise runs
+ * restir_denoise_lum's levels over the mean with a variance plane taken from S.  Every step below is one float32
+ * operation without contraction, divide and sqrt correctly rounded; the pure host functions are the kernels' own text
+ * (csrc/history.h), bit for bit.
+ * Record.  Per pixel: (N unnormalised, t) as the G-buffer's n_t holds it, the material's bits clamped to the miss material
+ * (every index at or above it is a miss), mean.rgb, S.rgb and n.  Two sets of three 16-byte planes, 96 bytes per pixel,
+ * 190 MiB at 1920 x 1080, allocated by the first advance and freed by restir_history_end.
+ * Rows.  G-buffer records -- n_t, p_mat, kept_n_t, kept_material, and the map with the indices in it -- are in G-buffer
+ * rows (y = 0 at the bottom) like restir_frame_reproject's; the image, mean, S, n and the variance plane are in image rows
+ * (row 0 = top).  Image row r is G-buffer row h - 1 - r.
+ * Advance, per pixel p of the new view, whose current record (N, t, P, material) is the new camera's G-buffer record:
+ *   1. restir_frame_reproject's steps 1 - 5 with reasons 0 - 5 unchanged.  The predecessor's camera is the camera of the
+ *      advance before; the predecessor's record at the source pixel q is the one the history kept from that advance --
+ *      nothing is traced a second time.
+ *   2. reason 6 (material), tested after reason 5: the kept material at q differs from the current one.
+ *   3. reason 7 (no history), tested last: the kept record at q has n == 0.  On the first advance after
+ *      restir_history_begin and the first after a reset nothing is kept and every pixel is reason 7, the misses included.
+ *   4. On any reason the gathered state is the empty one, (mean, S, n) = (+0, +0, 0); otherwise the kept one at q.
+ *   5. The fold of x, the last image at p.  When all of x.rgb are finite:  n' = min(n + 1, max_frames);
+ *      a = 1.0f / (float)n';  per channel  d = x - mean;  mean' = mean + d a;  dd = d d;  t = a dd;  u = S + t;
+ *      om = 1.0f - a;  S' = om u.  Below the cap mean' is restir_accum_fold's mean, the same operations, and S' is its
+ *      m2 / n; with the cap reached both are exponential averages with alpha = 1 / max_frames.  When a component of x is
+ *      not finite the gathered state passes through; an empty one then takes x's bits as its mean with S = +0 and n' = 0,
+ *      which the next advance treats as empty (reason 7).
+ *   6. (N, t, material of the current record, mean', S', n') are stored at p of the other set.
+ * out_map (nullable, host, W H words) follows restir_frame_reproject's convention: the flat G-buffer-row index of q, or
+ * 0xFFFFFFFF - reason.  With it the call synchronises; without, it only enqueues.
+ * The image follows restir_accum_add's producer rules: it must be an image a producer wrote, each is folded once, a
+ * resolve's or a denoiser's result and a halo frame are refused.  The "folded already" mark is the history's own: one
+ * image may go to restir_accum_add and to restir_history_advance.  cam is the camera the image was rendered with.  The
+ * current records come from restir_denoise's guide planes: a view is traced once across restir_history_advance,
+ * restir_denoise and restir_denoise_lum, and restir_denoise_guide_builds counts it.  The call consumes no frame index,
+ * leaves the image, the kept G-buffer, the tile flags, the shadow lists, the visibility bits, the p-hat table and the RIS
+ * look-ahead untouched, and has no RESTIR_K_* slot.  Whole images only: a last image whose size is not width x height (a
+ * screen tile's) is RESTIR_ERR_UNSUPPORTED.
+ * restir_history_resolve writes the mean (tone mapped by `tone`, or its bits) as the context's image, marked like
+ * restir_accum_resolve's.  restir_history_denoise is restir_denoise_lum over the mean -- exactly resolve(NULL)'s bits,
+ * whatever the last image is -- for the last advance's view; params->variance_source is checked and otherwise ignored.
+ * Its initial variance plane: a pixel whose mean is finite and whose n >= spatial_below has
+ *     inv = 1.0f / (float)(n - 1);  v = restir_denoise_lum's ACCUM expression with m2 = S  (s.j = sqrtf(S.j inv), ...)
+ * and every other pixel RESTIR_DENOISE_VAR_SPATIAL's estimate at p over the mean image with params->geo.  Under a reached
+ * cap S / (n - 1) over-states an exponential average's variance of the mean, by up to about 2 x (the steady-state factor
+ * is a / (2 - a) of S); the bias is conservative.  The result is marked like restir_denoise's and
+ * restir_denoise_lum_variance_download serves its final plane.  The host equivalent is restir_denoise_lum_host(mean,
+ * var = restir_history_variance_host(...)).
+ * Resets.  restir_set_scene (and _textured) and restir_update_meshes empty the history -- the kept records describe
+ * geometry that has moved --: the next advance is all reason 7, resolve and denoise are RESTIR_ERR_STATE until then, and
+ * `resets` counts it.  The size stays.  restir_set_lights does not reset: the history then lags the lighting by about
+ * max_frames frames.
+ * Errors, all found before anything is written.  RESTIR_ERR_INVALID: a NULL argument, max_frames outside 1 ..
+ * RESTIR_ACCUM_MAX_FRAMES, spatial_below < 2, flags or reserved != 0, an empty size, a camera whose derived frame is not
+ * finite, a download buffer below W H pixels, a map entry outside the image (restir_history_fold).  RESTIR_ERR_STATE: no
+ * scene, no open history, no image, a halo frame, a size other than the history's (the first advance's), an image folded
+ * already, a resolved or denoised image, resolve / denoise / download before the first advance (or the first after a
+ * reset).  RESTIR_ERR_HIP: an allocation the device refuses; it closes the history.
+ * restir_history_map_host: kept_n_t, kept_material and kept_n all NULL describe a history with nothing kept (all reason 7).
+ * restir_history_download is a test hook (each of mean, S, n nullable) and synchronises.
+ * Tuning "history.var_fused" (1, the default: one launch writes the mean image and the variance plane, running the spatial
+ * estimate only for the pixels that take it; 0: the spatial estimate over the whole mean image, the history's entries
+ * written over it, three launches): the same bits either way; the knob touches no frame and keeps the still view's caches. */
+typedef struct restir_history_params {
+    uint32_t max_frames;     /* 1 .. RESTIR_ACCUM_MAX_FRAMES: the count's cap, alpha's floor 1 / max_frames.  The default is 8 after the
+                              * sweep of {8, 16, 32, 64} x spatial_below {2, 4, 8} at 1920 x 1080 under a 0.1 degree per frame yaw: the
+                              * source pixel is the nearest one, so every advance displaces the history by up to half a pixel and a
+                              * longer history drifts further -- at frame 64 the filtered C2 result has MSE 0.233 / rel_mse 0.0021 at
+                              * 8, 0.346 / 0.0177 at 16, 0.620 / 0.117 at 32, 0.846 / 0.201 at 64; spatial_below does not separate
+                              * (README "Image history") */
+    uint32_t spatial_below;  /* >= 2: pixels with fewer samples take the spatial variance estimate */
+    uint32_t flags;          /* 0 */
+    uint32_t reserved;       /* 0 */
+} restir_history_params;
+void          restir_history_params_default(restir_history_params* out);   /* 8, 4, 0, 0 */
+restir_status restir_history_begin(restir_ctx* ctx, const restir_history_params* params);
+restir_status restir_history_advance(restir_ctx* ctx, const restir_camera* cam, uint32_t width, uint32_t height,
+                                     uint32_t* out_map /* nullable, host, W*H words: synchronises when given */);
+restir_status restir_history_resolve(restir_ctx* ctx, const restir_features* tone /* nullable */);
+restir_status restir_history_denoise(restir_ctx* ctx, const restir_denoise_lum_params* params,
+                                     const restir_features* tone /* nullable */, float* out_rgb /* nullable */);
+restir_status restir_history_download(restir_ctx* ctx, float* mean, float* S, uint32_t* n, size_t pixels);
+restir_status restir_history_frames(restir_ctx* ctx, uint64_t* advances, uint64_t* resets);
+restir_status restir_history_end(restir_ctx* ctx);
+/* pure host, the kernel's own text */
+restir_status restir_history_fold(const float* mean_in, const float* S_in, const uint32_t* n_in, const uint32_t* map,
+                                  const float* x, uint32_t w, uint32_t h, uint32_t max_frames,
+                                  float* mean_out, float* S_out, uint32_t* n_out);
+restir_status restir_history_map_host(const restir_camera_frame* prev_cam, uint32_t w, uint32_t h,
+                                      const float* cur_n_t, const float* cur_p_mat,
+                                      const float* kept_n_t, const uint32_t* kept_material, const uint32_t* kept_n,
+                                      uint32_t miss_material, uint32_t* map);
+restir_status restir_history_variance_host(const float* mean, const float* S, const uint32_t* n,
+                                           const float* n_t, const float* p_mat, uint32_t w, uint32_t h,
+                                           uint32_t miss_material, const restir_history_params* params,
+                                           const restir_denoise_params* geo, float* var);
+
 /* ---- stage-level access for parity tests and profiling ---------------------------------------------- *
  * Buffers are the device SoA layout (DESIGN.md "Data layout"), one entry per pixel of the computed region
  * (row-major, y = 0 bottom), and for reservoirs [N][pixels]:

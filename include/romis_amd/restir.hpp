@@ -52,6 +52,11 @@ struct DenoiseLumParams : restir_denoise_lum_params {
     DenoiseLumParams() { restir_denoise_lum_params_default(this); }
 };
 
+// restir_history_params with its defaults (a cap of 8 samples, the spatial variance estimate below 4)
+struct HistoryParams : restir_history_params {
+    HistoryParams() { restir_history_params_default(this); }
+};
+
 // The reference's own struct Features (src/utils/common.h:89-136) -> Features, field by field by the reference's
 // member names (any type with those members works, so the reference's header is not needed here).  The enums
 // keep their values: RayTraceMode {ReSTIR, RMIS, ROMIS} (common.h:25-29) = restir_mode,
@@ -425,6 +430,34 @@ public:
         check(restir_denoise_guide_builds(ctx_, &n), "restir_denoise_guide_builds");
         return n;
     }
+    // a reprojected image history (restir_history_*): a per-pixel mean, variance and sample count that follow the camera.
+    // The viewer loop, tone mapping off until the last step: render, historyAdvance(camera the frame was rendered with),
+    // historyDenoise(params, &tone), present
+    void historyBegin(const HistoryParams& params = HistoryParams()) { check(restir_history_begin(ctx_, &params), "restir_history_begin"); }
+    // only enqueues; with map (width x height words, rows y = 0 bottom: the source pixel's flat index or 0xFFFFFFFF - reason)
+    // it synchronises
+    void historyAdvance(const Camera& camera, uint32_t width, uint32_t height, uint32_t* map = nullptr) {
+        check(restir_history_advance(ctx_, &camera, width, height, map), "restir_history_advance");
+    }
+    void historyResolve(const Features* tone = nullptr) { check(restir_history_resolve(ctx_, tone), "restir_history_resolve"); }
+    void historyDenoise(const DenoiseLumParams& params = DenoiseLumParams(), const Features* tone = nullptr, float* rgb = nullptr) {
+        check(restir_history_denoise(ctx_, &params, tone, rgb), "restir_history_denoise");
+    }
+    // Test hook (restir_history_download): mean and S width x height x 3 floats, n width x height words, image rows
+    void historyState(std::vector<float>& mean, std::vector<float>& S, std::vector<uint32_t>& n, uint32_t width, uint32_t height) {
+        const size_t px = size_t(width) * height;
+        mean.assign(px * 3, 0.0f);
+        S.assign(px * 3, 0.0f);
+        n.assign(px, 0u);
+        check(restir_history_download(ctx_, mean.data(), S.data(), n.data(), px), "restir_history_download");
+    }
+    // (advances, resets) since historyBegin
+    std::pair<uint64_t, uint64_t> historyFrames() const {
+        uint64_t a = 0, r = 0;
+        check(restir_history_frames(ctx_, &a, &r), "restir_history_frames");
+        return {a, r};
+    }
+    void historyEnd() { check(restir_history_end(ctx_), "restir_history_end"); }
     restir_ctx* handle() const { return ctx_; }
 
 private:

@@ -188,6 +188,17 @@ RESTIR_DENOISE_VAR_SPATIAL = 0
 RESTIR_DENOISE_VAR_ACCUM = 1
 assert C.sizeof(DenoiseLumParams) == 28
 
+
+class HistoryParams(C.Structure):
+    """restir_history_params: the image history's sample cap and the count below which a pixel takes the spatial variance."""
+    _fields_ = [("max_frames", C.c_uint32), ("spatial_below", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# restir_history_advance's reasons beyond restir_frame_reproject's 0 .. 5
+RESTIR_HISTORY_REASON_MATERIAL = 6
+RESTIR_HISTORY_REASON_NO_HISTORY = 7
+assert C.sizeof(HistoryParams) == 16
+
 RESTIR_MAX_TILES_X = 16
 RESTIR_MAX_TILES_Y = 16
 
@@ -321,6 +332,23 @@ SIGNATURES = {
                                           C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DenoiseLumParams), C.POINTER(C.c_float),
                                           C.POINTER(C.c_float)]),
     "restir_denoise_lum_variance_download": (C.c_int, [_P, C.POINTER(C.c_float), C.c_size_t]),
+    "restir_history_params_default": (None, [C.POINTER(HistoryParams)]),
+    "restir_history_begin": (C.c_int, [_P, C.POINTER(HistoryParams)]),
+    "restir_history_advance": (C.c_int, [_P, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "restir_history_resolve": (C.c_int, [_P, C.POINTER(Features)]),
+    "restir_history_denoise": (C.c_int, [_P, C.POINTER(DenoiseLumParams), C.POINTER(Features), C.POINTER(C.c_float)]),
+    "restir_history_download": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_size_t]),
+    "restir_history_frames": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "restir_history_end": (C.c_int, [_P]),
+    "restir_history_fold": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "restir_history_map_host": (C.c_int, [C.POINTER(CameraFrame), C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
+                                          C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                          C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "restir_history_variance_host": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.POINTER(HistoryParams), C.POINTER(DenoiseParams), C.POINTER(C.c_float)]),
     "restir_stage_configure": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "restir_stage_upload": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     "restir_stage_download": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),

@@ -39,6 +39,7 @@ ABI_UNITS = [
     ("abi_error.cpp", ["-x", "c++"]),            # no HIP header
     ("layout.cpp", ["-x", "c++"]),
     ("denoise_host.cpp", ["-x", "c++"]),         # no HIP header, no HIP call: a stand-alone program links it
+    ("history_host.cpp", ["-x", "c++"]),         # likewise
 ]
 
 SOURCES = [("kernels.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS)] + ABI_UNITS + [
@@ -52,11 +53,12 @@ SOURCES = [("kernels.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS)] + ABI_UNITS +
     ("accum.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("exact.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("denoise.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
+    ("history.hip", ["-x", "hip"] + DEVICE + KERNEL_FLAGS),
     ("bvh.cpp", ["-x", "c++"]),
     ("screen.cpp", ["-x", "c++"]),
 ]
 HEADERS = ["device_math.h", "restir_types.h", "launch.h", "bvh.h", "pow10_table.h", "kernels_common.h", "launch_events.h", "launch_shape.h",
-           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "shadow_vis.h", "phat_table.h", "abi_error.h", "layout.h", "halo_segs.h", "present.h", "accum.h", "exact.h", "denoise.h", "ris_ahead.h"]
+           "route.h", "ris_members.h", "refit.h", "reproject.h", "shadow_lists.h", "shadow_vis.h", "phat_table.h", "abi_error.h", "layout.h", "halo_segs.h", "present.h", "accum.h", "exact.h", "denoise.h", "ris_ahead.h", "history.h"]
 
 
 def source_hash() -> str:
@@ -238,7 +240,7 @@ CPP_PROGRAMS = [("render_scene.cpp", "render_scene"), ("render_threads.cpp", "re
                 ("write_outputs.cpp", "write_outputs"), ("update_scene.cpp", "update_scene"),
                 ("present_frames.cpp", "present_frames"), ("accumulate_frames.cpp", "accumulate_frames"),
                 ("exact_image.cpp", "exact_image"), ("denoise_frames.cpp", "denoise_frames"),
-                ("denoise_lum_frames.cpp", "denoise_lum_frames")]
+                ("denoise_lum_frames.cpp", "denoise_lum_frames"), ("history_frames.cpp", "history_frames")]
 CPP_DIR = os.path.join(ROOT, "tests", "cpp")
 
 

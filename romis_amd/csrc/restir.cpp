@@ -7,6 +7,7 @@
 #include "accum.h"
 #include "denoise.h"
 #include "exact.h"
+#include "history.h"
 #include "layout.h"
 
 #include <rccl/rccl.h>
@@ -44,6 +45,7 @@ namespace romis {
 bool write_bmp_words(const char* path, uint32_t width, uint32_t height, const uint32_t* words);   // screen.cpp
 restir_status denoise_params_check(const restir_denoise_params* p, const char* who);               // denoise_host.cpp
 restir_status denoise_lum_params_check(const restir_denoise_lum_params* p, const char* who);
+restir_status history_params_check(const restir_history_params* p, const char* who);                 // history_host.cpp
 }
 using namespace romis;
 
@@ -474,6 +476,30 @@ struct restir_ctx {
     DevBuf dn_var[2];
     uint32_t dn_var_last = 0;
     size_t dn_var_px = 0;
+
+    // the reprojected image history (restir_history_*, history.h), behind everything a frame reads like the denoiser,
+    // whose guide planes give it the current view's records.  planes: two sets of three 16-byte planes of width x height
+    // pixels (set k's (N, t), (mean, n), (S, material) at planes 3 k ..), sized by the first advance.  have: set `set`
+    // holds what the last advance kept, for camera `cam` (false: the next advance is all reason 7).  added_serial is the
+    // history's own "folded already" mark (rgb_serial of the last image folded; 0: none), apart from acc's.
+    struct {
+        bool open = false, have = false;
+        uint32_t var_fused = 1;   // tuning history.var_fused: the variance plane in one launch (0: three)
+        restir_history_params params{};
+        uint32_t width = 0, height = 0;
+        int set = 0;
+        uint64_t added_serial = 0;
+        uint64_t advances = 0, resets = 0;
+        restir_camera cam{};
+        DevBuf planes, map;
+    } hist;
+    // the geometry changed (restir_set_scene, restir_update_meshes): the kept records describe surfaces that have moved
+    void history_reset() {
+        if (hist.open && hist.have) {
+            hist.have = false;
+            hist.resets++;
+        }
+    }
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -984,7 +1010,7 @@ void restir_destroy(restir_ctx* c) {
         for (DevBuf* b : {&c->ahead.hnd, &c->ahead.rp, &c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
                           &c->rpj_map, &c->acc.mean, &c->acc.m2, &c->acc.partials, &c->exact_nt, &c->exact_pm, &c->exact_uv,
                           &c->ref, &c->err_partials, &c->dn_nt, &c->dn_pf, &c->dn_ga, &c->dn_uv, &c->dn_tmp[0], &c->dn_tmp[1],
-                          &c->dn_var[0], &c->dn_var[1]})
+                          &c->dn_var[0], &c->dn_var[1], &c->hist.planes, &c->hist.map})
             b->release();
         drop_shadow_lists(c);
         drop_phat_table(c);
@@ -1452,6 +1478,7 @@ restir_status restir_set_scene_textured(restir_ctx* c, const restir_mesh* meshes
         for (size_t i = 0; i < nv->size(); i++)
             if ((i % 4) != 3 && !(std::fabs((*nv)[i]) <= 0x1p125f)) s.normals_bounded = 0u;
     c->geom_gen = ++g_scene_gens;
+    c->history_reset();
     c->has_scene = true;
     return RESTIR_OK;
 }
@@ -1505,6 +1532,7 @@ restir_status restir_update_meshes(restir_ctx* c, const restir_mesh_update* upda
     HIP_TRY(hipSetDevice(c->device));
     c->gbuf.valid = false; ahead_drop(c);   // the kept G-buffer is the old geometry's: the next frame traces
     c->geom_gen = ++g_scene_gens;
+    c->history_reset();
     for (uint32_t u = 0; u < count; u++) {
         const restir_mesh_update& up = updates[u];
         restir_ctx::MeshKeep& mk = c->mesh_keep[up.mesh];
@@ -3429,6 +3457,235 @@ restir_status restir_denoise_guide_builds(restir_ctx* c, uint64_t* out) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// the reprojected image history (include/restir_c.h "a reprojected image history", history.h, DESIGN.md §6 "Image
+// history").  Like the denoiser, nothing here reads or writes the frame path's G-buffer planes or what is built over
+// them, the frame index or the stage buffers; an advance leaves the image as it is.
+static void history_close(restir_ctx* c) {
+    auto& hs = c->hist;
+    hs.open = hs.have = false;
+    hs.width = hs.height = 0;
+    hs.planes.release();
+    hs.map.release();
+}
+
+restir_status restir_history_begin(restir_ctx* c, const restir_history_params* params) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    ST_TRY(history_params_check(params, "restir_history_begin"));
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto& hs = c->hist;
+    hs.open = true;
+    hs.have = false;
+    hs.params = *params;
+    hs.width = hs.height = 0;
+    hs.set = 0;
+    hs.added_serial = 0;
+    hs.advances = hs.resets = 0;
+    return RESTIR_OK;
+}
+
+restir_status restir_history_advance(restir_ctx* c, const restir_camera* cam, uint32_t width, uint32_t height, uint32_t* out_map) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (!cam) return fail(RESTIR_ERR_INVALID, "restir_history_advance: camera is NULL");
+    if (width == 0 || height == 0) return fail(RESTIR_ERR_INVALID, "restir_history_advance: empty image %ux%u", width, height);
+    restir_camera_frame cf;
+    restir_camera_derive(cam, &cf);
+    if (!camera_frame_finite(cf)) return fail(RESTIR_ERR_INVALID, "restir_history_advance: the camera's derived frame is not finite");
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto& hs = c->hist;
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_history_advance before restir_set_scene");
+    if (!hs.open) return fail(RESTIR_ERR_STATE, "restir_history_advance before restir_history_begin");
+    if (c->halo.active) return fail(RESTIR_ERR_STATE, "restir_history_advance between restir_halo_begin and restir_halo_end");
+    if (c->rgb_from == restir_ctx::RGB_RESOLVED)
+        return fail(RESTIR_ERR_STATE, "restir_history_advance: the last image is a resolve's or a denoiser's, not a frame");
+    if (c->rgb_from != restir_ctx::RGB_PRODUCED || (size_t)c->rgb_w * c->rgb_h == 0)
+        return fail(RESTIR_ERR_STATE, "restir_history_advance: nothing rendered yet");
+    if (hs.width && (hs.width != width || hs.height != height))
+        return fail(RESTIR_ERR_STATE, "restir_history_advance: the view is %ux%u, the history %ux%u", width, height, hs.width, hs.height);
+    if (c->rgb_w != width || c->rgb_h != height)
+        return fail(RESTIR_ERR_UNSUPPORTED, "restir_history_advance: the last image is %ux%u, not the whole %ux%u view (a screen tile's?)",
+                    c->rgb_w, c->rgb_h, width, height);
+    if (hs.added_serial == c->rgb_serial) return fail(RESTIR_ERR_STATE, "restir_history_advance: the last image was folded already");
+    restir_tile t;
+    ST_TRY(frame_tile(nullptr, width, height, 0, t));
+    HIP_TRY(hipSetDevice(c->device));
+
+    // every buffer first: a refused allocation leaves the image as it was (and closes the history)
+    const size_t npx = (size_t)width * height;
+    DenoiseView view;
+    restir_status st = denoise_guides_alloc(c, cam, width, height, t, view);
+    if (st == RESTIR_OK) st = hs.planes.ensure(npx * 16 * 6);
+    if (st == RESTIR_OK && out_map) st = hs.map.ensure(npx * 4);
+    if (st != RESTIR_OK) { history_close(c); return st; }
+    set_launch_events(nullptr, nullptr);   // no RESTIR_K_* slot: restir_timings does not see these launches
+    ST_TRY(denoise_guides_trace(c, width, height, t, view));
+    c->stage_ok = false;   // like restir_denoise: the stage API is to be configured again
+
+    restir_camera_frame pf;
+    restir_camera_derive(&hs.cam, &pf);
+    HistoryDev a{};
+    a.prev_cam = reproj_cam(hs.have ? pf : cf, width, height);
+    a.miss_mat = c->sdev.num_materials - 1u;
+    a.max_frames = hs.params.max_frames;
+    a.fresh = hs.have ? 0u : 1u;
+    a.cur_nt = c->dn_nt.as<float4>(); a.cur_pf = c->dn_pf.as<float4>(); a.cur_ga = c->dn_ga.as<float4>();
+    a.x = c->rgb.as<float>();
+    float4* pl = hs.planes.as<float4>();
+    const int in = hs.set, out = hs.set ^ 1;
+    a.in_a = pl + (size_t)(3 * in) * npx; a.in_b = a.in_a + npx; a.in_c = a.in_b + npx;
+    a.out_a = pl + (size_t)(3 * out) * npx; a.out_b = a.out_a + npx; a.out_c = a.out_b + npx;
+    a.map = out_map ? hs.map.as<uint32_t>() : nullptr;
+    HIP_TRY(launch_history_advance(a, c->stream));
+    hs.set = out;
+    hs.have = true;
+    hs.width = width; hs.height = height;
+    hs.cam = *cam;
+    hs.added_serial = c->rgb_serial;
+    hs.advances++;
+    if (out_map) {
+        HIP_TRY(hipMemcpyAsync(out_map, hs.map.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return RESTIR_OK;
+}
+
+restir_status restir_history_resolve(restir_ctx* c, const restir_features* tone) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto& hs = c->hist;
+    if (!hs.open || !hs.have) return fail(RESTIR_ERR_STATE, "restir_history_resolve: the history holds no advance");
+    if (c->halo.active) return fail(RESTIR_ERR_STATE, "restir_history_resolve between restir_halo_begin and restir_halo_end");
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t px = (uint64_t)hs.width * hs.height;
+    ST_TRY(c->rgb.ensure(px * 12));   // a render of another size may have come between
+    c->image_pending(hs.width, hs.height);
+    FeaturesDev d{};
+    if (tone) {
+        d.tone_map = tone->enable_tone_mapping;
+        d.gamma = tone->gamma;
+        d.exposure = tone->exposure;
+    }
+    HIP_TRY(launch_history_resolve(hs.planes.as<float4>() + (size_t)(3 * hs.set + 1) * px, c->rgb.as<float>(), px, d, c->stream));
+    c->rgb_from = restir_ctx::RGB_RESOLVED;
+    return RESTIR_OK;
+}
+
+// restir_denoise_lum's levels over the history's mean; the initial plane and the packed mean image come from
+// k_history_var_fused, or (tuning history.var_fused = 0) from the three-launch form that computes the spatial estimate everywhere
+restir_status restir_history_denoise(restir_ctx* c, const restir_denoise_lum_params* params, const restir_features* tone,
+                                     float* out_rgb) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    ST_TRY(denoise_lum_params_check(params, "restir_history_denoise"));
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto& hs = c->hist;
+    if (!c->has_scene) return fail(RESTIR_ERR_STATE, "restir_history_denoise before restir_set_scene");
+    if (!hs.open || !hs.have) return fail(RESTIR_ERR_STATE, "restir_history_denoise: the history holds no advance");
+    if (c->halo.active) return fail(RESTIR_ERR_STATE, "restir_history_denoise between restir_halo_begin and restir_halo_end");
+    restir_tile t;
+    ST_TRY(frame_tile(nullptr, hs.width, hs.height, 0, t));
+    HIP_TRY(hipSetDevice(c->device));
+
+    const size_t npx = (size_t)hs.width * hs.height;
+    const restir_denoise_params& geo = params->geo;
+    const uint32_t levels = geo.iterations;
+    DenoiseView view;
+    // every buffer first: a refused allocation leaves the image as it was
+    ST_TRY(denoise_guides_alloc(c, &hs.cam, hs.width, hs.height, t, view));
+    ST_TRY(c->dn_tmp[0].ensure(npx * 12));
+    if (levels > 2u) ST_TRY(c->dn_tmp[1].ensure(npx * 12));
+    c->dn_var_px = 0;
+    ST_TRY(c->dn_var[0].ensure(npx * 4));
+    ST_TRY(c->dn_var[1].ensure(npx * 4));
+    if (c->rgb.bytes < npx * 12 || !c->rgb.p) {   // a render of another size may have come between
+        c->rgb_from = restir_ctx::RGB_NONE;
+        ST_TRY(c->rgb.ensure(npx * 12));
+    }
+    set_launch_events(nullptr, nullptr);   // no RESTIR_K_* slot
+    ST_TRY(denoise_guides_trace(c, hs.width, hs.height, t, view));
+    c->stage_ok = false;
+
+    FeaturesDev tf{};
+    if (tone) {
+        tf.tone_map = tone->enable_tone_mapping;
+        tf.gamma = tone->gamma;
+        tf.exposure = tone->exposure;
+    }
+    const float4 *n_t = c->dn_nt.as<float4>(), *ga = c->dn_ga.as<float4>(), *pf = c->dn_pf.as<float4>();
+    const float4* hb = hs.planes.as<float4>() + (size_t)(3 * hs.set + 1) * npx;
+    float* rgb = c->rgb.as<float>();
+    // the mean becomes the image, as restir_history_resolve(ctx, NULL) would write it; the history is only read
+    c->image_pending(hs.width, hs.height);
+    if (hs.var_fused) {
+        HIP_TRY(launch_history_var_fused(hb, hb + npx, rgb, c->dn_var[0].as<float>(), n_t, ga, pf, t.width, t.height,
+                                         hs.params.spatial_below, geo.normal_power_log2, geo.sigma_plane, c->stream));
+    } else {   // the spatial estimate everywhere, the history's entries written over it: the same bits in three launches
+        HIP_TRY(launch_history_resolve(hb, rgb, npx, FeaturesDev{}, c->stream));
+        HIP_TRY(launch_denoise_var_spatial(rgb, c->dn_var[0].as<float>(), n_t, ga, pf, t.width, t.height, geo.normal_power_log2,
+                                           geo.sigma_plane, c->stream));
+        HIP_TRY(launch_history_var(hb, hb + npx, c->dn_var[0].as<float>(), npx, hs.params.spatial_below, c->stream));
+    }
+    const float* in = rgb;
+    if (levels == 1u) {
+        HIP_TRY(hipMemcpyAsync(c->dn_tmp[0].p, rgb, npx * 12, hipMemcpyDeviceToDevice, c->stream));
+        in = c->dn_tmp[0].as<float>();
+    }
+    for (uint32_t level = 0; level < levels; level++) {
+        const bool last = level + 1u == levels;
+        float* out = last ? rgb : c->dn_tmp[level & 1u].as<float>();
+        HIP_TRY(launch_denoise_level_lum(in, out, c->dn_var[level & 1u].as<float>(), c->dn_var[(level + 1u) & 1u].as<float>(), n_t, ga,
+                                         pf, t.width, t.height, level, geo.normal_power_log2, geo.sigma_plane, params->sigma_lum,
+                                         last ? &tf : nullptr, c->stream));
+        in = out;
+    }
+    c->rgb_from = restir_ctx::RGB_RESOLVED;
+    c->dn_var_last = levels & 1u;
+    c->dn_var_px = npx;
+    if (out_rgb) {
+        HIP_TRY(hipMemcpyAsync(out_rgb, c->rgb.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return RESTIR_OK;
+}
+
+restir_status restir_history_download(restir_ctx* c, float* mean, float* S, uint32_t* n, size_t pixels) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto& hs = c->hist;
+    if (!hs.open || !hs.have) return fail(RESTIR_ERR_STATE, "restir_history_download: the history holds no advance");
+    const size_t npx = (size_t)hs.width * hs.height;
+    if (pixels < npx) return fail(RESTIR_ERR_INVALID, "buffer holds %zu pixels, need %zu", pixels, npx);
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<float> host(npx * 8);   // the (mean, n) and (S, material) planes
+    HIP_TRY(hipMemcpyAsync(host.data(), hs.planes.as<float4>() + (size_t)(3 * hs.set + 1) * npx, npx * 32, hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < npx; i++) {
+        const float* b = host.data() + 4 * i;
+        const float* s = host.data() + 4 * (npx + i);
+        if (mean) std::memcpy(mean + 3 * i, b, 12);
+        if (S) std::memcpy(S + 3 * i, s, 12);
+        if (n) n[i] = f2u(b[3]);
+    }
+    return RESTIR_OK;
+}
+
+restir_status restir_history_frames(restir_ctx* c, uint64_t* advances, uint64_t* resets) {
+    if (!c || !advances || !resets) return fail(RESTIR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->hist.open) return fail(RESTIR_ERR_STATE, "restir_history_frames before restir_history_begin");
+    *advances = c->hist.advances;
+    *resets = c->hist.resets;
+    return RESTIR_OK;
+}
+
+restir_status restir_history_end(restir_ctx* c) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    (void)hipSetDevice(c->device);
+    history_close(c);   // (hipFree waits for the kernels that use the planes)
+    return RESTIR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // stage API (parity tests): a whole width x height image, reservoir slot 0 = "current", slot 1 = "prev"
 restir_status restir_stage_configure(restir_ctx* c, uint32_t width, uint32_t height, uint32_t n) {
     if (!c || width == 0 || height == 0 || n < 1 || n > RESTIR_MAX_N) return fail(RESTIR_ERR_INVALID, "bad stage size");
@@ -4490,7 +4747,7 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     // a cache is built -- none of them reaches a kernel's arguments or launch shape, so no stored byte of the G-buffer,
     // the tile flags, the shadow lists or the visibility bits can differ (DESIGN.md §6 "Knobs that keep the caches")
     static const char* const kKeepsCaches[] = {"timing.mask", "timing.every", "timing.fence", "final.lists_after", "final.vis_after",
-                                              "ris.phat_after", "frames.ahead_after"};
+                                              "ris.phat_after", "frames.ahead_after", "history.var_fused"};
     bool keeps = false;
     for (const char* k : kKeepsCaches) keeps = keeps || !std::strcmp(key, k);
     if (!keeps) { c->gbuf.valid = false; ahead_drop(c); c->ahead.tuning_gen++; }
@@ -4556,6 +4813,7 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     else if (!std::strcmp(key, "mis.chunk")) t.mis_chunk = v;   // applies from the next ensure_mis
     else if (!std::strcmp(key, "layout.records")) t.records = v;   // frame-path buffer layout
     else if (!std::strcmp(key, "final.lds")) t.final_lds = v;
+    else if (!std::strcmp(key, "history.var_fused")) { if (v > 1) return fail(RESTIR_ERR_INVALID, "history.var_fused: 0 or 1"); c->hist.var_fused = v; }
     else return fail(RESTIR_ERR_INVALID, "unknown tuning key '%s'", key);
     return RESTIR_OK;
 }

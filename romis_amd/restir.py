@@ -419,6 +419,71 @@ class Renderer:
         check(self.lib, self.lib.restir_denoise_guide_builds(self.ctx, C.byref(n)), "restir_denoise_guide_builds")
         return n.value
 
+    # ---- a reprojected image history (include/restir_c.h "a reprojected image history") --------------
+    def history_begin(self, params=None) -> None:
+        """restir_history_begin: open (or restart) an empty image history -- per pixel a mean, the variance of the samples
+        and a count, which history_advance carries from camera to camera.  params: a HistoryParams (None: the defaults)."""
+        if params is None:
+            params = history_params()
+        check(self.lib, self.lib.restir_history_begin(self.ctx, C.byref(params)), "restir_history_begin")
+
+    def history_advance(self, camera, width: int, height: int, want_map: bool = False):
+        """restir_history_advance: move the history to `camera` -- the camera the last image was rendered with -- and fold
+        that image in; only enqueues.  Render the frames with enable_tone_mapping = 0.  want_map: returns the map [h][w]
+        uint32 (rows y = 0 bottom) with the source pixel's flat index or 0xFFFFFFFF - reason (restir_frame_reproject's 0 -
+        5, 6 material, 7 no history), and synchronises."""
+        smap = np.zeros((height, width), np.uint32) if want_map else None
+        check(self.lib, self.lib.restir_history_advance(self.ctx, C.byref(camera), width, height,
+                                                        smap.ctypes.data_as(C.POINTER(C.c_uint32)) if want_map else None),
+              "restir_history_advance")
+        self._history_shape = (height, width)
+        return smap
+
+    def history_resolve(self, features=None) -> None:
+        """restir_history_resolve: the history's mean becomes the last image -- tone mapped by `features`, or its own bits
+        without."""
+        check(self.lib, self.lib.restir_history_resolve(self.ctx, C.byref(features) if features is not None else None),
+              "restir_history_resolve")
+
+    def history_denoise(self, params=None, tone=None, download: bool = True):
+        """restir_history_denoise: denoise_lum's levels over the history's mean for the last advance's view, the initial
+        variance taken from the history (a pixel with a short history takes the spatial estimate).  Returns rgb [h][w][3]
+        (row 0 = top), or None with download=False, which only enqueues; denoise_lum_variance serves the final plane."""
+        if params is None:
+            params = denoise_lum_params()
+        shape = getattr(self, "_history_shape", None)
+        if shape is None:
+            raise RuntimeError("history_denoise before history_advance")
+        rgb = np.zeros(shape + (3,), np.float32) if download else None
+        check(self.lib, self.lib.restir_history_denoise(
+            self.ctx, C.byref(params), C.byref(tone) if tone is not None else None,
+            rgb.ctypes.data_as(C.POINTER(C.c_float)) if download else None), "restir_history_denoise")
+        self._denoise_lum_shape = shape
+        return rgb
+
+    def history_state(self):
+        """restir_history_download: (mean [h][w][3] float32, S [h][w][3] float32, n [h][w] uint32) in image rows as the
+        last advance left them; synchronises.  A test hook."""
+        shape = getattr(self, "_history_shape", None)
+        if shape is None:
+            raise RuntimeError("history_state before history_advance")
+        mean, S, n = np.zeros(shape + (3,), np.float32), np.zeros(shape + (3,), np.float32), np.zeros(shape, np.uint32)
+        FP = C.POINTER(C.c_float)
+        check(self.lib, self.lib.restir_history_download(self.ctx, mean.ctypes.data_as(FP), S.ctypes.data_as(FP),
+                                                         n.ctypes.data_as(C.POINTER(C.c_uint32)), n.size),
+              "restir_history_download")
+        return mean, S, n
+
+    def history_frames(self) -> tuple[int, int]:
+        """restir_history_frames: (advances, resets) since history_begin."""
+        a, r = C.c_uint64(), C.c_uint64()
+        check(self.lib, self.lib.restir_history_frames(self.ctx, C.byref(a), C.byref(r)), "restir_history_frames")
+        return a.value, r.value
+
+    def history_end(self) -> None:
+        """restir_history_end: close the history and free its planes."""
+        check(self.lib, self.lib.restir_history_end(self.ctx), "restir_history_end")
+
     # ---- halo-mode frames (include/restir_c.h "halo-mode frames") -------------------------------------
     def halo_begin(self, prev, camera, width, height, features, tiles, rank, layout=None):
         """Primary rays on the tile + ring, RIS / temporal on the owned tile.  Returns (send_bytes, recv_bytes).
@@ -843,6 +908,90 @@ def denoise_host(rgb, n_t, p_mat, miss_material: int, params=None) -> np.ndarray
     check(lib, lib.restir_denoise_host(c.ctypes.data_as(FP), nt.ctypes.data_as(FP), pm.ctypes.data_as(FP), w, h,
                                        miss_material, C.byref(params), out.ctypes.data_as(FP)), "restir_denoise_host")
     return out
+
+
+def history_params(max_frames: int | None = None, spatial_below: int | None = None) -> _abi.HistoryParams:
+    """restir_history_params_default, with the given fields replaced."""
+    lib = _abi.load_library()
+    p = _abi.HistoryParams()
+    lib.restir_history_params_default(C.byref(p))
+    if max_frames is not None:
+        p.max_frames = max_frames
+    if spatial_below is not None:
+        p.spatial_below = spatial_below
+    return p
+
+
+def history_fold(mean, S, n, smap, x, max_frames: int):
+    """restir_history_fold (pure host): one advance's gather and fold, bit for bit.  mean, S [h][w][3] float32 and n [h][w]
+    uint32 (image rows): the kept state; smap [h][w] uint32 (rows y = 0 bottom): history_advance's map; x [h][w][3]: the
+    image.  Returns the new (mean, S, n)."""
+    lib = _abi.load_library()
+    xa = np.ascontiguousarray(x, np.float32)
+    if xa.ndim != 3 or xa.shape[2] != 3:
+        raise ValueError("history_fold: x must be [h][w][3]")
+    h, w = xa.shape[:2]
+    m, s = np.ascontiguousarray(mean, np.float32), np.ascontiguousarray(S, np.float32)
+    na, ma = np.ascontiguousarray(n, np.uint32), np.ascontiguousarray(smap, np.uint32)
+    if m.size != xa.size or s.size != xa.size or na.size != w * h or ma.size != w * h:
+        raise ValueError("history_fold: mean, S, n and the map must have x's size")
+    mo, so, no = np.zeros_like(xa), np.zeros_like(xa), np.zeros((h, w), np.uint32)
+    FP, UP = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    check(lib, lib.restir_history_fold(m.ctypes.data_as(FP), s.ctypes.data_as(FP), na.ctypes.data_as(UP), ma.ctypes.data_as(UP),
+                                       xa.ctypes.data_as(FP), w, h, max_frames, mo.ctypes.data_as(FP), so.ctypes.data_as(FP),
+                                       no.ctypes.data_as(UP)), "restir_history_fold")
+    return mo, so, no
+
+
+def history_map_host(prev_cam: _abi.CameraFrame, width: int, height: int, cur_gbuffer, kept, miss_material: int) -> np.ndarray:
+    """restir_history_map_host (pure host): history_advance's map [h][w] uint32 (rows y = 0 bottom).  cur_gbuffer: (n_t,
+    p_mat) of the new camera, 4 floats per pixel, rows y = 0 bottom; kept: (n_t, material, n) the history kept from the
+    advance before -- n_t and the material's words in G-buffer rows, n [h][w] in image rows --, or None: nothing kept."""
+    lib = _abi.load_library()
+    FP, UP = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    cn, cp = (np.ascontiguousarray(a, np.float32) for a in cur_gbuffer)
+    px = width * height
+    if cn.size != 4 * px or cp.size != 4 * px:
+        raise ValueError("history_map_host: the G-buffer must hold 4 floats per pixel")
+    kn = km = kc = None
+    if kept is not None:
+        kn, km, kc = np.ascontiguousarray(kept[0], np.float32), np.ascontiguousarray(kept[1], np.uint32), \
+            np.ascontiguousarray(kept[2], np.uint32)
+        if kn.size != 4 * px or km.size != px or kc.size != px:
+            raise ValueError("history_map_host: kept must be (n_t, material, n) of the image's size")
+    out = np.zeros((height, width), np.uint32)
+    check(lib, lib.restir_history_map_host(C.byref(prev_cam), width, height, cn.ctypes.data_as(FP), cp.ctypes.data_as(FP),
+                                           kn.ctypes.data_as(FP) if kept is not None else None,
+                                           km.ctypes.data_as(UP) if kept is not None else None,
+                                           kc.ctypes.data_as(UP) if kept is not None else None, miss_material,
+                                           out.ctypes.data_as(UP)), "restir_history_map_host")
+    return out
+
+
+def history_variance_host(mean, S, n, n_t, p_mat, miss_material: int, params=None, geo=None) -> np.ndarray:
+    """restir_history_variance_host (pure host): history_denoise's initial variance plane [h][w] (row 0 = top), bit for
+    bit.  mean, S, n as history_state gives them; n_t, p_mat as denoise_host's; params: a HistoryParams, geo: a
+    DenoiseParams (None: the defaults)."""
+    lib = _abi.load_library()
+    m = np.ascontiguousarray(mean, np.float32)
+    if m.ndim != 3 or m.shape[2] != 3:
+        raise ValueError("history_variance_host: mean must be [h][w][3]")
+    h, w = m.shape[:2]
+    s, na = np.ascontiguousarray(S, np.float32), np.ascontiguousarray(n, np.uint32)
+    nt, pm = np.ascontiguousarray(n_t, np.float32), np.ascontiguousarray(p_mat, np.float32)
+    if s.size != m.size or na.size != w * h or nt.size != 4 * w * h or pm.size != 4 * w * h:
+        raise ValueError("history_variance_host: S, n, n_t and p_mat must have mean's size")
+    if params is None:
+        params = history_params()
+    if geo is None:
+        geo = denoise_params()
+    var = np.zeros((h, w), np.float32)
+    FP = C.POINTER(C.c_float)
+    check(lib, lib.restir_history_variance_host(m.ctypes.data_as(FP), s.ctypes.data_as(FP), na.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                nt.ctypes.data_as(FP), pm.ctypes.data_as(FP), w, h, miss_material,
+                                                C.byref(params), C.byref(geo), var.ctypes.data_as(FP)),
+          "restir_history_variance_host")
+    return var
 
 
 def reproject_pixel(prev_cam: _abi.CameraFrame, width: int, height: int, point):
