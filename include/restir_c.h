@@ -1068,6 +1068,11 @@ restir_status restir_phat_builds(restir_ctx* ctx, uint64_t* out_builds);
  * restir_synchronize, restir_timings, scene and light updates and restir_destroy wait for the second stream too; a
  * look-ahead launch is timed as RESTIR_K_PRIMARY_RIS.  A view that moves after a pause pays for one launch that is
  * never read (restir_ahead_discards counts them); restir_set_seed always drops a pending result.
+ * From frames.batch_after consecutive reusing frames on (default 8; never effective below frames.ahead_after) a
+ * look-ahead launch runs RIS for two frames in one pass over the table (frames.batch: 2, the default; 1 keeps the single
+ * launch) and the two calls after take its results in turn, each from a plane set of its own (12 bytes a pixel; three
+ * sets beside the frame's own from the first batch on).  A batch is timed as one RESTIR_K_PRIMARY_RIS launch.
+ * restir_ahead_discards counts launches with at least one result nobody took.
  * restir_ahead_frames: the frames so far that took their RIS result from a look-ahead. */
 restir_status restir_ahead_frames(restir_ctx* ctx, uint64_t* out_frames);
 restir_status restir_ahead_discards(restir_ctx* ctx, uint64_t* out_discards);

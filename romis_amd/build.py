@@ -115,6 +115,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_shadow_vis_layout(force)
     build_phat_layout(force)
     build_ris_ahead_key(force)
+    build_ris_batch_ring(force)
     if verbose:
         print(LIB)
     return LIB
@@ -203,6 +204,18 @@ def build_ris_ahead_key(force: bool = False) -> str:
     key's comparison, one case per member (tests/test_ris_ahead_key.py); no device code, no HIP header."""
     tool = os.path.join(OUT, "tools", "ris_ahead_key")
     src = os.path.join(ROOT, "tests", "cpp", "ris_ahead_key.cpp")
+    deps = [src, os.path.join(CSRC, "ris_ahead.h"), __file__]
+    if os.path.exists(src) and (force or _stale(tool, deps)):
+        os.makedirs(os.path.dirname(tool), exist_ok=True)
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", tool])
+    return tool
+
+
+def build_ris_batch_ring(force: bool = False) -> str:
+    """tools/ris_batch_ring: tests/cpp/ris_batch_ring.cpp over csrc/ris_ahead.h with the host compiler -- the result
+    ring and the two batch cadences walked over every reachable state (tests/test_ris_batch_ring.py); no device code."""
+    tool = os.path.join(OUT, "tools", "ris_batch_ring")
+    src = os.path.join(ROOT, "tests", "cpp", "ris_batch_ring.cpp")
     deps = [src, os.path.join(CSRC, "ris_ahead.h"), __file__]
     if os.path.exists(src) and (force or _stale(tool, deps)):
         os.makedirs(os.path.dirname(tool), exist_ok=True)

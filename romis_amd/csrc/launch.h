@@ -48,6 +48,14 @@ hipError_t launch_primary_ris(const Route& r, const SceneDev& s, const Region& r
 // launch_primary_ris's launch for a kGbufRis route with `phat` (phat_table.hip)
 hipError_t launch_gbuf_ris_phat(const Route& r, const SceneDev& s, const Region& rg, const FeaturesDev& f, const LaunchBufs& b,
                                 hipStream_t stream);
+// ... for two RNG keys in one pass over the table (DESIGN.md §6 "RIS batch"): what each key's result is written to
+struct RisBatchOut {
+    uint32_t key = 0;
+    Handles h{nullptr, nullptr};
+    float* rp = nullptr;
+};
+hipError_t launch_gbuf_ris_phat_batch(const Route& r, const SceneDev& s, const Region& rg, const FeaturesDev& f, const LaunchBufs& b,
+                                      const RisBatchOut (&out)[2], hipStream_t stream);
 hipError_t launch_temporal(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key, const float* origin,
                            const float4* n_t, const float4* p_mat, const float4* ca, const float4* cb,
                            const float4* pa, const float4* pb, float4* oa, float4* ob, float2* odbg,

@@ -313,6 +313,149 @@ __device__ __forceinline__ void pt_ris_body(const SceneDev& s, const Region& rg,
     if (hw) { hw[p] = r.W; hm[p] = r.M | (hidx << 24); }
 }
 
+
+// pt_ris_body<false> for two RNG keys in one launch (DESIGN.md §6 "RIS batch"): the rows of a step go to LDS once; phases
+// A-D and the tail run once per key, key 1's (key1, rp1, hw1, hm1) exactly as a launch of its own would -- every draw, add
+// and accept is that launch's.  The keys share the row bytes, s_loop and the pixel's nt / pm, nothing else.  It serves the
+// look-ahead's route alone: the reservoir planes are dead, there is no debug plane, and every output plane is there
+// (launch_gbuf_ris_phat_batch refuses anything else).  A copy of the body, not a parameter of it: with the parameter the
+// one-key kernels' registers were allocated differently, and their instruction streams are held fixed
+// (scripts/device_code_diff.py).  A change to phases A-D or the tail of either body goes into both.
+__device__ __forceinline__ void pt_ris_batch_body(const SceneDev& s, const Region& rg, const FeaturesDev& f, uint32_t key, v3 origin,
+                                                  const float4* __restrict__ n_t, const float4* __restrict__ p_mat,
+                                                  float* __restrict__ rp, const uint8_t* __restrict__ tmiss, uint32_t skip_res,
+                                                  float* __restrict__ hw, uint32_t* __restrict__ hm,
+                                                  const float* __restrict__ tab, uint32_t key1, float* __restrict__ rp1,
+                                                  float* __restrict__ hw1, uint32_t* __restrict__ hm1) {
+    constexpr uint32_t NB = 2u;   // the keys
+    const uint32_t tile = blockIdx.x;
+    if (tile >= work_items(rg)) return;   // block-uniform
+    const bool any = pt_tile_live(tmiss, tile);
+    if (!any && (skip_res & 1u)) return;
+    // accepted candidate + 1 (0: none) in a byte (M <= 32): four blocks a CU keep their LDS
+    typedef uint8_t best_t;
+    __shared__ best_t s_best[NB][kPtTilePx];
+    __shared__ float s_wsum[NB][kPtTilePx], s_pd[NB][kPtTilePx];
+    __shared__ uint8_t s_loop[kPtTilePx];
+    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+    const uint32_t L = s.num_lights, M = f.M, rf = pt_row_floats(L);
+    uint32_t x, y;
+    size_t p;
+    const bool live = work_pixel(rg, tile, x, y, p);
+    float4 nt = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pm = nt;
+    if (live) {
+        nt = n_t[gidx(rg, p)];
+        pm = p_mat[p];
+    }
+    const bool loop = live && any && pt_runs_loop(s, pm);
+#pragma unroll
+    for (uint32_t kb = 0; kb < NB; kb++) {
+        s_best[kb][t] = 0u;
+        s_wsum[kb][t] = ROMIS_FLT_MIN;
+        s_pd[kb][t] = 0.0f;
+    }
+    s_loop[t] = loop ? 1u : 0u;
+    const GlTabs tb = gl_stage_tables<false>();
+    __syncthreads();
+    if (any) {
+        const uint32_t q = lane / kG, j = lane % kG;
+        const uint32_t chunk = (M + kG - 1u) / kG;
+        const uint32_t c0 = min(j * chunk, M), c1 = min(c0 + chunk, M);
+        const float invL = 1.0f / (float)L;
+        auto weight = [&](float pd) { return s.light_scale != 0.0f ? pd * s.light_scale : pd / invL; };   // ris_pixel's
+        const uint32_t ntx = (rg.rw + kTileW - 1u) / kTileW;
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const uint32_t n4 = kStepPx * rf / 4u;
+        // the wave's LDS: the step's rows
+        float* const l_base = reinterpret_cast<float*>(g_lds) + (size_t)wave * kStepPx * rf * (ROMIS_PT_LDS2 ? 2u : 1u);
+        f4v v[kRowF4];
+        auto fetch = [&](uint32_t step) {
+            const f4v* src = reinterpret_cast<const f4v*>(tab + pt_index(pt_row_of_thread(tile, (wave << 6) + step * kStepPx), rf, 0u));
+#pragma unroll
+            for (uint32_t u = 0; u < kRowF4; u++)
+                if (64u * u + lane < n4) v[u] = __builtin_nontemporal_load(src + 64u * u + lane);
+        };
+        if (ROMIS_PT_PREFETCH) fetch(0u);
+#pragma unroll 1
+        for (uint32_t step = 0; step < kSteps; step++) {
+            if (!ROMIS_PT_PREFETCH) fetch(step);
+            float* const l_rows = l_base + (ROMIS_PT_LDS2 ? (step & 1u) * kStepPx * rf : 0u);
+            f4v* const dst = reinterpret_cast<f4v*>(l_rows);
+#pragma unroll
+            for (uint32_t u = 0; u < kRowF4; u++)
+                if (64u * u + lane < n4) dst[64u * u + lane] = v[u];
+            if (ROMIS_PT_PREFETCH && step + 1u < kSteps) fetch(step + 1u);
+            // the step's pixel of this lane: thread tq of the block (tile_pixel_of's mapping, map2d = 1) and its RNG state
+            const uint32_t tq = (wave << 6) + step * kStepPx + q;
+            const uint32_t xq = rg.rx0 + (tile % ntx) * kTileW + tq % kTileW, yq = rg.ry0 + (tile / ntx) * kTileH + tq / kTileW;
+            uint32_t psq[NB];
+#pragma unroll
+            for (uint32_t kb = 0; kb < NB; kb++) psq[kb] = pix_state(kb ? key1 : key, yq * rg.W + xq);
+            const bool lq = s_loop[tq] != 0u;
+            pt_wave_sync();
+#pragma unroll
+            for (uint32_t kb = 0; kb < NB; kb++) {   // phases A-D under key kb, over the same rows
+                float w[kChunk], ws[kChunk];
+#pragma unroll
+                for (uint32_t k = 0; k < kChunk; k++)   // (an index past the chunk still reads inside the row)
+                    w[k] = weight(l_rows[q * rf + uniform_index(draw(psq[kb], 4u * (c0 + k)), L)]);
+                float run = ROMIS_FLT_MIN;
+#pragma unroll
+                for (uint32_t r = 0; r < kG; r++) {
+                    const float left = pt_from_left(run);
+                    run = j == 0u ? ROMIS_FLT_MIN : left;   // sub_init's wsum, or the total of the candidates before this chunk
+#pragma unroll
+                    for (uint32_t k = 0; k < kChunk; k++) {
+                        run = c0 + k < c1 ? run + w[k] : run;
+                        ws[k] = run;
+                    }
+                }
+                uint32_t best = 0u;
+#pragma unroll
+                for (uint32_t k = 0; k < kChunk; k++) {
+                    const bool acc = accept_u(rand01(draw(psq[kb], 4u * (c0 + k) + 3u)), w[k], ws[k]);
+                    if (acc && c0 + k < c1) best = c0 + k + 1u;
+                }
+                best = pt_group_max(lq ? best : 0u);
+                if (lq && j == kG - 1u) {   // the pixel's last lane holds the whole sum
+                    s_wsum[kb][tq] = run;
+                    s_best[kb][tq] = (best_t)best;
+                    if (best) s_pd[kb][tq] = l_rows[q * rf + uniform_index(draw(psq[kb], 4u * (best - 1u)), L)];
+                }
+            }
+            if (!ROMIS_PT_LDS2) pt_wave_sync();   // the rows are overwritten by the next step
+        }
+    }
+    if (!live) return;
+    // ris_pixel's tail (NT = 1, kLtPoint, no temporal reuse, no initial visibility rays)
+#pragma unroll
+    for (uint32_t kb = 0; kb < NB; kb++) {
+        float* const rpk = kb ? rp1 : rp;   // key kb's planes
+        float* const hwk = kb ? hw1 : hw;
+        uint32_t* const hmk = kb ? hm1 : hm;
+        Sub r;
+        sub_init(r);
+        r.M = M;
+        r.wsum = s_wsum[kb][t];
+        const uint32_t b = s_best[kb][t];
+        uint32_t hidx = L;
+        float pj;
+        if (b) {
+            hidx = uniform_index(draw(pix_state(kb ? key1 : key, y * rg.W + x), 4u * (b - 1u)), L);
+            r.pos = xyz(s.light_c2[hidx]);
+            r.col = xyz(s.light_c2[L + hidx]);
+            pj = s_pd[kb][t];
+            r.chosen = s.light_scale != 0.0f ? pj * s.light_scale : pj / (1.0f / (float)L);
+        } else {
+            pj = target_pdf(s, f, make_px(s, nt, pm, origin, p), r.pos, r.col, tb);
+        }
+        r.W = contribution_weight(pj, r.M, r.wsum);
+        rpk[p] = pj;
+        hwk[p] = r.W;
+        hmk[p] = r.M | (hidx << 24);
+    }
+}
+
 }  // namespace
 }  // namespace romis
 
@@ -328,6 +471,14 @@ extern "C" __global__ __launch_bounds__(256) void k_gbuf_ris_n1_lds_pt_phat_temp
     float4* ra, float4* rb, float2* rdbg, float* rp, TemporalIn tin, float* hw, uint32_t* hm, uint32_t res_dead,
     const float* tab) {
     pt_ris_body<true>(s, rg, f, key, mk(ox, oy, oz), n_t, p_mat, ra, rb, rdbg, rp, nullptr, 0u, hw, hm, res_dead, tab, tin);
+}
+// k_gbuf_ris_n1_lds_pt_phat for two RNG keys in one pass over the table (DESIGN.md §6 "RIS batch"): key k's pdf cache to
+// rp_k, its handles to (hw_k, hm_k).  The reservoir planes are dead and there is no debug plane.
+extern "C" __global__ __launch_bounds__(256) void k_gbuf_ris_n1_lds_pt_phat_batch2(
+    SceneDev s, Region rg, FeaturesDev f, uint32_t key0, uint32_t key1, float ox, float oy, float oz, const float4* n_t,
+    const float4* p_mat, float* rp0, float* rp1, const uint8_t* tmiss, uint32_t skip_res, float* hw0, uint32_t* hm0, float* hw1,
+    uint32_t* hm1, const float* tab) {
+    pt_ris_batch_body(s, rg, f, key0, mk(ox, oy, oz), n_t, p_mat, rp0, tmiss, skip_res, hw0, hm0, tab, key1, rp1, hw1, hm1);
 }
 
 namespace romis {
@@ -386,6 +537,29 @@ hipError_t launch_gbuf_ris_phat(const Route& r, const SceneDev& s, const Region&
                  (const float4*)b.p_mat, b.oa, b.ob, r.dbg ? b.dbg : nullptr, r.rp_out ? b.rp_out : nullptr,
                  r.flags ? (const uint8_t*)b.flags : nullptr, r.skip, r.how ? b.hout.w : nullptr, r.hom ? b.hout.m : nullptr,
                  r.res_dead, b.phat);
+    return hipGetLastError();
+}
+
+// A frame's routed launch_gbuf_ris_phat launch for two RNG keys at once: key k's handles to out[k].h, its pdf cache to
+// out[k].rp; b's own key, hout and rp_out are not used.  The route is one whose reservoir planes are dead and that
+// writes both handle planes and the pdf cache, without temporal reuse or the debug plane (the look-ahead's frames).
+hipError_t launch_gbuf_ris_phat_batch(const Route& r, const SceneDev& s, const Region& rg0, const FeaturesDev& f, const LaunchBufs& b,
+                                      const RisBatchOut (&out)[2], hipStream_t stream) {
+    if (r.kernel != Kernel::kGbufRis || !r.phat || !b.phat || r.n != 1u || r.lt != kLtPoint || r.map2d != 1u || f.initial_vis)
+        return hipErrorInvalidValue;
+    if (!r.res_dead || r.dbg || !r.how || !r.hom || !r.rp_out) return hipErrorInvalidValue;
+    for (const RisBatchOut& o : out)
+        if (!o.h.w || !o.h.m || !o.rp) return hipErrorInvalidValue;
+    if (out[0].h.w == out[1].h.w || out[0].h.m == out[1].h.m || out[0].rp == out[1].rp) return hipErrorInvalidValue;
+    const Region rg = r.region(rg0);
+    const float* o = b.origin;
+    if (!pt_fast(s.num_lights, f.M) || r.lds != pt_lds_bytes(s.num_lights)) return hipErrorInvalidValue;
+    if (kG != kPtLanesPerPx || ROMIS_PT_LDS2) return hipErrorInvalidValue;   // (the A/B forms have no batch kernel)
+    const size_t lds = pt_lds_bytes(s.num_lights);
+    if (lds + 8192u > kLdsBudget) return hipErrorInvalidValue;   // (static LDS: 5,376 B)
+    ROMIS_LAUNCH(k_gbuf_ris_n1_lds_pt_phat_batch2, dim3(r.grid), dim3(r.block), lds, stream, s, rg, f, out[0].key, out[1].key, o[0], o[1],
+                 o[2], (const float4*)b.n_t, (const float4*)b.p_mat, out[0].rp, out[1].rp, r.flags ? (const uint8_t*)b.flags : nullptr,
+                 r.skip, out[0].h.w, out[0].h.m, out[1].h.w, out[1].h.m, b.phat);
     return hipGetLastError();
 }
 

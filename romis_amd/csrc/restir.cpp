@@ -343,24 +343,28 @@ struct restir_ctx {
     uint64_t phat_builds = 0;                       // k_phat_table launches (restir_phat_builds)
     // RIS look-ahead (ris_ahead.h, tuning "frames.ahead"; DESIGN.md §6 "RIS look-ahead"): on a still view served by the
     // p-hat table without temporal reuse, frame f + 1's RIS runs on `stream` beside frame f's last pass and writes the
-    // plane set frame f does not read -- set 0 is (hnd[0], rp[0]), set 1 (hnd, rp) here: 12 B a pixel of the view.
-    // `valid`: a result keyed `key` is in (or on its way into) set `set`; the next restir_render takes it when its own
-    // key is equal and launches no RIS, else marks it invalid (discards) and runs as if there had been none.
+    // plane set frame f does not read -- set 0 is (hnd[0], rp[0]), set s >= 1 (hnd[s - 1], rp[s - 1]) here: 12 B a pixel of
+    // the view each.  `ring` holds the results that are in (or on their way into) a set, each under its key; the next
+    // restir_render takes the one whose key equals its own and launches no RIS, else marks them all invalid (discards)
+    // and runs as if there had been none.  From the batch_after-th still frame on a launch serves two frames (frames.batch,
+    // DESIGN.md §6 "RIS batch"): the ring then holds up to kRisRingSlots results in kRisSets sets.
     struct {
         uint32_t on = 1, after = 4, prio = 0;       // knobs frames.ahead (2: RIS enqueued before the last pass), _after, _prio
+        uint32_t batch = 2, batch_after = 8;        // knobs frames.batch (keys per launch from that streak on), _after
+        uint32_t batch_form = 1;                    // frames.batch_form: 0 a batch when nothing is pending, 1 when one result is (A/B)
+        uint32_t serial = 0;                        // frames.ahead_serial: 1 the launch waits for the frame's last pass (kernel times alone)
         hipStream_t stream = nullptr;               // created by the first eligible frame, non-blocking
         uint32_t stream_prio = 0;                   // frames.ahead_prio the stream was created with
-        DevBuf hnd, rp;
-        // done[s]: after the look-ahead launch into set s; consumed[s]: after the last pass that read set s; ready: on
-        // the frame's stream once the G-buffer and the table the launches read are final.  *_ev: the one a stream has
-        // yet to wait for (null: none, or everything before it was synchronised)
-        hipEvent_t done[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr}, ready = nullptr;
-        hipEvent_t done_ev = nullptr, consumed_ev[2] = {nullptr, nullptr};
+        DevBuf hnd[kRisSets - 1], rp[kRisSets - 1];   // sets 2 ..: allocated when a batch is first launched
+        // done[s]: after the look-ahead launch whose last set is s; consumed[s]: after the last pass that read set s;
+        // ready: on the frame's stream once the G-buffer and the table the launches read are final.  slot_done[i]: the
+        // done event ring slot i's taker has yet to wait for, consumed_ev[s]: the one the next writer of set s has
+        // (null: none, or everything before it was synchronised)
+        hipEvent_t done[kRisSets] = {}, consumed[kRisSets] = {}, ready = nullptr;
+        hipEvent_t slot_done[kRisRingSlots] = {}, consumed_ev[kRisSets] = {};
         bool ready_ok = false;
         uint64_t ready_epoch = 0, ready_build = 0;  // the G-buffer and table build `ready` was recorded behind
-        bool valid = false;
-        int set = 0;
-        RisAheadKey key;
+        RisRing ring;
         uint64_t tuning_gen = 0;
         uint64_t frames = 0, discards = 0;          // restir_ahead_frames, restir_ahead_discards
         // the event the next timed_begin's launch records as its stop event when it carries no timing pair
@@ -764,19 +768,17 @@ hipError_t sync_streams(restir_ctx* c) {
         if (e == hipSuccess) e = e2;
     }
     // nothing is left to wait for
-    c->ahead.done_ev = c->ahead.consumed_ev[0] = c->ahead.consumed_ev[1] = nullptr;
+    for (hipEvent_t& ev : c->ahead.slot_done) ev = nullptr;
+    for (hipEvent_t& ev : c->ahead.consumed_ev) ev = nullptr;
     return e;
 }
 
-// Drop a look-ahead result: mark it invalid (counted) and wait for its launch -- nothing is cancelled.  For whatever
+// Drop the look-ahead results: mark them invalid (counted per launch) and wait for their launches -- nothing is cancelled.  For whatever
 // changes what the launch read or will write outside restir_render: a seed, a knob, the stage and halo paths, a scene.
 void ahead_drop(restir_ctx* c) {
-    if (c->ahead.valid) {
-        c->ahead.valid = false;
-        c->ahead.discards++;
-    }
+    c->ahead.discards += ris_ring_drop(c->ahead.ring);
     if (c->ahead.stream) (void)hipStreamSynchronize(c->ahead.stream);
-    c->ahead.done_ev = nullptr;
+    for (hipEvent_t& ev : c->ahead.slot_done) ev = nullptr;
 }
 
 restir_status collect_timings(restir_ctx* c) {
@@ -838,9 +840,9 @@ struct FrameBufs {
     bool records;
     size_t npx;
     uint32_t N;
-    // the plane set grid 0's handles and pdf cache lie in (1: restir_ctx::ahead's, a look-ahead result the frame took)
+    // the plane set grid 0's handles and pdf cache lie in (>= 1: restir_ctx::ahead's, a look-ahead result the frame took)
     int set0 = 0;
-    const DevBuf& hnd(int i) const { return i == 0 && set0 ? c->ahead.hnd : c->hnd[i]; }
+    const DevBuf& hnd(int i) const { return i == 0 && set0 ? c->ahead.hnd[set0 - 1] : c->hnd[i]; }
     float4* pm() const { return c->p_mat.as<float4>(); }
     DevBuf& rgb() const { return c->rgb; }
     DevBuf& uv() const { return c->uv; }
@@ -867,7 +869,7 @@ struct FrameBufs {
     float4* rb(int i) const { return c->rec[i].as<float4>() + (records ? 2 : npx * N); }
     float4* nt2() const { return records ? c->rec[1].as<float4>() : nullptr; }
     // the target-pdf cache planes (N = 1 planes layout only)
-    float* rp(int i) const { return (!records && N == 1) ? (i == 0 && set0 ? c->ahead.rp : c->rp[i]).as<float>() : nullptr; }
+    float* rp(int i) const { return (!records && N == 1) ? (i == 0 && set0 ? c->ahead.rp[set0 - 1] : c->rp[i]).as<float>() : nullptr; }
     const float4* pa(const restir_frame* f) const { return f->rec.as<float4>() + (records ? 1 : 0); }
     const float4* pb(const restir_frame* f) const { return f->rec.as<float4>() + (records ? 2 : npx * N); }
     Region region(Region r) const { return records ? with_records(r, N) : r; }
@@ -1007,7 +1009,8 @@ void restir_destroy(restir_ctx* c) {
         std::lock_guard<std::mutex> lk(c->mu);
         (void)hipSetDevice(c->device);
         (void)sync_streams(c);   // a look-ahead launch may still be in flight
-        for (DevBuf* b : {&c->ahead.hnd, &c->ahead.rp, &c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
+        for (int i = 0; i < kRisSets - 1; i++) { c->ahead.hnd[i].release(); c->ahead.rp[i].release(); }
+        for (DevBuf* b : {&c->vis, &c->tmiss, &c->hnd[0], &c->hnd[1], &c->rpj_nt[0], &c->rpj_nt[1], &c->rpj_pm[0], &c->rpj_pm[1],
                           &c->rpj_map, &c->acc.mean, &c->acc.m2, &c->acc.partials, &c->exact_nt, &c->exact_pm, &c->exact_uv,
                           &c->ref, &c->err_partials, &c->dn_nt, &c->dn_pf, &c->dn_ga, &c->dn_uv, &c->dn_tmp[0], &c->dn_tmp[1],
                           &c->dn_var[0], &c->dn_var[1], &c->hist.planes, &c->hist.map})
@@ -1023,8 +1026,9 @@ void restir_destroy(restir_ctx* c) {
         c->pool->close();   // frames still alive free their records themselves on release
         release_rccl(c);
         release_images(c);
-        for (hipEvent_t ev : {c->ahead.done[0], c->ahead.done[1], c->ahead.consumed[0], c->ahead.consumed[1], c->ahead.ready})
-            if (ev) (void)hipEventDestroy(ev);
+        for (hipEvent_t ev : c->ahead.done) if (ev) (void)hipEventDestroy(ev);
+        for (hipEvent_t ev : c->ahead.consumed) if (ev) (void)hipEventDestroy(ev);
+        if (c->ahead.ready) (void)hipEventDestroy(c->ahead.ready);
         if (c->ahead.stream) (void)hipStreamDestroy(c->ahead.stream);
         (void)hipStreamDestroy(c->stream);
     }
@@ -1034,7 +1038,7 @@ void restir_destroy(restir_ctx* c) {
 restir_status restir_set_seed(restir_ctx* c, uint32_t seed, uint32_t frame_index) {
     if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->ahead.valid) {   // keyed by the seed and frame index that were: dropped, whatever the new ones are
+    if (ris_ring_pending(c->ahead.ring)) {   // keyed by the seed and frame index that were: dropped, whatever the new ones are
         HIP_TRY(hipSetDevice(c->device));
         ahead_drop(c);
     }
@@ -1981,6 +1985,7 @@ struct Frame {
     // ris_stage: the frame may run the next frame's RIS beside its last pass (restir_ctx::ahead) -- its own key, and its
     // RIS launch as routed, which the look-ahead repeats with the next frame's RNG key into the other plane set
     bool ahead_ok;
+    uint32_t ahead_streak;   // the streak of reusing frames this one is in (the knobs *_after count it)
     RisAheadKey ahead_key;
     Route ahead_route;
     LaunchBufs ahead_b;
@@ -2016,7 +2021,18 @@ struct Frame {
     restir_status alloc(const FramePlan& p);
     restir_status ris_stage(const FramePlan& p);
     restir_status ahead_prepare(const FramePlan& p, const Route& ris);
+    restir_status ahead_planes(int sets);
     restir_status look_ahead();
+    // every pending result marked invalid (counted per launch); this stream waits for their launches
+    restir_status ahead_invalidate() {
+        auto& a = c->ahead;
+        for (int i = 0; i < kRisRingSlots; i++) {
+            if (a.ring.slot[i].valid && a.slot_done[i]) HIP_TRY(hipStreamWaitEvent(st, a.slot_done[i], 0));
+            a.slot_done[i] = nullptr;
+        }
+        a.discards += ris_ring_drop(a.ring);
+        return RESTIR_OK;
+    }
     void ahead_consumed_hint() {
         c->ahead.stop_hint = c->ahead.consumed_ev[fb.set0] = c->ahead.consumed[fb.set0];
         c->ahead.stop_hint_stream = st;
@@ -2168,26 +2184,27 @@ restir_status Frame::ris_stage(const FramePlan& p) {
     // and this stream waits for its launch.
     bool took = false;
     const uint32_t streak_now = c->gbuf_streak_lights == c->scene_gen ? c->gbuf_streak + 1u : 1u;
+    ahead_streak = streak_now;
     if (c->ahead.on && p.fused && !p.temporal && p.handles && ris.phat && b.phat && ris.kernel == Kernel::kGbufRis &&
         ris.res_dead && ris.hom && ris.rp_out && !ris.dbg && !fb.records && streak_now >= c->ahead.after) {
         ST_TRY(ahead_prepare(p, ris));
-        if (c->ahead.valid && ris_ahead_key_equal(c->ahead.key, ahead_key)) {
-            if (c->ahead.done_ev) HIP_TRY(hipStreamWaitEvent(st, c->ahead.done_ev, 0));
-            c->ahead.done_ev = nullptr;
-            c->ahead.valid = false;
-            c->ahead.frames++;
-            fb.set0 = c->ahead.set;
+        auto& a = c->ahead;
+        const int slot = ris_ring_find(a.ring, ahead_key);
+        if (slot >= 0) {
+            if (a.slot_done[slot]) HIP_TRY(hipStreamWaitEvent(st, a.slot_done[slot], 0));
+            a.slot_done[slot] = nullptr;
+            ris_ring_take(a.ring, slot);
+            a.frames++;
+            fb.set0 = a.ring.slot[slot].set;
             took = true;
+            // what still waits is the frames' after this one, in order; anything else is stale: all of it goes
+            const int n = ris_ring_pending(a.ring);
+            bool chain = true;
+            for (int i = 1; i <= n; i++) chain = chain && ris_ring_find(a.ring, ris_ahead_nth(ahead_key, (uint32_t)i)) >= 0;
+            if (!chain) ST_TRY(ahead_invalidate());
         }
     }
-    if (!took) {
-        if (c->ahead.valid) {
-            c->ahead.valid = false;
-            c->ahead.discards++;
-        }
-        if (c->ahead.done_ev) HIP_TRY(hipStreamWaitEvent(st, c->ahead.done_ev, 0));
-        c->ahead.done_ev = nullptr;
-    }
+    if (!took) ST_TRY(ahead_invalidate());
     // kept by a frame that reuses it; a frame that traces replaces it once its launch is issued (any error return in
     // between leaves none)
     if (!ris_ask.gbuf_cached) c->gbuf.valid = false;
@@ -2253,14 +2270,11 @@ restir_status Frame::ahead_prepare(const FramePlan& p, const Route& ris) {
         a.stream_prio = a.prio;
     }
     // (the events a launch records within its dispatch, as the timing pairs are: timing_event_create)
-    for (hipEvent_t* e : {&a.done[0], &a.done[1], &a.consumed[0], &a.consumed[1], &a.ready})
-        if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableSystemFence));
-    const size_t px = (size_t)t.gwidth * t.gheight;
-    if (a.hnd.bytes < c->hnd[0].bytes || a.rp.bytes < px * 4) {
-        ahead_drop(c);   // (a result in the smaller planes)
-        ST_TRY(a.hnd.ensure(c->hnd[0].bytes));
-        ST_TRY(a.rp.ensure(px * 4));
-    }
+    for (int i = 0; i < kRisSets; i++)
+        for (hipEvent_t* e : {&a.done[i], &a.consumed[i]})
+            if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableSystemFence));
+    if (!a.ready) HIP_TRY(hipEventCreateWithFlags(&a.ready, hipEventDisableSystemFence));
+    ST_TRY(ahead_planes(2));
     RisAheadKey k;
     k.seed = c->seed; k.frame = frame;
     k.gbuf_epoch = c->gbuf_epoch; k.scene_gen = c->scene_gen; k.geom_gen = c->geom_gen; k.phat_build = c->phat_builds;
@@ -2282,12 +2296,37 @@ restir_status Frame::ahead_prepare(const FramePlan& p, const Route& ris) {
     return RESTIR_OK;
 }
 
+// Plane sets 1 .. sets - 1 at the view's size (set 0 is the frame's own)
+restir_status Frame::ahead_planes(int sets) {
+    auto& a = c->ahead;
+    const size_t px = (size_t)t.gwidth * t.gheight;
+    for (int i = 0; i < kRisSets - 1; i++) {
+        if (i >= sets - 1 && !a.hnd[i].p) continue;   // (a set beyond `sets` that exists follows the view's size too)
+        if (a.hnd[i].bytes >= c->hnd[0].bytes && a.rp[i].bytes >= px * 4) continue;
+        if (a.hnd[i].p || a.rp[i].p) ahead_drop(c);   // (a result in the smaller planes)
+        ST_TRY(a.hnd[i].ensure(c->hnd[0].bytes));
+        ST_TRY(a.rp[i].ensure(px * 4));
+    }
+    return RESTIR_OK;
+}
+
 // The next frame's RIS on the look-ahead stream, into the plane set this frame does not read: this frame's own launch
-// again under the key (seed, frame + 1, RIS, 0).  It reads the kept G-buffer, the tile flags and the table, which no
-// frame kernel writes while they stand, and writes planes whose last reader's event it waits for.
+// again under the key (seed, frame + 1, RIS, 0) -- from the batch streak on the next two frames' behind the results that
+// already wait, in one launch over the table into two sets neither read nor pending (DESIGN.md §6 "RIS batch").  It reads
+// the kept G-buffer, the tile flags and the table, which no frame kernel writes while they stand, and writes planes
+// whose last reader's event it waits for.
 restir_status Frame::look_ahead() {
     auto& a = c->ahead;
-    const int wset = ris_ahead_other_set(fb.set0);
+    // how many frames this launch serves (ris_batch_launch): none while enough results wait, one below the batch streak,
+    // two from it on -- the frames after the last one a result waits for
+    const bool batching = ahead_streak >= std::max(a.batch_after, a.after);
+    const int sets = ris_batch_sets(a.batch, a.batch_form);
+    if (a.batch == 2u && batching) ST_TRY(ahead_planes(sets));   // (the planes of sets 2 ..: from the first batch on)
+    const int pending = ris_ring_pending(a.ring);
+    const int n = ris_batch_launch(a.batch, a.batch_form, batching, pending);
+    if (!n) return RESTIR_OK;
+    int wset[2] = {0, 0}, slots[2] = {0, 0};
+    if (!ris_ring_pick(ris_ring_busy(a.ring, fb.set0), n, sets, wset)) return fail(RESTIR_ERR_STATE, "RIS look-ahead: no free plane set");
     if (!a.ready_ok || a.ready_epoch != c->gbuf_epoch || a.ready_build != c->phat_builds) {
         // the G-buffer and the table were written on the frame's stream: once per build
         HIP_TRY(hipEventRecord(a.ready, st));
@@ -2296,21 +2335,35 @@ restir_status Frame::look_ahead() {
         a.ready_epoch = c->gbuf_epoch;
         a.ready_build = c->phat_builds;
     }
-    if (a.consumed_ev[wset]) HIP_TRY(hipStreamWaitEvent(a.stream, a.consumed_ev[wset], 0));
-    a.consumed_ev[wset] = nullptr;
-    LaunchBufs b = ahead_b;
-    b.key = restir_rng_key(c->seed, frame + 1u, RESTIR_STAGE_RIS, 0);
-    FrameBufs out = fb;
-    out.set0 = wset;
-    b.hout = out.h(0);
-    b.rp_out = out.rp(0);
-    a.stop_hint = a.done[wset];
+    // (frames.ahead_serial with frames.ahead = 1: behind this frame's last launch, which recorded its set's `consumed`)
+    if (a.serial && a.on == 1u && a.consumed_ev[fb.set0]) HIP_TRY(hipStreamWaitEvent(a.stream, a.consumed_ev[fb.set0], 0));
+    RisAheadKey keys[2];
+    RisBatchOut out[2];
+    for (int i = 0; i < n; i++) {
+        if (a.consumed_ev[wset[i]]) HIP_TRY(hipStreamWaitEvent(a.stream, a.consumed_ev[wset[i]], 0));
+        a.consumed_ev[wset[i]] = nullptr;
+        keys[i] = ris_ahead_nth(ahead_key, (uint32_t)(pending + 1 + i));
+        FrameBufs o = fb;
+        o.set0 = wset[i];
+        out[i].key = restir_rng_key(c->seed, keys[i].frame, RESTIR_STAGE_RIS, 0);
+        out[i].h = o.h(0);
+        out[i].rp = o.rp(0);
+    }
+    // the launch's done event is its last set's: that set stays busy until both results were taken or dropped
+    const hipEvent_t done = a.done[wset[n - 1]];
+    a.stop_hint = done;
     a.stop_hint_stream = a.stream;
-    TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ahead_route, s, view, f, b, a.stream));
-    a.done_ev = a.done[wset];
-    a.set = wset;
-    a.key = ris_ahead_next(ahead_key);
-    a.valid = true;
+    if (n == 1) {
+        LaunchBufs b = ahead_b;
+        b.key = out[0].key;
+        b.hout = out[0].h;
+        b.rp_out = out[0].rp;
+        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_primary_ris(ahead_route, s, view, f, b, a.stream));
+    } else {
+        TIMED(c, RESTIR_K_PRIMARY_RIS, launch_gbuf_ris_phat_batch(ahead_route, s, view, f, ahead_b, out, a.stream));
+    }
+    if (!ris_ring_push(a.ring, n, keys, wset, slots)) return fail(RESTIR_ERR_STATE, "RIS look-ahead: the result ring is full");
+    for (int i = 0; i < n; i++) a.slot_done[slots[i]] = done;
     return RESTIR_OK;
 }
 
@@ -4807,6 +4860,10 @@ restir_status restir_set_tuning(restir_ctx* c, const char* key, int value) {
     else if (!std::strcmp(key, "ris.phat_max_mb")) t.ris_phat_max_mb = v;
     else if (!std::strcmp(key, "frames.ahead")) { if (v > 2) return fail(RESTIR_ERR_INVALID, "frames.ahead: 0 (off), 1 or 2 (RIS enqueued first)"); c->ahead.on = v; }
     else if (!std::strcmp(key, "frames.ahead_after")) { if (v < 1) return fail(RESTIR_ERR_INVALID, "frames.ahead_after: >= 1"); c->ahead.after = v; }
+    else if (!std::strcmp(key, "frames.batch")) { if (v < 1 || v > 2) return fail(RESTIR_ERR_INVALID, "frames.batch: 1 or 2 (frames per look-ahead launch)"); c->ahead.batch = v; }
+    else if (!std::strcmp(key, "frames.batch_after")) { if (v < 1) return fail(RESTIR_ERR_INVALID, "frames.batch_after: >= 1"); c->ahead.batch_after = v; }
+    else if (!std::strcmp(key, "frames.batch_form")) { if (v > 1) return fail(RESTIR_ERR_INVALID, "frames.batch_form: 0 or 1"); c->ahead.batch_form = v; }
+    else if (!std::strcmp(key, "frames.ahead_serial")) { if (v > 1) return fail(RESTIR_ERR_INVALID, "frames.ahead_serial: 0 or 1"); c->ahead.serial = v; }
     else if (!std::strcmp(key, "frames.ahead_prio")) { if (v > 1) return fail(RESTIR_ERR_INVALID, "frames.ahead_prio: 0 or 1"); c->ahead.prio = v; }
     else if (!std::strcmp(key, "primary.tl")) t.primary_tl = v;
     else if (!std::strcmp(key, "gbuf.reuse")) t.gbuf_reuse = v;

@@ -56,4 +56,94 @@ inline RisAheadKey ris_ahead_next(RisAheadKey k) {
 // writes: the other
 inline int ris_ahead_other_set(int set) { return set ^ 1; }
 
+// ---- RIS batch (DESIGN.md §6 "RIS batch"): one look-ahead launch may serve two frames, so results wait in a small ring.
+// Plane set 0 is the frame's own (hnd[0], rp[0]); sets 1 .. kRisSets - 1 are the look-ahead's.  A result is pending from
+// its launch until a frame takes it or everything pending is dropped; its set is busy that long, and the set a frame
+// reads is busy for that frame.  tests/cpp/ris_batch_ring.cpp walks every reachable state of both cadences.
+
+constexpr int kRisSets = 4;        // cadence (a) uses 3 of them, (b) all 4 (ris_batch_sets)
+constexpr int kRisRingSlots = 3;   // cadence (b) launches two results with one still pending
+
+// The key of the n-th frame after `k` on the same view (n = 1: ris_ahead_next)
+inline RisAheadKey ris_ahead_nth(RisAheadKey k, uint32_t n) {
+    k.frame += n;
+    return k;
+}
+
+struct RisRingSlot {
+    bool valid = false;
+    int set = 0;           // the plane set the result lies in
+    uint64_t launch = 0;   // the look-ahead launch that wrote it (RisRing::launches at that time): a batch's two share one
+    RisAheadKey key;
+};
+struct RisRing {
+    RisRingSlot slot[kRisRingSlots];
+    uint64_t launches = 0;
+};
+
+inline int ris_ring_pending(const RisRing& r) {
+    int n = 0;
+    for (const RisRingSlot& s : r.slot) n += s.valid ? 1 : 0;
+    return n;
+}
+// The sets no launch may write while a frame reads `read_set`: that one and every pending result's (bit s: set s)
+inline uint32_t ris_ring_busy(const RisRing& r, int read_set) {
+    uint32_t m = 1u << read_set;
+    for (const RisRingSlot& s : r.slot)
+        if (s.valid) m |= 1u << s.set;
+    return m;
+}
+// The pending result keyed `k` (-1: none)
+inline int ris_ring_find(const RisRing& r, const RisAheadKey& k) {
+    for (int i = 0; i < kRisRingSlots; i++)
+        if (r.slot[i].valid && ris_ahead_key_equal(r.slot[i].key, k)) return i;
+    return -1;
+}
+// The n lowest of the first `sets` plane sets outside `busy`, ascending; false: fewer than n are free
+inline bool ris_ring_pick(uint32_t busy, int n, int sets, int* out) {
+    int got = 0;
+    for (int s = 0; s < sets && got < n; s++)
+        if (!((busy >> s) & 1u)) out[got++] = s;
+    return got == n;
+}
+// One launch's n results (keys[i] in sets[i]) become pending; slots[i]: where.  false: the ring has no room (nothing changed)
+inline bool ris_ring_push(RisRing& r, int n, const RisAheadKey* keys, const int* sets, int* slots) {
+    if (ris_ring_pending(r) + n > kRisRingSlots) return false;
+    r.launches++;
+    int at = 0;
+    for (int i = 0; i < n; i++) {
+        while (r.slot[at].valid) at++;
+        r.slot[at].valid = true;
+        r.slot[at].set = sets[i];
+        r.slot[at].launch = r.launches;
+        r.slot[at].key = keys[i];
+        slots[i] = at;
+    }
+    return true;
+}
+inline void ris_ring_take(RisRing& r, int i) { r.slot[i].valid = false; }
+// Every pending result dropped: the number of launches with a result nobody took (restir_ahead_discards counts launches,
+// so a batch whose first result was taken and one whose results both wait count one each)
+inline uint32_t ris_ring_drop(RisRing& r) {
+    uint32_t n = 0;
+    for (int i = 0; i < kRisRingSlots; i++) {
+        if (!r.slot[i].valid) continue;
+        bool seen = false;
+        for (int j = 0; j < i; j++) seen = seen || (r.slot[j].valid && r.slot[j].launch == r.slot[i].launch);
+        n += seen ? 0u : 1u;
+    }
+    for (RisRingSlot& s : r.slot) s.valid = false;
+    return n;
+}
+
+// Cadence.  How many results the look-ahead beside a frame launches, with `pending` results waiting once the frame took
+// its own: below the batch streak one when none waits (the single look-ahead); from it on (`batching`) two -- form 0
+// when none waits, form 1 when at most one does, so that a batch runs beside two frames' last passes.
+inline int ris_batch_launch(uint32_t batch, uint32_t form, bool batching, int pending) {
+    if (batch == 2u && batching) return pending <= (form ? 1 : 0) ? 2 : 0;
+    return pending == 0 ? 1 : 0;
+}
+// Plane sets a cadence needs, set 0 included: the one being read, the pending ones, the two being written
+inline int ris_batch_sets(uint32_t batch, uint32_t form) { return batch == 2u ? (form ? 4 : 3) : 2; }
+
 }  // namespace romis

@@ -31,10 +31,32 @@ def instructions(obj, tmp):
     return [ln for ln in lines if ln]
 
 
+def kernel_text(ins, name):
+    """the lines of symbol `name` in a unit's disassembly: from its label to the next symbol's, without the padding behind
+    its s_endpgm, and with the pc-relative literal behind an s_getpc_b64 (the distance to a constant table, which moves
+    when another kernel joins the unit) replaced by a token"""
+    out, on, getpc = [], False, -9
+    for ln in ins:
+        m = re.match(r"^<(\S+)>:$", ln)
+        if m:
+            on = m.group(1) == name
+        elif on:
+            if ln.startswith("s_getpc_b64"):
+                getpc = len(out)
+            elif len(out) - getpc <= 2 and re.match(r"^s_add_u32 (s\d+), \1, 0x[0-9a-f]+$", ln):
+                ln = re.sub(r"0x[0-9a-f]+$", "<pcrel>", ln)
+            out.append(ln)
+    while out and (out[-1].startswith("s_nop") or out[-1].startswith("s_code_end") or out[-1] == "..."):
+        out.pop()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("other")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "history", "device_code.json"))
+    ap.add_argument("--kernels", nargs="*", default=[], metavar="UNIT:KERNEL",
+                    help="also compare single kernels of a unit that differs, e.g. phat_table.hip.o:k_phat_table")
     a = ap.parse_args()
     here = {os.path.basename(p): p for p in glob.glob(os.path.join(ROOT, "romis_amd", "_build", "*.hip.o"))}
     there = {os.path.basename(p): p for p in glob.glob(os.path.join(os.path.abspath(a.other), "romis_amd", "_build", "*.hip.o"))}
@@ -49,12 +71,23 @@ def main():
                     rec[label] = {"sha256": hashlib.sha256("\n".join(ins).encode()).hexdigest()[:16], "lines": len(ins)}
             rec["equal"] = "this" in rec and "other" in rec and rec["this"] == rec["other"]
             res["units"][name] = rec
+        for uk in a.kernels:
+            unit, _, kern = uk.partition(":")
+            rec = {}
+            for label, objs in (("this", here), ("other", there)):
+                if unit in objs:
+                    ins = kernel_text(instructions(objs[unit], tmp), kern)
+                    rec[label] = {"sha256": hashlib.sha256("\n".join(ins).encode()).hexdigest()[:16], "lines": len(ins)}
+            rec["equal"] = "this" in rec and "other" in rec and rec["this"] == rec["other"] and rec["this"]["lines"] > 0
+            res.setdefault("kernels", {})[uk] = rec
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1)
     for name, rec in res["units"].items():
         print(name, "equal" if rec["equal"] else ("only here" if "other" not in rec else "only there" if "this" not in rec else "DIFFERENT"),
               rec.get("this", {}).get("lines"))
+    for uk, rec in res.get("kernels", {}).items():
+        print(uk, "equal" if rec["equal"] else "DIFFERENT", rec.get("this", {}).get("lines"), rec.get("other", {}).get("lines"))
     return 0
 
 

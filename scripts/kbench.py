@@ -24,7 +24,8 @@ DEFAULTS = {"primary.lds": 1, "ris.lds": 1, "ris.compact": 1, "ris.late": 1, "mi
             "spatial.xcd_rows": 255, "spatial.xcd_cols": 255, "spatial.lean": 1, "spatial.th": 0, "spatial.handles": 1, "spatial.gather": 1, "spatial.n2h": 1,
             "fuse.primary_ris": 1, "fuse.temporal": 1, "bvh.max_leaf": 2, "final.lds": 1, "final.sort": 1, "final.fuse": 1, "final.qbvh": 2, "primary.tl": 1, "final.miss": 1, "layout.records": 0,
             "gbuf.reuse": 1, "final.lists": 1, "final.lists_after": 2, "final.lists_cap": 15,
-            "final.vis": 1, "final.vis_after": 4, "ris.phat": 1, "ris.phat_after": 4, "ris.phat_max_mb": 2048}
+            "final.vis": 1, "final.vis_after": 4, "ris.phat": 1, "ris.phat_after": 4, "ris.phat_max_mb": 2048,
+            "frames.batch": 2, "frames.batch_after": 8, "frames.batch_form": 1, "frames.ahead_serial": 0}
 
 VARIANTS = {
     "default": {},
