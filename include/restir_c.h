@@ -817,6 +817,51 @@ restir_status restir_history_variance_host(const float* mean, const float* S, co
                                            uint32_t miss_material, const restir_history_params* params,
                                            const restir_denoise_params* geo, float* var);
 
+/* The gather of restir_history_advance.  NEAREST (the default) takes the kept record of the nearest source pixel, as
+ * described above.  BILINEAR blends the 2 x 2 kept records around the continuous source position, SVGF's footprint with a
+ * test per tap, so that an advance no longer displaces the history by up to half a pixel:
+ *   1. Reasons 0 - 2 are unchanged, the range test on the nearest pixel included: they mark the same pixels in both modes.
+ *   2. (cfx, cfy) is the position the nearest pixel is rounded from, cfx = ((nx + 1.0f) * 0.5f) * (float)W; pixel x sits at
+ *      coordinate x.  x0 = floorf(cfx); fx = cfx - x0; gx = 1.0f - fx; the same for y.
+ *   3. Taps j = 0 .. 3 at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), G-buffer coordinates, with w0 = gx gy,
+ *      w1 = fx gy, w2 = gx fy, w3 = fx fy.  A tap contributes when it lies inside the image, w_j > 0 and the kept record
+ *      there passes steps 1's tests 3 - 5 and reasons 6 and 7 against the same d.
+ *   4. No tap contributes: the pixel is rejected with the reason the nearest pixel gives.  The nearest pixel is one of the
+ *      four, so every pixel NEAREST accepts from a given kept state BILINEAR accepts too, and a pixel both reject has the
+ *      same reason.
+ *   5. sum = the contributing w_j added in tap order; v_j = w_j / sum; per channel mean = sum_j v_j mean_j and
+ *      S = sum_j (v_j v_j) S_j, accumulated in tap order from the first term; nf = sum_j v_j (float)n_j,
+ *      n = (uint32_t)floorf(nf + 0.5f), raised to 1 from 0.  One contributing tap: its record verbatim.
+ *   6. The fold and the stored record are unchanged.
+ *   7. out_map: the flat index of the nearest pixel when it contributes, else of the contributing tap of the largest
+ *      weight (the first in tap order on a tie); 0xFFFFFFFF - reason for a rejected pixel.
+ * What S means afterwards.  restir_history_denoise reads S / (n - 1) as the variance of the kept mean.  A blend of
+ * independent means with weights v_j has variance sum_j v_j^2 S_j / (n_j - 1), with equal counts (sum_j v_j^2 S_j) / (n - 1).
+ * After a BILINEAR advance S is therefore the number whose S / (n - 1) estimates the variance of the mean, no longer the
+ * population variance of the samples; the fold continues from it.  The rule ignores the correlation the blend creates
+ * between neighbouring pixels.  The plain average sum_j v_j S_j was tried in a CPU prototype: it made the filtered result
+ * worse than this rule.
+ * The mode is context state: it may be set at any time, with or without an open history, holds for every later advance
+ * until set again -- across restir_history_begin / _end and across resets --, touches no frame and keeps the still view's
+ * caches.  Consecutive advances may use different modes: the state planes are the same.  A value above 1 or a NULL
+ * argument is RESTIR_ERR_INVALID and changes nothing.
+ * restir_history_advance_host is one whole advance in either mode, rows as restir_history_map_host's and
+ * restir_history_fold's: with NEAREST exactly those two in sequence.  kept_n_t and kept_material both NULL: nothing kept
+ * (mean_in, S_in and n_in are still required, and not read).  n_in is the kept count, image rows.  The outputs must not
+ * overlap the inputs.  RESTIR_ERR_INVALID, before anything is written: a NULL argument, one kept pointer without the
+ * other, an empty or too large size, max_frames outside 1 .. RESTIR_ACCUM_MAX_FRAMES, gather above 1, with BILINEAR an
+ * n_in above RESTIR_ACCUM_MAX_FRAMES. */
+typedef enum restir_history_gather { RESTIR_HISTORY_GATHER_NEAREST = 0, RESTIR_HISTORY_GATHER_BILINEAR = 1 } restir_history_gather;
+restir_status restir_history_gather_set(restir_ctx* ctx, uint32_t gather);
+restir_status restir_history_gather_get(restir_ctx* ctx, uint32_t* gather);
+/* pure host, the kernel's own text: one whole advance in either mode */
+restir_status restir_history_advance_host(const restir_camera_frame* prev_cam, uint32_t w, uint32_t h,
+                                          const float* cur_n_t, const float* cur_p_mat,
+                                          const float* kept_n_t, const uint32_t* kept_material,   /* both NULL: nothing kept */
+                                          const float* mean_in, const float* S_in, const uint32_t* n_in,
+                                          const float* x, uint32_t miss_material, uint32_t max_frames, uint32_t gather,
+                                          float* mean_out, float* S_out, uint32_t* n_out, uint32_t* out_map /* nullable */);
+
 /* ---- stage-level access for parity tests and profiling ---------------------------------------------- *
  * Buffers are the device SoA layout (DESIGN.md "Data layout"), one entry per pixel of the computed region
  * (row-major, y = 0 bottom), and for reservoirs [N][pixels]:

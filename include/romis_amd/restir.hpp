@@ -57,6 +57,9 @@ struct HistoryParams : restir_history_params {
     HistoryParams() { restir_history_params_default(this); }
 };
 
+// restir_history_gather: the nearest source pixel, or the 2 x 2 records around the continuous source position
+enum class HistoryGather : uint32_t { Nearest = RESTIR_HISTORY_GATHER_NEAREST, Bilinear = RESTIR_HISTORY_GATHER_BILINEAR };
+
 // The reference's own struct Features (src/utils/common.h:89-136) -> Features, field by field by the reference's
 // member names (any type with those members works, so the reference's header is not needed here).  The enums
 // keep their values: RayTraceMode {ReSTIR, RMIS, ROMIS} (common.h:25-29) = restir_mode,
@@ -438,6 +441,14 @@ public:
     // it synchronises
     void historyAdvance(const Camera& camera, uint32_t width, uint32_t height, uint32_t* map = nullptr) {
         check(restir_history_advance(ctx_, &camera, width, height, map), "restir_history_advance");
+    }
+    // how historyAdvance gathers the kept state (restir_history_gather_set): context state, Nearest by default, kept across
+    // historyBegin / historyEnd and resets
+    void historyGather(HistoryGather mode) { check(restir_history_gather_set(ctx_, static_cast<uint32_t>(mode)), "restir_history_gather_set"); }
+    HistoryGather historyGather() const {
+        uint32_t g = 0;
+        check(restir_history_gather_get(ctx_, &g), "restir_history_gather_get");
+        return static_cast<HistoryGather>(g);
     }
     void historyResolve(const Features* tone = nullptr) { check(restir_history_resolve(ctx_, tone), "restir_history_resolve"); }
     void historyDenoise(const DenoiseLumParams& params = DenoiseLumParams(), const Features* tone = nullptr, float* rgb = nullptr) {

@@ -197,6 +197,9 @@ class HistoryParams(C.Structure):
 # restir_history_advance's reasons beyond restir_frame_reproject's 0 .. 5
 RESTIR_HISTORY_REASON_MATERIAL = 6
 RESTIR_HISTORY_REASON_NO_HISTORY = 7
+# restir_history_gather
+RESTIR_HISTORY_GATHER_NEAREST = 0
+RESTIR_HISTORY_GATHER_BILINEAR = 1
 assert C.sizeof(HistoryParams) == 16
 
 RESTIR_MAX_TILES_X = 16
@@ -346,6 +349,13 @@ SIGNATURES = {
     "restir_history_map_host": (C.c_int, [C.POINTER(CameraFrame), C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
                                           C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "restir_history_gather_set": (C.c_int, [_P, C.c_uint32]),
+    "restir_history_gather_get": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "restir_history_advance_host": (C.c_int, [C.POINTER(CameraFrame), C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
+                                              C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
+                                              C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "restir_history_variance_host": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.POINTER(HistoryParams), C.POINTER(DenoiseParams), C.POINTER(C.c_float)]),

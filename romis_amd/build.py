@@ -253,7 +253,8 @@ CPP_PROGRAMS = [("render_scene.cpp", "render_scene"), ("render_threads.cpp", "re
                 ("write_outputs.cpp", "write_outputs"), ("update_scene.cpp", "update_scene"),
                 ("present_frames.cpp", "present_frames"), ("accumulate_frames.cpp", "accumulate_frames"),
                 ("exact_image.cpp", "exact_image"), ("denoise_frames.cpp", "denoise_frames"),
-                ("denoise_lum_frames.cpp", "denoise_lum_frames"), ("history_frames.cpp", "history_frames")]
+                ("denoise_lum_frames.cpp", "denoise_lum_frames"), ("history_frames.cpp", "history_frames"),
+                ("history_gather_frames.cpp", "history_gather_frames")]
 CPP_DIR = os.path.join(ROOT, "tests", "cpp")
 
 

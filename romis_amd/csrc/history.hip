@@ -7,7 +7,8 @@
 // in both axes.  A lane reads its 12 bytes of image, its three current guide records (48 B), the three kept records of
 // its source pixel (48 B, under the lane mask: a rejected pixel reads none) and writes the three records of the other set
 // (48 B), all as 16-byte loads and stores but the packed image.  Nothing is shared between lanes: no LDS, no barrier, no
-// atomics.  Every index is below W * H: the lane's own by the bounds test, the source's by reproject_source's range test.
+// atomics.  Every index is below W * H: the lane's own by the bounds test, the source's by reproject_source's range test,
+// a bilinear tap's by history_gather_bilinear's signed test before the index is formed.
 // The guide planes and the map are in G-buffer rows (y = 0 bottom), the image and the state planes in image rows: lane
 // (x, y) of the G-buffer is image pixel (x, H - 1 - y), and source (sx, sy) is state pixel (sx, H - 1 - sy).
 //
@@ -26,6 +27,34 @@ namespace {
 
 constexpr uint32_t kHistBlock = 256;
 
+// the kernel's Kept of history_gather_bilinear: the kept set's planes, image rows.  test reads the tap's (N, t) record and
+// the two 4-byte words the test needs, load the two records of a contributing tap.
+struct HistKeptDev {
+    const float4* a;
+    const float4* b;
+    const float4* c;
+    uint32_t W, H;
+    __device__ __forceinline__ void test(uint32_t tx, uint32_t ty, float& nx, float& ny, float& nz, float& t, uint32_t& mat,
+                                         uint32_t& n) const {
+        const size_t qi = (size_t)(H - 1u - ty) * W + tx;
+        const float4 ka = a[qi];
+        nx = ka.x; ny = ka.y; nz = ka.z; t = ka.w;
+        mat = __float_as_uint(c[qi].w);   // (stored clamped)
+        n = __float_as_uint(b[qi].w);
+    }
+    __device__ __forceinline__ void load(uint32_t tx, uint32_t ty, HistState& s) const {
+        const size_t qi = (size_t)(H - 1u - ty) * W + tx;
+        const float4 kb = b[qi], kc = c[qi];
+        s.mr = kb.x; s.mg = kb.y; s.mb = kb.z;
+        s.sr = kc.x; s.sg = kc.y; s.sb = kc.z;
+        s.n = __float_as_uint(kb.w);
+    }
+};
+
+// kGather == kHistGatherNearest is the kernel as it was before the mode existed, instruction for instruction
+// (scripts/device_code_diff.py).  kHistGatherBilinear: up to four taps per lane, each inside tap 24 bytes for its test and a
+// contributing one 32 more, all under the lane mask; neighbouring lanes' footprints overlap almost completely.
+template <uint32_t kGather>
 __global__ __launch_bounds__(kBlock) void k_history_advance(HistoryDev a) {
     const uint32_t x = blockIdx.x * kTileW + threadIdx.x, y = blockIdx.y * kTileH + threadIdx.y;
     const uint32_t W = a.prev_cam.W, H = a.prev_cam.H;
@@ -38,26 +67,42 @@ __global__ __launch_bounds__(kBlock) void k_history_advance(HistoryDev a) {
 
     uint32_t why = kHistNoHistory, sx = 0u, sy = 0u;
     HistState s{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0u};
-    if (a.fresh == 0u) {
-        float d;
-        why = history_source(a.prev_cam, cur_mat, a.miss_mat, cpf.x, cpf.y, cpf.z, sx, sy, d);
-        if (why == kReprojOk) {   // (loads under the lane mask)
-            const size_t qi = (size_t)(H - 1u - sy) * W + sx;
-            const float4 ka = a.in_a[qi], kb = a.in_b[qi], kc = a.in_c[qi];
-            why = history_accept(ka.x, ka.y, ka.z, ka.w, __float_as_uint(kc.w), __float_as_uint(kb.w), cnt.x, cnt.y, cnt.z,
-                                 cur_mat, a.miss_mat, d);
-            if (why == kReprojOk) {
-                s.mr = kb.x; s.mg = kb.y; s.mb = kb.z;
-                s.sr = kc.x; s.sg = kc.y; s.sb = kc.z;
-                s.n = __float_as_uint(kb.w);
+    if constexpr (kGather == kHistGatherBilinear) {
+        uint32_t src = 0u;
+        if (a.fresh == 0u) {
+            float d, cfx, cfy;
+            why = history_source_at(a.prev_cam, cur_mat, a.miss_mat, cpf.x, cpf.y, cpf.z, sx, sy, d, cfx, cfy);
+            if (why == kReprojOk)   // (loads under the lane mask)
+                why = history_gather_bilinear(HistKeptDev{a.in_a, a.in_b, a.in_c, W, H}, W, H, sx, sy, cfx, cfy, d, cnt.x, cnt.y,
+                                              cnt.z, cur_mat, a.miss_mat, s, src);
+        }
+        history_fold(xr, xg, xb, a.max_frames, s);
+        a.out_a[pi] = cnt;
+        a.out_b[pi] = make_float4(s.mr, s.mg, s.mb, __uint_as_float(s.n));
+        a.out_c[pi] = make_float4(s.sr, s.sg, s.sb, __uint_as_float(cur_mat));
+        if (a.map) a.map[gi] = why == kReprojOk ? src : 0xFFFFFFFFu - why;
+    } else {
+        if (a.fresh == 0u) {
+            float d;
+            why = history_source(a.prev_cam, cur_mat, a.miss_mat, cpf.x, cpf.y, cpf.z, sx, sy, d);
+            if (why == kReprojOk) {   // (loads under the lane mask)
+                const size_t qi = (size_t)(H - 1u - sy) * W + sx;
+                const float4 ka = a.in_a[qi], kb = a.in_b[qi], kc = a.in_c[qi];
+                why = history_accept(ka.x, ka.y, ka.z, ka.w, __float_as_uint(kc.w), __float_as_uint(kb.w), cnt.x, cnt.y, cnt.z,
+                                     cur_mat, a.miss_mat, d);
+                if (why == kReprojOk) {
+                    s.mr = kb.x; s.mg = kb.y; s.mb = kb.z;
+                    s.sr = kc.x; s.sg = kc.y; s.sb = kc.z;
+                    s.n = __float_as_uint(kb.w);
+                }
             }
         }
+        history_fold(xr, xg, xb, a.max_frames, s);
+        a.out_a[pi] = cnt;
+        a.out_b[pi] = make_float4(s.mr, s.mg, s.mb, __uint_as_float(s.n));
+        a.out_c[pi] = make_float4(s.sr, s.sg, s.sb, __uint_as_float(cur_mat));
+        if (a.map) a.map[gi] = why == kReprojOk ? sy * W + sx : 0xFFFFFFFFu - why;
     }
-    history_fold(xr, xg, xb, a.max_frames, s);
-    a.out_a[pi] = cnt;
-    a.out_b[pi] = make_float4(s.mr, s.mg, s.mb, __uint_as_float(s.n));
-    a.out_c[pi] = make_float4(s.sr, s.sg, s.sb, __uint_as_float(cur_mat));
-    if (a.map) a.map[gi] = why == kReprojOk ? sy * W + sx : 0xFFFFFFFFu - why;
 }
 
 __global__ __launch_bounds__(kHistBlock) void k_history_resolve(const float4* __restrict__ b, float* __restrict__ rgb,
@@ -149,7 +194,10 @@ hipError_t launch_history_advance(const HistoryDev& a, hipStream_t stream) {
     if (!W || !H) return hipSuccess;
     const uint32_t gy = (H + kTileH - 1u) / kTileH;
     if (gy > 65535u || (uint64_t)W * H > 0xFFFFFFF0ull - kHistReasons) return hipErrorInvalidValue;   // a flat index is a map word
-    hipLaunchKernelGGL(k_history_advance, dim3((W + kTileW - 1u) / kTileW, gy), dim3(kTileW, kTileH), 0, stream, a);
+    const dim3 grid((W + kTileW - 1u) / kTileW, gy), block(kTileW, kTileH);
+    if (a.gather == kHistGatherBilinear) hipLaunchKernelGGL(k_history_advance<kHistGatherBilinear>, grid, block, 0, stream, a);
+    else if (a.gather == kHistGatherNearest) hipLaunchKernelGGL(k_history_advance<kHistGatherNearest>, grid, block, 0, stream, a);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

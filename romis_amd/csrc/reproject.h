@@ -39,7 +39,11 @@ struct ReprojCam {
 // quat * vec3 (type_quat.inl:347-354) of the conjugate, device_math.h qrotate's expressions -- the pixel is the nearest
 // sample position to (-c.x / c.z / half_w, c.y / c.z / half_h).  d = glm::length(P - o), the depth the predecessor's
 // pixel must show.  Returns kReprojOk with (sx, sy), else kReprojBehind / kReprojOffScreen.
-ROMIS_HD uint32_t reproject_source(const ReprojCam& cam, float Px, float Py, float Pz, uint32_t& sx, uint32_t& sy, float& d) {
+// at (nullable): the continuous position (at[0], at[1]) the nearest pixel is rounded from -- pixel x sits at coordinate x, as
+// primary_pixel places its sample -- for the image history's bilinear gather (history.h); written only with kReprojOk or
+// kReprojOffScreen.  The same expressions either way: without `at` the function is what it was before the parameter existed.
+ROMIS_HD uint32_t reproject_source(const ReprojCam& cam, float Px, float Py, float Pz, uint32_t& sx, uint32_t& sy, float& d,
+                                   float* at = nullptr) {
     const float vx = Px - cam.ox, vy = Py - cam.oy, vz = Pz - cam.oz;
     d = sqrtf((vx * vx + vy * vy) + vz * vz);
     const float qx = -cam.qx, qy = -cam.qy, qz = -cam.qz, qw = cam.qw;
@@ -52,8 +56,14 @@ ROMIS_HD uint32_t reproject_source(const ReprojCam& cam, float Px, float Py, flo
     const float nx = (-r) / cam.half_w;
     const float s = cy / cz;
     const float ny = s / cam.half_h;
-    const float fx = floorf(((nx + 1.0f) * 0.5f) * (float)cam.W + 0.5f);
-    const float fy = floorf(((ny + 1.0f) * 0.5f) * (float)cam.H + 0.5f);
+    const float cfx = ((nx + 1.0f) * 0.5f) * (float)cam.W;
+    const float cfy = ((ny + 1.0f) * 0.5f) * (float)cam.H;
+    const float fx = floorf(cfx + 0.5f);
+    const float fy = floorf(cfy + 0.5f);
+    if (at) {
+        at[0] = cfx;
+        at[1] = cfy;
+    }
     if (!(fx >= 0.0f && fx < (float)cam.W && fy >= 0.0f && fy < (float)cam.H)) return kReprojOffScreen;   // NaN too
     sx = (uint32_t)fx;
     sy = (uint32_t)fy;

@@ -489,6 +489,7 @@ struct restir_ctx {
     struct {
         bool open = false, have = false;
         uint32_t var_fused = 1;   // tuning history.var_fused: the variance plane in one launch (0: three)
+        uint32_t gather = RESTIR_HISTORY_GATHER_NEAREST;   // restir_history_gather_set: outlives begin / end and resets
         restir_history_params params{};
         uint32_t width = 0, height = 0;
         int set = 0;
@@ -3587,6 +3588,7 @@ restir_status restir_history_advance(restir_ctx* c, const restir_camera* cam, ui
     a.in_a = pl + (size_t)(3 * in) * npx; a.in_b = a.in_a + npx; a.in_c = a.in_b + npx;
     a.out_a = pl + (size_t)(3 * out) * npx; a.out_b = a.out_a + npx; a.out_c = a.out_b + npx;
     a.map = out_map ? hs.map.as<uint32_t>() : nullptr;
+    a.gather = hs.gather;
     HIP_TRY(launch_history_advance(a, c->stream));
     hs.set = out;
     hs.have = true;
@@ -3598,6 +3600,23 @@ restir_status restir_history_advance(restir_ctx* c, const restir_camera* cam, ui
         HIP_TRY(hipMemcpyAsync(out_map, hs.map.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
+    return RESTIR_OK;
+}
+
+// the mode is plain context state: no frame, no cache and no open history is touched
+restir_status restir_history_gather_set(restir_ctx* c, uint32_t gather) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (gather > RESTIR_HISTORY_GATHER_BILINEAR) return fail(RESTIR_ERR_INVALID, "restir_history_gather_set: gather %u (0 or 1)", gather);
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->hist.gather = gather;
+    return RESTIR_OK;
+}
+
+restir_status restir_history_gather_get(restir_ctx* c, uint32_t* gather) {
+    if (!c) return fail(RESTIR_ERR_INVALID, "ctx is NULL");
+    if (!gather) return fail(RESTIR_ERR_INVALID, "restir_history_gather_get: gather is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *gather = c->hist.gather;
     return RESTIR_OK;
 }
 

@@ -439,6 +439,17 @@ class Renderer:
         self._history_shape = (height, width)
         return smap
 
+    def history_gather(self, mode: int | None = None) -> int:
+        """restir_history_gather_set / _get: how history_advance gathers the kept state -- HISTORY_GATHER_NEAREST (the
+        default) from the nearest source pixel, HISTORY_GATHER_BILINEAR from the 2 x 2 records around the continuous source
+        position.  Sets the mode when one is given; returns the current mode.  Context state: it holds until set again,
+        across history_begin / history_end and resets."""
+        if mode is not None:
+            check(self.lib, self.lib.restir_history_gather_set(self.ctx, int(mode)), "restir_history_gather_set")
+        g = C.c_uint32()
+        check(self.lib, self.lib.restir_history_gather_get(self.ctx, C.byref(g)), "restir_history_gather_get")
+        return g.value
+
     def history_resolve(self, features=None) -> None:
         """restir_history_resolve: the history's mean becomes the last image -- tone mapped by `features`, or its own bits
         without."""
@@ -910,6 +921,11 @@ def denoise_host(rgb, n_t, p_mat, miss_material: int, params=None) -> np.ndarray
     return out
 
 
+# restir_history_gather: Renderer.history_gather's modes
+HISTORY_GATHER_NEAREST = _abi.RESTIR_HISTORY_GATHER_NEAREST
+HISTORY_GATHER_BILINEAR = _abi.RESTIR_HISTORY_GATHER_BILINEAR
+
+
 def history_params(max_frames: int | None = None, spatial_below: int | None = None) -> _abi.HistoryParams:
     """restir_history_params_default, with the given fields replaced."""
     lib = _abi.load_library()
@@ -966,6 +982,41 @@ def history_map_host(prev_cam: _abi.CameraFrame, width: int, height: int, cur_gb
                                            kc.ctypes.data_as(UP) if kept is not None else None, miss_material,
                                            out.ctypes.data_as(UP)), "restir_history_map_host")
     return out
+
+
+def history_advance_host(prev_cam: _abi.CameraFrame, cur_gbuffer, kept, mean, S, n, x, miss_material: int, max_frames: int,
+                         gather: int = _abi.RESTIR_HISTORY_GATHER_NEAREST):
+    """restir_history_advance_host (pure host): one whole history_advance in either gather mode, bit for bit.  prev_cam: the
+    derived CameraFrame of the advance before; cur_gbuffer: (n_t, p_mat) of the new camera and kept: (n_t, material) the
+    history kept from the advance before, or None: nothing kept -- all in rows y = 0 bottom; mean, S [h][w][3] float32
+    and n [h][w] uint32 (image rows): the kept state; x [h][w][3]: the image.  Returns (mean, S, n, map): the new state and
+    the map [h][w] uint32 (rows y = 0 bottom)."""
+    lib = _abi.load_library()
+    FP, UP = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    xa = np.ascontiguousarray(x, np.float32)
+    if xa.ndim != 3 or xa.shape[2] != 3:
+        raise ValueError("history_advance_host: x must be [h][w][3]")
+    h, w = xa.shape[:2]
+    px = w * h
+    cn, cp = (np.ascontiguousarray(a, np.float32) for a in cur_gbuffer)
+    if cn.size != 4 * px or cp.size != 4 * px:
+        raise ValueError("history_advance_host: the G-buffer must hold 4 floats per pixel")
+    kn = km = None
+    if kept is not None:
+        kn, km = np.ascontiguousarray(kept[0], np.float32), np.ascontiguousarray(kept[1], np.uint32)
+        if kn.size != 4 * px or km.size != px:
+            raise ValueError("history_advance_host: kept must be (n_t, material) of the image's size")
+    m, s, na = np.ascontiguousarray(mean, np.float32), np.ascontiguousarray(S, np.float32), np.ascontiguousarray(n, np.uint32)
+    if m.size != xa.size or s.size != xa.size or na.size != px:
+        raise ValueError("history_advance_host: mean, S and n must have x's size")
+    mo, so, no, smap = np.zeros_like(xa), np.zeros_like(xa), np.zeros((h, w), np.uint32), np.zeros((h, w), np.uint32)
+    check(lib, lib.restir_history_advance_host(
+        C.byref(prev_cam), w, h, cn.ctypes.data_as(FP), cp.ctypes.data_as(FP),
+        kn.ctypes.data_as(FP) if kept is not None else None, km.ctypes.data_as(UP) if kept is not None else None,
+        m.ctypes.data_as(FP), s.ctypes.data_as(FP), na.ctypes.data_as(UP), xa.ctypes.data_as(FP), miss_material, max_frames,
+        int(gather), mo.ctypes.data_as(FP), so.ctypes.data_as(FP), no.ctypes.data_as(UP), smap.ctypes.data_as(UP)),
+        "restir_history_advance_host")
+    return mo, so, no, smap
 
 
 def history_variance_host(mean, S, n, n_t, p_mat, miss_material: int, params=None, geo=None) -> np.ndarray:

@@ -56,7 +56,9 @@ def main():
     ap.add_argument("other")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "history", "device_code.json"))
     ap.add_argument("--kernels", nargs="*", default=[], metavar="UNIT:KERNEL",
-                    help="also compare single kernels of a unit that differs, e.g. phat_table.hip.o:k_phat_table")
+                    help="also compare single kernels of a unit that differs, e.g. phat_table.hip.o:k_phat_table; "
+                         "UNIT:KERNEL=OTHER_KERNEL where the other tree names the kernel differently (a kernel that became a "
+                         "template's instantiation)")
     a = ap.parse_args()
     here = {os.path.basename(p): p for p in glob.glob(os.path.join(ROOT, "romis_amd", "_build", "*.hip.o"))}
     there = {os.path.basename(p): p for p in glob.glob(os.path.join(os.path.abspath(a.other), "romis_amd", "_build", "*.hip.o"))}
@@ -73,10 +75,11 @@ def main():
             res["units"][name] = rec
         for uk in a.kernels:
             unit, _, kern = uk.partition(":")
+            kern, _, other_kern = kern.partition("=")
             rec = {}
             for label, objs in (("this", here), ("other", there)):
                 if unit in objs:
-                    ins = kernel_text(instructions(objs[unit], tmp), kern)
+                    ins = kernel_text(instructions(objs[unit], tmp), other_kern if label == "other" and other_kern else kern)
                     rec[label] = {"sha256": hashlib.sha256("\n".join(ins).encode()).hexdigest()[:16], "lines": len(ins)}
             rec["equal"] = "this" in rec and "other" in rec and rec["this"] == rec["other"] and rec["this"]["lines"] > 0
             res.setdefault("kernels", {})[uk] = rec

@@ -7,6 +7,10 @@ headline bench (bench.py); nothing here is a pass / fail bar.
     python scripts/history_bench.py --ab PARENT_TREE [--rounds 5] [--out profiles/history/bench_ab.json]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python scripts/history_bench.py --child trace
     python scripts/history_bench.py --steps-from DIR [--out profiles/history/kernels.json]
+    ... --gather nearest|bilinear|both on the loop, the trace child and --quality: restir_history_gather_set's mode.  "both"
+    runs the two modes side by side -- the loop's history arms per mode, interleaved; the trace child's twelve frames once
+    per mode in one process, so that --steps-from reports both instantiations of k_history_advance from one run; one
+    --quality process per mode -- and every record names its mode (profiles/history_bilinear/).
 
 Scene: the nightclub with 128 point lights at 1920 x 1080, the camera yawing 0.1 degree per frame
 (scripts/reproject_bench.py's motion), C2's features (one pass, no temporal reuse) and C3's (two passes, temporal reuse,
@@ -51,6 +55,7 @@ CAPS = [8, 16, 32, 64]
 BELOWS = [2, 4, 8]
 AT = [4, 16, 64]
 OUT_DIR = os.path.join(ROOT, "profiles", "history")
+GATHERS = {"nearest": 0, "bilinear": 1}   # RESTIR_HISTORY_GATHER_*
 
 
 def new_renderer():
@@ -82,10 +87,11 @@ def render_loop(r, f):
     return render
 
 
-def child_loop(cfg, arm, frames, warmup):
+def child_loop(cfg, arm, frames, warmup, gather):
     from romis_amd import _abi
     w, h = SIZE
     r = new_renderer()
+    r.history_gather(GATHERS[gather])
     f = _abi.default_features(**SETS[cfg])
     tone = _abi.default_features()
     render = render_loop(r, f)
@@ -113,13 +119,14 @@ def child_loop(cfg, arm, frames, warmup):
             im.wait()
     r.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / frames
-    print(json.dumps({"what": "loop", "cfg": cfg, "arm": arm, "frames": frames, "ms_per_frame": ms,
+    print(json.dumps({"what": "loop", "cfg": cfg, "arm": arm, "gather": gather, "frames": frames, "ms_per_frame": ms,
                       "guide_builds": r.denoise_guide_builds()}))
     r.close()
 
 
-def child_trace():
-    """a short history loop for a kernel trace, and device-to-device copies of the bytes an advance moves"""
+def child_trace(gathers):
+    """a short history loop per gather mode for a kernel trace, and device-to-device copies of the bytes a nearest advance
+    moves"""
     import torch
 
     from romis_amd import _abi
@@ -127,13 +134,16 @@ def child_trace():
     r = new_renderer()
     f = _abi.default_features(**C2)
     render = render_loop(r, f)
-    r.history_begin()
-    for k in range(12):
-        cam = camera(k)
-        render(cam, None)
-        r.history_advance(cam, w, h)
-        r.history_denoise(download=False)
-    r.synchronize()
+    for gather in gathers:
+        r.history_gather(GATHERS[gather])
+        r.history_begin()
+        for k in range(12):
+            cam = camera(k)
+            render(cam, None)
+            r.history_advance(cam, w, h)
+            r.history_denoise(download=False)
+        r.synchronize()
+        r.history_end()
     r.close()
     half = w * h * 156 // 2   # a copy reads and writes its bytes: half the advance's traffic each way
     a = torch.empty(half, dtype=torch.uint8, device="cuda")
@@ -153,7 +163,7 @@ def figures(e):
     return dict(mse=e.mse, rel_mse=e.rel_mse, mae=e.mae, bias=e.bias, max_abs=e.max_abs, nonfinite=e.nonfinite)
 
 
-def child_quality(cfg, caps, belows, half):
+def child_quality(cfg, caps, belows, half, gather):
     """per (max_frames, spatial_below) one moving sequence of max(AT) frames; the four arms' figures at every frame of AT.
     half: at frame max(AT) also the host filter over the downloaded history with the variance plane as it is and scaled by
     1/2 (what the cap's over-statement could cost), against the downloaded exact image"""
@@ -165,6 +175,7 @@ def child_quality(cfg, caps, belows, half):
     f = _abi.default_features(**SETS[cfg])
     render = render_loop(r, f)
     miss = len(scene.bench_scene(NAME).meshes)
+    r.history_gather(GATHERS[gather])
     for cap in caps:
         for below in belows:
             hp = restir.history_params(max_frames=cap, spatial_below=below)
@@ -177,7 +188,7 @@ def child_quality(cfg, caps, belows, half):
                 r.history_advance(cam, w, h)
                 if k + 1 not in AT:
                     continue
-                rec = {"what": "quality", "cfg": cfg, "max_frames": cap, "spatial_below": below, "frame": k + 1}
+                rec = {"what": "quality", "cfg": cfg, "gather": gather, "max_frames": cap, "spatial_below": below, "frame": k + 1}
                 raw = r.download_rgb(w, h)
                 exact = r.render_exact(cam, w, h, f)   # consumes no frame index, leaves the frame path's caches
                 r.reference_set()
@@ -254,7 +265,10 @@ def steps_from(d):
     per = {}
     for row in rows:
         name = row.get("Kernel_Name", "")
-        key = next((k for k in ("k_history_advance", "k_history_resolve", "k_history_var_fused", "k_history_var", "k_denoise_var_spatial", "k_denoise_level")
+        if "k_history_advance" in name:   # the instantiation: <1u> demangled, ILj1E mangled
+            tail = name.split("k_history_advance", 1)[1]
+            name = "k_history_advance<bilinear>" if tail.startswith(("<1", "ILj1E")) else "k_history_advance<nearest>"
+        key = next((k for k in ("k_history_advance<bilinear>", "k_history_advance<nearest>", "k_history_resolve", "k_history_var_fused", "k_history_var", "k_denoise_var_spatial", "k_denoise_level")
                     if k in name), None)
         if key:
             per.setdefault(key, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
@@ -275,16 +289,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps-from")
     ap.add_argument("--child", nargs="+")
+    ap.add_argument("--gather", choices=["nearest", "bilinear", "both"], default="nearest", help="restir_history_gather_set's mode")
     ap.add_argument("--out")
     a = ap.parse_args()
+    gathers = ["nearest", "bilinear"] if a.gather == "both" else [a.gather]
     if a.child:
         kind = a.child[0]
         if kind == "loop":
-            child_loop(a.child[1], a.child[2], int(a.child[3]), int(a.child[4]))
+            child_loop(a.child[1], a.child[2], int(a.child[3]), int(a.child[4]), gathers[0])
         elif kind == "trace":
-            child_trace()
+            child_trace(gathers)
         elif kind == "quality":
-            child_quality(a.child[1], [int(v) for v in a.child[2].split(",")], [int(v) for v in a.child[3].split(",")], a.child[4] == "1")
+            child_quality(a.child[1], [int(v) for v in a.child[2].split(",")], [int(v) for v in a.child[3].split(",")], a.child[4] == "1",
+                          gathers[0])
         return
     os.makedirs(OUT_DIR, exist_ok=True)
     if a.ab:
@@ -294,18 +311,24 @@ def main():
     elif a.quality:
         recs = []
         for cfg in a.cfgs.split(","):
-            recs += run_child(["--child", "quality", cfg, a.caps, a.belows, "1" if a.half else "0"], limit=900)
-            print(json.dumps(recs[-1])[:300], flush=True)
-        res, out = {"quality": recs, "size": SIZE, "yaw_step_deg": YAW_STEP}, a.out or os.path.join(OUT_DIR, "quality.json")
+            for g in gathers:
+                recs += run_child(["--child", "quality", cfg, a.caps, a.belows, "1" if a.half else "0", "--gather", g], limit=900)
+                print(json.dumps(recs[-1])[:300], flush=True)
+        res, out = {"quality": recs, "size": SIZE, "yaw_step_deg": YAW_STEP, "gather": a.gather}, a.out or os.path.join(OUT_DIR, "quality.json")
     else:
         runs = {}
+        # one mode: every arm, keyed cfg/arm as before; both: the baseline and the two history arms per mode, keyed cfg/arm/mode
+        arms = [(arm, gathers[0]) for arm in ARMS] if len(gathers) == 1 else \
+            [("present", "nearest")] + [(arm, g) for arm in ("history", "history_resolve") for g in gathers]
         for rep in range(a.reps):
             for cfg in a.cfgs.split(","):
-                for arm in (ARMS if rep % 2 == 0 else ARMS[::-1]):
-                    rec = run_child(["--child", "loop", cfg, arm, str(a.frames), str(a.warmup)])[0]
-                    runs.setdefault(f"{cfg}/{arm}", []).append(rec["ms_per_frame"])
+                for arm, g in (arms if rep % 2 == 0 else arms[::-1]):
+                    rec = run_child(["--child", "loop", cfg, arm, str(a.frames), str(a.warmup), "--gather", g])[0]
+                    key = f"{cfg}/{arm}" if len(gathers) == 1 or arm == "present" else f"{cfg}/{arm}/{g}"
+                    runs.setdefault(key, []).append(rec["ms_per_frame"])
                     print(json.dumps(rec), flush=True)
-        res = {"loop_ms_per_frame": {k: summary(v) for k, v in runs.items()}, "size": SIZE, "frames": a.frames, "yaw_step_deg": YAW_STEP}
+        res = {"loop_ms_per_frame": {k: summary(v) for k, v in runs.items()}, "size": SIZE, "frames": a.frames, "yaw_step_deg": YAW_STEP,
+               "gather": a.gather}
         out = a.out or os.path.join(OUT_DIR, "history.json")
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
